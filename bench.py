@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- series/sec (fwd+adjoint) for cdeint RK4, batch=32768, L=128, C=8, H=32 (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python bench.py --config 4 [--controller local|shared] [--adjoint] [--gpus N]     BASELINE configs[3] (see run_adaptive_config)
     python bench.py --config 5 [--method dopri5|rk4] [--controller local|shared] [--gpus N]   BASELINE configs[4] (see run_logode_config)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -19,8 +19,12 @@ communication is the all-reduce of the 8,448 parameter gradients, included in th
 ``--scaling strong`` (default; what BASELINE.json asks for: ONE 32768-series job on N GPUs) gives every rank
 32768 / N series -- below 16384 series per GPU cdeint switches to the workgroup-per-tile kernels (rk4_split.hip),
 which keep every SIMD busy down to 16 series per CU.  ``--scaling weak`` keeps 32768 series per rank.
-``python bench.py --gpus N`` without a torchrun environment re-executes itself under torch.distributed.run with N
-ranks on 127.0.0.1.
+``python bench.py --gpus N`` without a torchrun environment runs itself under torch.distributed.run with N
+ranks on 127.0.0.1 (a child process).
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step computed -- the solution, the gradient of the
+initial state and the field's parameter gradients -- as DIR/<name>.npy (float32), at most 64 MB in all (see dump_outputs).
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import gc
@@ -110,6 +114,61 @@ def emit(line):
         pass
     fd = 1 if _REAL_STDOUT is None else _REAL_STDOUT
     os.write(fd, (line + "\n").encode())
+
+
+DUMP_MAX_BYTES = 64 << 20              # --dump-outputs: all files together
+DUMP_BATCHED_MAX_BYTES = 16 << 20      # one per-series array above this is written as a fixed sample of its series
+
+
+def step_outputs(out, z, module):
+    """What a caller of the timed step receives: the solution, the gradient of the initial state (None when the step has no
+    backward pass), and the gradients of the vector field's parameters.  Returns (per-series arrays, the others)."""
+    batched = {"solution": out}
+    if z is not None and z.grad is not None:
+        batched["grad_z0"] = z.grad
+    shared = {"grad_" + name.replace(".", "_"): p.grad for name, p in module.named_parameters() if p.grad is not None}
+    return batched, shared
+
+
+def dump_outputs(directory, batched, shared, distributed, world, rank):
+    """--dump-outputs: write what the last timed step computed to DIR/<name>.npy (float32 / float64) from rank 0.
+    `batched`: arrays with the series along dim 0, this rank's shard; gathered over the ranks in rank order.  An array whose
+    gathered size exceeds DUMP_BATCHED_MAX_BYTES keeps a fixed sample of its series instead: the same rows of every rank's
+    shard, drawn by a generator seeded with 0, sorted.  `shared`: arrays that are the same on every rank (the all-reduced
+    parameter gradients), written whole.  Returns {name: shape} on rank 0, None elsewhere."""
+    import numpy as np
+    arrays = {}
+    for name, t in batched.items():
+        t = t.detach()
+        row_bytes = t[0].numel() * t.element_size()
+        if t.size(0) * world * row_bytes > DUMP_BATCHED_MAX_BYTES:
+            keep = max(1, DUMP_BATCHED_MAX_BYTES // (world * row_bytes))
+            rows = torch.randperm(t.size(0), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[rows.to(t.device)]
+        t = t.contiguous()
+        if distributed:
+            import torch.distributed as dist
+            if dist.get_backend() == "gloo":
+                t = t.cpu()
+            parts = [torch.empty_like(t) for _ in range(world)]
+            dist.all_gather(parts, t)
+            t = torch.cat(parts)
+        arrays[name] = t
+    arrays.update((name, t.detach()) for name, t in shared.items())
+    if rank != 0:
+        return None
+    arrays = {name: t.cpu().numpy() for name, t in arrays.items()}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise SystemExit("--dump-outputs: %s is %s, not float32 / float64" % (name, a.dtype))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    _log("dumped %d arrays (%.1f MB) to %s" % (len(arrays), total / 2**20, directory))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def cpu_baseline(max_sample, budget_s=20.0):
@@ -557,19 +616,25 @@ def run_adaptive_config(args, cde, device, rank, world, distributed, share_gpu):
     if shared and not distributed:
         raise SystemExit("--controller shared needs a process group (N > 1, or CDE_BENCH_FORCE_DIST=1 on one GPU)")
 
-    def step():
+    last = {}
+
+    def step(keep=False):
         scope = shared_step_control(n * world) if shared else contextlib.nullcontext()
         with scope:
             if args.adjoint:
                 z = z0.detach().requires_grad_(True)
                 for p in params:
                     p.grad = None
-                cde.cdeint(X, func, z, X.interval, **kw)[:, -1].sum().backward()
+                out = cde.cdeint(X, func, z, X.interval, **kw)
+                out[:, -1].sum().backward()
                 if distributed:
                     allreduce_gradients(params)
             else:
+                z = None
                 with torch.no_grad():
-                    cde.cdeint(X, func, z0, X.interval, **kw)
+                    out = cde.cdeint(X, func, z0, X.interval, **kw)
+        if keep:                                  # the last timed step: what it computed, for --dump-outputs
+            last["out"], last["z"] = out, z
 
     for _ in range(args.warmup):
         step()
@@ -578,8 +643,8 @@ def run_adaptive_config(args, cde, device, rank, world, distributed, share_gpu):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(keep=i == args.steps - 1)
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -589,6 +654,9 @@ def run_adaptive_config(args, cde, device, rank, world, distributed, share_gpu):
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, *step_outputs(last["out"], last["z"], func), distributed, world, rank)
     if rank == 0:
         fwd, bwd = dict(front.last_dopri5_stats), dict(front.last_dopri5_adjoint_stats) if args.adjoint else {}
         attempts = fwd.get("launches", 0) + bwd.get("launches", 0)
@@ -607,7 +675,8 @@ def run_adaptive_config(args, cde, device, rank, world, distributed, share_gpu):
                                                                  if shared else "no collective in the solve")},
             "extra": {"forward_steps": fwd, "backward_steps": {k: v for k, v in bwd.items() if k in ("n_accept", "n_reject", "launches")},
                       "kernel_launches_per_step": attempts,
-                      "us_per_attempted_step": elapsed / args.steps * 1e6 / max(attempts, 1)}}))
+                      "us_per_attempted_step": elapsed / args.steps * 1e6 / max(attempts, 1)},
+            "dumped_outputs": dumped}))
 
 
 def run_logode_config(args, cde, device, rank, world, distributed, share_gpu):
@@ -640,7 +709,9 @@ def run_logode_config(args, cde, device, rank, world, distributed, share_gpu):
     if shared and not distributed:
         raise SystemExit("--controller shared needs a process group (N > 1, or CDE_BENCH_FORCE_DIST=1 on one GPU)")
 
-    def step():
+    last = {}
+
+    def step(keep=False):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         ev[0].record()
         Xl = cde.LinearInterpolation(cde.linear_interpolation_coeffs(cde.logsig_windows(raw, 3, 8.0)))
@@ -650,9 +721,12 @@ def run_logode_config(args, cde, device, rank, world, distributed, share_gpu):
             p.grad = None
         # --controller shared: ONE step controller for the whole sharded batch (K4 / K4am with the two-layer field, round 4)
         with (shared_step_control(n * world) if shared else contextlib.nullcontext()):
-            cde.cdeint(Xl, field, z, Xl.interval, **solver)[:, -1].sum().backward()
+            out = cde.cdeint(Xl, field, z, Xl.interval, **solver)
+            out[:, -1].sum().backward()
         if distributed:
             allreduce_gradients(params)
+        if keep:                                  # the last timed step: what it computed, for --dump-outputs
+            last["out"], last["z"] = out, z
         return ev
 
     for _ in range(args.warmup):
@@ -662,7 +736,7 @@ def run_logode_config(args, cde, device, rank, world, distributed, share_gpu):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    events = [step() for _ in range(args.steps)]
+    events = [step(keep=i == args.steps - 1) for i in range(args.steps)]
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -673,6 +747,9 @@ def run_logode_config(args, cde, device, rank, world, distributed, share_gpu):
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, *step_outputs(last["out"], last["z"], field), distributed, world, rank)
     if rank == 0:
         extra = {"logsig_transform_ms": times["transform"]}
         if args.method != "rk4":
@@ -695,7 +772,7 @@ def run_logode_config(args, cde, device, rank, world, distributed, share_gpu):
                        "method": args.method, "adjoint_norm": args.norm, "controller": "shared" if shared else "local",
                        "batch_per_gpu": n, "global_batch": n * world,
                        "parallelism": "batch-sharded x%d, one gradient all-reduce per step" % world},
-            "extra": extra}))
+            "extra": extra, "dumped_outputs": dumped}))
 
 
 def main():
@@ -717,7 +794,11 @@ def main():
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong: 32768 series in total (32768/N per GPU); weak: 32768 series per GPU")
     ap.add_argument("--cpu-sample", type=int, default=8192, help="series in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (solution, gradients) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # not under torchrun: launch the N ranks ourselves (one process per GPU, RCCL over xGMI, rendezvous on 127.0.0.1)
@@ -725,9 +806,10 @@ def main():
         with socket.socket() as sock:
             sock.bind(("127.0.0.1", 0))
             port = sock.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
+        import subprocess
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                                   "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
-                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
 
     capture_stdout()
     rank = int(os.environ.get("RANK", "0"))
@@ -810,7 +892,9 @@ def main():
     t = X.interval
     params = list(func.parameters())
 
-    def step():
+    last = {}
+
+    def step(keep=False):
         z = z0.detach().requires_grad_(True)
         for p in params:
             p.grad = None
@@ -818,6 +902,8 @@ def main():
         out[:, -1].sum().backward()
         if distributed:
             allreduce_gradients(params)
+        if keep:                                  # the last timed step: what it computed, for --dump-outputs
+            last["out"], last["z"] = out, z
         return out
 
     _log("hermite fit %.3f ms; warm-up" % fit_ms)
@@ -839,8 +925,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(keep=i == args.steps - 1)
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -852,6 +938,11 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
+    # written now: the measurements below reuse the field and overwrite its gradients
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, *step_outputs(last["out"], last["z"], func), distributed, world, rank)
+    last.clear()
 
     fwd_ms = [a.elapsed_time(b) for kind, a, b in log if kind == "forward"]
     adj_ms = [a.elapsed_time(b) for kind, a, b in log if kind == "adjoint"]
@@ -928,6 +1019,7 @@ def main():
                 "missing_value_fill_ms_10pct_nan": fill_ms,
                 "missing_value_fill_series_per_s": B / (fill_ms * 1e-3),
             },
+            "dumped_outputs": dumped,
         }
         if world == 1:
             result["extra"]["strong_scaling_proxy_1gpu"] = strong_scaling_proxy(cde, x, func, z0, elapsed / args.steps * 1e3)

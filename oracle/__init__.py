@@ -19,8 +19,8 @@ What is restated, and what pins it
   standing in for the missing ``torchdiffeq`` module.
 * ``oracle.odeint``  -- the third-party solver ``torchdiffeq`` (requirement
   ``torchdiffeq>=0.2.0``, unpinned, reference ``setup.py:51``; call sites
-  ``torchcde/solver.py:226-227``).  That package is neither vendored under
-  ``/root/reference`` nor installed here, and the reference's tests hold no
+  ``torchcde/solver.py:226-227``).  That package is neither vendored with
+  the reference nor installed here, and the reference's tests hold no
   value-level vector for its output.  **PARITY UNPINNED** for this half: the
   file restates the published algorithm (fixed-grid RK4 3/8-rule, dopri5,
   continuous adjoint) and is validated by mathematics instead -- order-4

@@ -3,7 +3,7 @@
     python oracle/make_golden.py                        # (re)write the fixtures + bitwise self-check
     python oracle/make_golden.py --run-reference-tests  # additionally run the reference's own pytest files
 
-/root/reference is imported read-only.  Its ``torchcde/__init__.py:7`` imports
+``TORCHCDE_REFERENCE`` names a source checkout of the reference, imported read-only.  Its ``torchcde/__init__.py:7`` imports
 ``solver.py``, which imports ``torchdiffeq`` and ``torchsde`` (solver.py:2-3); neither is
 installed, so before importing we register ``oracle.odeint`` as ``torchdiffeq`` and an
 empty module as ``torchsde``.  Consequences, stated once:
@@ -14,7 +14,7 @@ empty module as ``torchsde``.  Consequences, stated once:
     defaults, permute) driving ``oracle.odeint`` -> they pin ``oracle.cde`` and the plumbing, but
     the integrator arithmetic itself stays PARITY UNPINNED (see oracle/odeint.py).
 
-Nothing here runs on the GPU box (no /root/reference there); tests read only the .pt files.
+Nothing here runs on the GPU box (no reference checkout there); tests read only the .pt files.
 """
 import argparse
 import os
@@ -25,7 +25,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-REFERENCE = "/root/reference"
+# a source checkout of the reference torchcde (its torchcde/ package and test/ directory); only this tool and
+# tests/tools/cpu_reference_baseline.py read it
+REFERENCE = os.environ.get("TORCHCDE_REFERENCE", "")
 OUT = os.path.join(ROOT, "tests", "golden")
 
 
@@ -38,9 +40,12 @@ def import_reference():
     sys.modules["torchsde"] = types.ModuleType("torchsde")
     from oracle import logsig as oracle_logsig
     sys.modules["signatory"] = oracle_logsig.as_signatory_module()      # log_ode.py:1-8 imports it at module load
-    sys.path.insert(0, REFERENCE)
+    if not os.path.isdir(os.path.join(REFERENCE, "torchcde")):
+        raise SystemExit("set TORCHCDE_REFERENCE to a source checkout of the reference torchcde (got %r)" % REFERENCE)
+    reference = os.path.realpath(REFERENCE)
+    sys.path.insert(0, reference)
     import torchcde
-    assert os.path.realpath(torchcde.__file__).startswith(REFERENCE)
+    assert os.path.realpath(torchcde.__file__).startswith(reference)
     return torchcde
 
 

@@ -2,8 +2,8 @@
 
 The reference never integrates anything itself: ``torchcde/solver.py:226-227`` hands a
 ``_VectorField`` to ``torchdiffeq.odeint`` / ``odeint_adjoint``.  ``torchdiffeq``
-(requirement ``>=0.2.0``, unpinned -- reference ``setup.py:51``) is NOT vendored under
-/root/reference and NOT installed here, so this file restates its published algorithm
+(requirement ``>=0.2.0``, unpinned -- reference ``setup.py:51``) is NOT vendored with
+the reference and NOT installed here, so this file restates its published algorithm
 (torchdiffeq 0.2.x ``_impl/{odeint,misc,solvers,fixed_grid,rk_common,dopri5,interp,adjoint}.py``)
 from the description in SURVEY.md Appendix A.
 

@@ -5,10 +5,11 @@
 
 TEST INFRASTRUCTURE.  The reference delegates all time stepping to the third-party ``torchdiffeq`` (reference
 ``setup.py:51``: ``torchdiffeq>=0.2.0``, unpinned; call sites ``torchcde/solver.py:226-227``).  The package is neither
-vendored under /root/reference nor installed in the build container (no network), so ``oracle/odeint.py`` restates it
+vendored with the reference nor installed in the build container (no network), so ``oracle/odeint.py`` restates it
 from its published algorithm and is anchored by mathematics + scipy's independent Dormand-Prince implementation
 (tests/test_oracle.py).  This script is the missing pin: it needs ``import torchdiffeq`` to succeed (``pip install
-torchdiffeq`` on any machine with network), and torchcde itself either from /root/reference or pip.
+torchdiffeq`` on any machine with network), and torchcde itself either from a source checkout named by
+``TORCHCDE_REFERENCE`` or from pip.
 
 What it compares, problem by problem (the seeded problems of tests/golden/cdeint.pt -- README toy, mid-size rk4 in
 float32/float64, half steps with outputs off the grid, irregular knots, dopri5 -- plus adaptive problems with
@@ -99,25 +100,29 @@ def main():
     from oracle import cde as oracle_cde, interp as oracle_interp, odeint as oracle_ode
     real = {"odeint": torchdiffeq.odeint, "odeint_adjoint": torchdiffeq.odeint_adjoint}
 
-    # the reference's own front end (solver.py:144-245) when torchcde is importable (from /root/reference or pip; its
+    # the reference's own front end (solver.py:144-245) when torchcde is importable (from TORCHCDE_REFERENCE or pip; its
     # other dependency torchsde is stubbed if absent -- the torchdiffeq backend never touches it), else the oracle's
     # restatement of that front end (bit-pinned to the reference by oracle/make_golden.py); the REAL integrators behind
-    # it either way
+    # it either way.  --self-test always takes the oracle's front end: it checks the script's plumbing, the same on
+    # every machine.
     reference_front_end = None
-    try:
-        import types
-        if "torchsde" not in sys.modules:
-            try:
-                import torchsde  # noqa: F401
-            except ImportError:
-                sys.modules["torchsde"] = types.ModuleType("torchsde")
-        if os.path.isdir("/root/reference"):
-            sys.path.insert(0, "/root/reference")
-        import torchcde
-        reference_front_end = torchcde.cdeint
-        print("front end: torchcde.cdeint from", os.path.dirname(torchcde.__file__))
-    except Exception as exc:                                            # noqa: BLE001
-        print("front end: oracle.cde.cdeint (torchcde not importable: %s)" % exc)
+    if opts.self_test:
+        print("front end: oracle.cde.cdeint (--self-test)")
+    else:
+        try:
+            import types
+            if "torchsde" not in sys.modules:
+                try:
+                    import torchsde  # noqa: F401
+                except ImportError:
+                    sys.modules["torchsde"] = types.ModuleType("torchsde")
+            if os.environ.get("TORCHCDE_REFERENCE"):
+                sys.path.insert(0, os.environ["TORCHCDE_REFERENCE"])
+            import torchcde
+            reference_front_end = torchcde.cdeint
+            print("front end: torchcde.cdeint from", os.path.dirname(torchcde.__file__))
+        except Exception as exc:                                        # noqa: BLE001
+            print("front end: oracle.cde.cdeint (torchcde not importable: %s)" % exc)
 
     def reference_cdeint(**kw):
         if reference_front_end is not None:

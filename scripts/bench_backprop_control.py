@@ -1,7 +1,8 @@
 """adjoint=False on the headline workload with a coefficient tensor that requires a gradient (cde_rk4_backprop_linear_dcontrol):
 ms per forward + backward step and the two kernels' own durations (HIP events on the launching stream)."""
-import sys, time, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys, time, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torchcde_amd as cde
 from helpers import LinearField, make_series
 front = sys.modules["torchcde_amd.cdeint"]

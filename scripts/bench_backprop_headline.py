@@ -1,5 +1,6 @@
 import os, sys, time, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torchcde_amd as cde
 from helpers import LinearField, make_series
 front = sys.modules["torchcde_amd.cdeint"]

@@ -2,8 +2,9 @@
 cdeint without `method`: dopri5 forward + adjoint).  Fused since round 3 (K4 forward, K4am backward); `stepwise` as a
 third argument forces the host-driven path of round 2.
     python scripts/bench_default_call.py [B] [seminorm|mixed] [stepwise|fused] [C] [H]     (C, H: e.g. 14 8 = config 5's shape)"""
-import sys, time, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys, time, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torchcde_amd as cde
 from helpers import make_series
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096

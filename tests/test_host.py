@@ -1097,3 +1097,29 @@ def test_fit_chain_detection_walks_the_autograd_graph():
     (want,) = torch.autograd.grad(fitted, t, gz, retain_graph=True)
     assert torch.allclose(got, direct + want, rtol=1e-12, atol=1e-14)
     assert front._with_fit_chain(types.SimpleNamespace(fit_chain=None), direct, g) is direct
+
+
+# ------------------------------------------------------------------ bench.py --dump-outputs
+def test_bench_dump_outputs_writes_what_the_step_returns(tmp_path):
+    """The arrays a caller of the timed step receives, as float32 .npy files named after them; a per-series array above
+    the per-array cap keeps a seeded, sorted sample of its rows, the same from call to call."""
+    import bench
+    field = LinearField(32, 8, seed=0)
+    out = torch.randn(4096, 2, 32)
+    z = torch.randn(4096, 32, requires_grad=True)
+    (field(None, z).sum() + (2 * z).sum()).backward()
+    shapes = bench.dump_outputs(str(tmp_path / "a"), *bench.step_outputs(out, z, field), False, 1, 0)
+    assert shapes == {"solution": [4096, 2, 32], "grad_z0": [4096, 32], "grad_linear_weight": [256, 32],
+                      "grad_linear_bias": [256]}
+    for name, want in (("solution", out), ("grad_z0", z.grad), ("grad_linear_weight", field.linear.weight.grad)):
+        got = np.load(str(tmp_path / "a" / (name + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, want.numpy()), name
+    big = torch.randn(8192, 128, 32)                                 # 128 MB: over the cap
+    for run in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / run), {"solution": big}, {}, False, 1, 0) == {"solution": [1024, 128, 32]}
+    sample = np.load(str(tmp_path / "b" / "solution.npy"))
+    assert sample.nbytes == bench.DUMP_BATCHED_MAX_BYTES and np.array_equal(sample, np.load(str(tmp_path / "c" / "solution.npy")))
+    rows = torch.randperm(8192, generator=torch.Generator().manual_seed(0))[:1024].sort().values
+    assert np.array_equal(sample, big[rows].numpy())
+    with pytest.raises(SystemExit):                                   # integer outputs are not part of the format
+        bench.dump_outputs(str(tmp_path / "d"), {"solution": torch.zeros(4, 2, dtype=torch.int64)}, {}, False, 1, 0)

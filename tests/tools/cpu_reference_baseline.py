@@ -1,11 +1,11 @@
 #!/usr/bin/env python
 """Container-side CPU baseline with the REFERENCE's own classes: torchcde.CubicSpline and
-torchcde.solver._VectorField imported unmodified from /root/reference, the reference's own
+torchcde.solver._VectorField imported unmodified from the reference checkout named by TORCHCDE_REFERENCE, the reference's own
 hermite_cubic_coefficients_with_backward_differences, driven by the oracle's restatement of torchdiffeq (registered as
-the `torchdiffeq` module: the real package is not installable here).  Runs only where /root/reference exists (the
+the `torchdiffeq` module: the real package is not installable here).  Runs only where a reference checkout exists (the
 build container, not the GPU box); writes profiles/r05_cpu_reference_container.json.
 
-    python tests/tools/cpu_reference_baseline.py [series=4096] [threads=all]
+    TORCHCDE_REFERENCE=<torchcde checkout> python tests/tools/cpu_reference_baseline.py [series=4096] [threads=all]
 """
 import json
 import os
@@ -55,7 +55,7 @@ def solve(coeffs, adjoint):
 _, coeffs = fit()
 solve(coeffs, True)                                   # warm-up
 res = {"series": n, "threads": threads, "cores_available": os.cpu_count(), "length": L, "channels": C, "hidden": H,
-       "classes": "reference torchcde.CubicSpline / _VectorField / cdeint (imported from /root/reference) over the "
+       "classes": "reference torchcde.CubicSpline / _VectorField / cdeint (imported from the reference checkout) over the "
                   "oracle's torchdiffeq restatement (oracle/odeint.py)"}
 for name, fn in (("fit", lambda: fit()[0]), ("forward", lambda: solve(coeffs, False)), ("forward_adjoint", lambda: solve(coeffs, True))):
     times = sorted(fn() for _ in range(3))
