@@ -62,10 +62,12 @@ enum {
   CDE_VARIANT_MFMA = 2,    /* fail with CDE_ERR_UNSUPPORTED unless the MFMA kernel applies   */
   CDE_VARIANT_SPLIT = 3,   /* MFMA, one workgroup (4 waves) per 16 series: the latency-oriented kernels for small
                               per-GPU batches (strong scaling); AUTO picks them when B <= CDE_SPLIT_MAX_BATCH */
-  CDE_VARIANT_BF16X3 = 4   /* opt-in: the weight GEMMs on the bf16 matrix pipe at float32 accuracy (every operand split
-                              into three bf16 pieces, six piece products per block, f32 accumulate; csrc/rk4_bf16x3.hip).
+  CDE_VARIANT_BF16X3 = 4   /* the weight GEMMs on the bf16 matrix pipe at float32 accuracy (every operand split
+                              into three bf16 pieces, six piece products per block, f32 accumulate; csrc/rk4_bf16x3.hip,
+                              the adjoint as K3p's bf16 form in csrc/rk4_adjoint_pair.hip).
                               f32, H <= 32, C <= 8, identity activation, rk4 forward and adjoint (no control gradients);
-                              CDE_ERR_UNSUPPORTED otherwise.  Never chosen by AUTO. */
+                              CDE_ERR_UNSUPPORTED otherwise.  AUTO takes it for such fields above CDE_SPLIT_MAX_BATCH
+                              series (rk4 forward / adjoint=True); CDE_VARIANT_MFMA keeps the exact-f32 kernels. */
 };
 #define CDE_SPLIT_MAX_BATCH 16384
 
@@ -264,6 +266,10 @@ int cde_contract(const void* F, const void* dX, void* out, int64_t B, int64_t H,
  * H <= 32, C <= 8, the wide tile kernels f32 and H <= 64, C <= 8 or H <= 32, C <= 16 (variant AUTO only); the
  * generic kernels H <= 256 and one series' stage data (adjoint: H + C + H*C values) within 64 KB of LDS.  The Python host solves anything else step by step (torchcde_amd/stepwise.py) instead of failing in
  * the backward pass. */
+/* 1 when an rk4 solve of the affine field with these dimensions takes the bf16x3 kernels (variant = CDE_VARIANT_BF16X3,
+ * or CDE_VARIANT_AUTO on the headline field above CDE_SPLIT_MAX_BATCH series; under AUTO a request with control gradients
+ * runs the bf16x3 forward and the exact-f32 adjoint), 0 otherwise. */
+int cde_rk4_bf16x3_form(int64_t B, int64_t C, int64_t H, int dtype, int act, int variant);
 int cde_rk4_supported(int64_t C, int64_t H, int dtype, int act, int adjoint, int variant);
 
 /* ---------------------------------------------------------------------------------------------

@@ -1748,6 +1748,13 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
         # 32 units x 16 channels: fused where the kernels read the upper half (see _UPPER_HALF_PATHS)
         request = request._replace(tiles_ok=False)
         choice = dispatch.select_path(request)
+    if choice.path == "rk4" and field is not None and field.kind == "affine":
+        B_total = z0.numel() // H
+        if _lib.load().cde_rk4_bf16x3_form(B_total, C, H, _lib.dtype_enum(z0.dtype), field.act, variant):
+            form = "bf16x3_forward" if (control_wants and variant == _lib.VARIANT_AUTO) else "bf16x3"
+        else:
+            form = "exact"
+        choice = choice.with_form(form)
     dispatch.record(choice, request)
 
     if choice.path == dispatch.STEPWISE:

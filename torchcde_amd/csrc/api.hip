@@ -69,7 +69,7 @@ int launch_forward_mfma_method(int, const void*, const void*, int64_t, int, cons
 template <typename TT>
 int launch_adjoint_jacobian_pair(const void*, const void*, int64_t, int, const void*, const void*, const void*, const void*,
                                  const void*, const int64_t*, int64_t, void*, void*, void*, int64_t, int64_t, int64_t,
-                                 const int64_t*, const void*, float*, hipStream_t, int method);
+                                 const int64_t*, const void*, float*, hipStream_t, int method, bool bx = false);
 // K2 with the stage states stored (rk4_mfma.hip) and the reverse-mode sweep over them (rk4_backprop.hip): adjoint=False
 template <typename TT>
 int launch_forward_mfma_stages(const void*, const void*, int64_t, int, const void*, const void*, int, const void*, const void*,
@@ -89,6 +89,12 @@ int launch_adjoint_bf16x3(const void*, const void*, int64_t, int, const void*, c
                           const int64_t*, const void*, float*, hipStream_t);
 static bool bf16x3_applicable(int64_t C, int64_t H, int dtype, int act) {
   return dtype == CDE_F32 && act == CDE_ACT_NONE && H >= 1 && H <= 32 && C >= 1 && C <= 8;
+}
+// AUTO takes the bf16x3 kernels (K2b forward, K3p's bf16 form backward) for the headline field on the wave-per-tile
+// batches: float32, identity activation, H <= 32, C <= 8, more than CDE_SPLIT_MAX_BATCH series, no control gradients.
+// variant = "mfma" keeps the exact-f32 kernels.
+static bool auto_bf16x3(int variant, int64_t B, int64_t C, int64_t H, int dtype, int act) {
+  return variant == CDE_VARIANT_AUTO && B > CDE_SPLIT_MAX_BATCH && bf16x3_applicable(C, H, dtype, act);
 }
 
 // from rk4_mlp_adjoint.hip
@@ -178,7 +184,7 @@ static int forward_typed(const void* coeffs, const void* knots, int64_t n_interv
                          int variant, int64_t* stage_index, void* stage_frac, hipStream_t s) {
   int rc = fill_stage_table<T, TT>(knots, n_intervals, grid, n_grid - 1, 0, stage_index, stage_frac, s);
   if (rc != CDE_OK) return rc;
-  if (variant == CDE_VARIANT_BF16X3) {
+  if (variant == CDE_VARIANT_BF16X3 || auto_bf16x3(variant, B, C, H, dtype, act)) {
     if (!bf16x3_applicable(C, H, dtype, act)) return CDE_ERR_UNSUPPORTED;
     return launch_forward_bf16x3<TT>(coeffs, knots, n_intervals, degree, W, bias, z0, grid, n_grid, t_out, n_out, z_out, B, C,
                                      H, stage_index, stage_frac, s);
@@ -205,7 +211,7 @@ static int adjoint_typed(const void* coeffs, const void* knots, int64_t n_interv
                          void* grad_z0, void* grad_W, void* grad_b, int64_t B, int64_t C, int64_t H, int dtype,
                          int variant, void* workspace, size_t workspace_bytes, void* grad_coeffs, hipStream_t s) {
   int rc;
-  if (variant == CDE_VARIANT_BF16X3) {
+  if (variant == CDE_VARIANT_BF16X3 || (auto_bf16x3(variant, B, C, H, dtype, act) && !grad_coeffs)) {
     if (!bf16x3_applicable(C, H, dtype, act) || grad_coeffs) return CDE_ERR_UNSUPPORTED;
     const int64_t n_steps_b = n_sgrid - 1;
     const size_t off_frac_b = align256((size_t)(4 * n_steps_b) * sizeof(int64_t));
@@ -215,8 +221,13 @@ static int adjoint_typed(const void* coeffs, const void* knots, int64_t n_interv
     void* sfrac = (unsigned char*)workspace + off_frac_b;
     rc = fill_stage_table<T, TT>(knots, n_intervals, sgrid, n_steps_b, 1, sidx, sfrac, s);
     if (rc != CDE_OK) return rc;
-    // the reverse sweep: K3j with its J rows on the bf16 pipe (rk4_mfma.hip); CDE_OPT_K3_FORM = 1 keeps K3b (three GEMMs,
-    // two of them on the bf16 pipe)
+    // the reverse sweep: K3p with its J rows on the bf16 pipe (rk4_adjoint_pair.hip); CDE_OPT_K3_WAVES = 1 keeps the
+    // one-wave form K3bj (rk4_mfma.hip, bitwise the same results), CDE_OPT_K3_FORM = 1 K3b (three GEMMs, two of them on the
+    // bf16 pipe)
+    if (cde::option(CDE_OPT_K3_FORM) != 1 && cde::option(CDE_OPT_K3_WAVES) != 1)
+      return launch_adjoint_jacobian_pair<TT>(coeffs, knots, n_intervals, degree, W, bias, z_saved, grad_out, sgrid, seg_off,
+                                              n_out, grad_z0, grad_W, grad_b, B, C, H, sidx, sfrac,
+                                              (float*)((unsigned char*)workspace + off_part_b), s, CDE_METHOD_RK4, true);
     if (cde::option(CDE_OPT_K3_FORM) != 1)
       return launch_adjoint_jacobian_bx<TT>(coeffs, knots, n_intervals, degree, W, bias, z_saved, grad_out, sgrid, seg_off,
                                             n_out, grad_z0, grad_W, grad_b, B, C, H, sidx, sfrac,
@@ -261,6 +272,13 @@ static int adjoint_typed(const void* coeffs, const void* knots, int64_t n_interv
 }
 
 }  // namespace cde
+
+// which arithmetic an rk4 solve of the affine field takes (1: the bf16x3 kernels, 0: the exact-f32 / other kernels) --
+// the rule of forward_typed / adjoint_typed, for the host's dispatch record
+extern "C" int cde_rk4_bf16x3_form(int64_t B, int64_t C, int64_t H, int dtype, int act, int variant) {
+  if (variant == CDE_VARIANT_BF16X3) return cde::bf16x3_applicable(C, H, dtype, act) ? 1 : 0;
+  return cde::auto_bf16x3(variant, B, C, H, dtype, act) ? 1 : 0;
+}
 
 extern "C" int cde_rk4_supported(int64_t C, int64_t H, int dtype, int act, int adjoint, int variant) {
   if (C < 1 || H < 1 || (dtype != CDE_F32 && dtype != CDE_F64)) return 0;

@@ -43,6 +43,15 @@ constexpr int KP_WJ_FLOATS = KP_WJ_ROWS * 64 * 4;
 constexpr int KP_ZA_FLOATS = 2 * 64 * 20;                          // one stage's transposed (z, a): 64 rows x 20 each
 constexpr int KP_TILE_FLOATS = 2 * KP_ZA_FLOATS + 3 * 256 + 3 * 256;   // per tile: 2 x (z^T | a^T), 3 x dX, 3 x weighted dX
 constexpr int KP_LDS_FLOATS = KP_WJ_FLOATS + 4 * KP_TILE_FLOATS;
+// BX: the weight image as bf16 pieces, [row][piece][k slot] of 8 channels (16 B), stored once per k slot (the two half-lanes
+// that read one slot take the same entry; the third MFMA's lower half-lanes read piece 1 again): 50.7 KB, so that with the
+// four tiles' buffers the workgroup fits the 160 KB of LDS.
+constexpr int KP_WJB_U4 = KP_WJ_ROWS * 3 * 32;
+constexpr int KP_WJB_FLOATS = KP_WJB_U4 * 4;
+constexpr int KP_LDS_FLOATS_BX = KP_WJB_FLOATS + 4 * KP_TILE_FLOATS;
+static_assert(KP_LDS_FLOATS_BX * 4 <= 160 * 1024, "BX workgroup exceeds the LDS of a CU");
+using kp_bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using kp_u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 __device__ __forceinline__ void kp_swap32(float& x, float& y) {    // x[lanes 32..63] <-> y[lanes 0..31]
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
@@ -56,12 +65,39 @@ __device__ __forceinline__ float kp_wj_image(const float* __restrict__ W, const 
   if (h < MH) return h < d.H ? W[(h * d.C + c) * d.H + k] : 0.f;
   return bias[k * d.C + c];
 }
+// x = a + b + c in bf16 pieces (each the round-to-nearest bf16 of what the larger ones leave)
+__device__ __forceinline__ void kp_split3(float x, __bf16& a, __bf16& b, __bf16& c) {
+  a = (__bf16)x;
+  const float r1 = x - (float)a;
+  b = (__bf16)r1;
+  c = (__bf16)(r1 - (float)b);
+}
+// piece m of the 8 channel weights of row h at k slot j (hidden unit k = rho(j)); row MH: the bias rows
+__device__ __forceinline__ kp_u32x4 kp_wjb_image(const float* __restrict__ W, const float* __restrict__ bias, int h, int m, int j,
+                                                 Dims d) {
+  const int k = rho(j);
+  kp_bf16x8 out;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    float w = 0.f;
+    if (c < d.C && k < d.H) w = h < MH ? (h < d.H ? W[(h * d.C + c) * d.H + k] : 0.f) : bias[k * d.C + c];
+    __bf16 p1, p2, p3;
+    kp_split3(w, p1, p2, p3);
+    out[c] = m == 0 ? p1 : m == 1 ? p2 : p3;
+  }
+  return __builtin_bit_cast(kp_u32x4, out);
+}
 // the stage barrier: this wave's LDS traffic done, then all eight waves meet
 __device__ __forceinline__ void kp_stage_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // METHOD (CDE_METHOD_*): the 3/8 rule, or torchdiffeq's midpoint / euler on the same augmented system -- two stages / one
 // stage per step, quadrature weights (0, ds) / (ds) for the parameter gradients (a zero-weight stage costs the helper nothing).
-template <typename TT, int DEGREE, int METHOD = CDE_METHOD_RK4>
+// BX: both GEMMs on the bf16 matrix pipe.  The J rows as K3bj forms them (rk4_mfma.hip): three v_mfma_f32_32x32x16_bf16
+// per row take the six piece products W_i dX_j with i + j <= 4, float32 accumulation, in K3bj's order -- so dL/dz0 and the
+// trajectories are bitwise K3bj's.  The helper's dL/dW: 12 bf16 MFMAs per channel tile (six piece products x two K blocks
+// of 16 series) instead of 16 f32 ones, its operands split on the helper itself with non-packed vector instructions, which
+// hide in the chain wave's MFMA gaps (scripts/ubench/mfma_bf16_fill.hip).  dL/db keeps the f32 form's fma order.
+template <typename TT, int DEGREE, int METHOD = CDE_METHOD_RK4, bool BX = false>
 __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
     const float* __restrict__ coeffs, const float* __restrict__ knots, int64_t n_intervals,
     const float* __restrict__ W, const float* __restrict__ bias, const float* __restrict__ z_saved,
@@ -71,7 +107,13 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
   const int Hr = dims.H, Cr = dims.C;
   constexpr int NS = METHOD == CDE_METHOD_RK4 ? 4 : METHOD == CDE_METHOD_MIDPOINT ? 2 : 1;     // stages per step
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  for (int e = threadIdx.x; e < KP_WJ_FLOATS; e += 512) lds[e] = kp_wj_image(W, bias, e >> 8, e & 3, (e >> 2) & 63, dims);
+  static_assert(!BX || METHOD == CDE_METHOD_RK4, "BX: rk4 only");
+  if constexpr (BX) {
+    kp_u32x4* img = reinterpret_cast<kp_u32x4*>(lds);
+    for (int e = threadIdx.x; e < KP_WJB_U4; e += 512) img[e] = kp_wjb_image(W, bias, e / 96, (e >> 5) % 3, e & 31, dims);
+  } else {
+    for (int e = threadIdx.x; e < KP_WJ_FLOATS; e += 512) lds[e] = kp_wj_image(W, bias, e >> 8, e & 3, (e >> 2) & 63, dims);
+  }
   const float4* wj = reinterpret_cast<const float4*>(lds);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -79,7 +121,7 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
   const bool helper = wave >= 4;
   const int n = lane & 31, half = lane >> 5;
   // per tile: [2 x (z^T | a^T)] [3 x dX] [3 x weighted dX]          (KP_TILE_FLOATS)
-  float* tile_lds = lds + KP_WJ_FLOATS + slot * KP_TILE_FLOATS;
+  float* tile_lds = lds + (BX ? KP_WJB_FLOATS : KP_WJ_FLOATS) + slot * KP_TILE_FLOATS;
   float* ring_dx = tile_lds + 2 * KP_ZA_FLOATS;                      // + (stage % 3) * 256: dX_c of series n at [n*8 + c]
   float* ring_dw = ring_dx + 3 * 256;                                // + (stage % 3) * 256: (quadrature weight * ds) * dX_c
 
@@ -148,7 +190,12 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
       const f32x2 d0 = half ? f32x2{dX[4], dX[5]} : f32x2{dX[0], dX[1]}, d1 = half ? f32x2{dX[6], dX[7]} : f32x2{dX[2], dX[3]};
       *reinterpret_cast<float4*>(ring_dx + which * 256 + n * 8 + 4 * half) = make_float4(d0[0], d0[1], d1[0], d1[1]);
       const f32x2 w0 = d0 * p_wq, w1 = d1 * p_wq;
-      *reinterpret_cast<float4*>(ring_dw + which * 256 + n * 8 + 4 * half) = make_float4(w0[0], w0[1], w1[0], w1[1]);
+      if constexpr (BX) {                      // channel-major [c][series parity][series >> 1]: the K order of the bf16 MFMAs
+        float* wr = ring_dw + which * 256 + 4 * half * 32 + (n & 1) * 16 + (n >> 1);
+        wr[0] = w0[0]; wr[32] = w0[1]; wr[64] = w1[0]; wr[96] = w1[1];
+      } else {
+        *reinterpret_cast<float4*>(ring_dw + which * 256 + n * 8 + 4 * half) = make_float4(w0[0], w0[1], w1[0], w1[1]);
+      }
     };
     advance();
     if (cur_ok) idx_ahead = stage_index[cur_e];
@@ -163,7 +210,51 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
       fetch();                                                      // stage st + 3: requested, used next iteration
       const bool weighted = METHOD != CDE_METHOD_MIDPOINT || cs == 1;      // midpoint: the first evaluation carries no weight
       cs = cs + 1 == NS ? 0 : cs + 1;
-      if (weighted) {
+      if (weighted && BX) {
+      // (BX) dL/dW tile c on the bf16 pipe: D[h][k] += sum_series v_c[h] z_k with v_c = (w ds dX_c) a_h, both operands split
+      // into three bf16 pieces and the six piece products with i + j <= 4 taken, smallest first.  MFMA K = 16 series:
+      // this lane supplies K index 8 * half + j = series 2 (8 g + j) + half, row h = n (A: v of a_n), column k = n (B: z_n);
+      // two K blocks g per tile.  dL/db as before: sum_series (w ds dX_c) a_n, the same fma order (bitwise the f32 form's).
+      const float* base = tile_lds + par * KP_ZA_FLOATS;
+      const float4* zt4 = reinterpret_cast<const float4*>(base + (half * 32 + n) * 20);
+      const float4* at4 = reinterpret_cast<const float4*>(base + 64 * 20 + (half * 32 + n) * 20);
+      const float4* dw4 = reinterpret_cast<const float4*>(ring_dw + rs * 256 + half * 16);   // + c * 8 + g * 2: 8 series
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        const float4 z0 = zt4[2 * g], z1 = zt4[2 * g + 1], a0 = at4[2 * g], a1 = at4[2 * g + 1];
+        const float zv[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
+        const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+        kp_bf16x8 zp1, zp2, zp3;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          __bf16 p1, p2, p3;
+          kp_split3(zv[j], p1, p2, p3);
+          zp1[j] = p1; zp2[j] = p2; zp3[j] = p3;
+        }
+#pragma unroll
+        for (int c = 0; c < MC; ++c) {
+          const float4 e0 = dw4[c * 8 + 2 * g], e1 = dw4[c * 8 + 2 * g + 1];
+          const float ev[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+          kp_bf16x8 vp1, vp2, vp3;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            __bf16 p1, p2, p3;
+            kp_split3(ev[j] * av[j], p1, p2, p3);
+            vp1[j] = p1; vp2[j] = p2; vp3[j] = p3;
+            gbp[c >> 1][c & 1] = __builtin_fmaf(ev[j], av[j], gbp[c >> 1][c & 1]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          f32x16 acc = accW[c];
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vp3, zp1, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vp1, zp3, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vp2, zp2, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vp2, zp1, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vp1, zp2, acc, 0, 0, 0);
+          accW[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vp1, zp1, acc, 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      } else if (weighted) {
       // dL/dW tile c: D[h][k] += sum_series (w ds a_h dX_c)[series] * z_k[series]; this lane feeds MFMA K index `half`
       // of K-step s2, i.e. series 2*s2 + half, row h = n, column k = n.  Operands of K-step s2 + 1 are requested from LDS
       // before the MFMAs of K-step s2 are issued (their issue blocks this wave for as long as they take).
@@ -242,10 +333,25 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
         // ---- this stage's control derivative (the helper wave left it two stages ago), the stage state -> this stage's
         // buffer (transposed); then the stage barrier
         float bs0, bs1, bs2, bs3;
+        kp_u32x4 b01, b2;                        // (BX) bf16 pieces of the 8 channel values: lower half-lanes d1 | d3, upper d2 | d1
         {
           const float4 dA = *reinterpret_cast<const float4*>(ring_dx + rs * 256 + n * 8);
           const float4 dB = *reinterpret_cast<const float4*>(ring_dx + rs * 256 + n * 8 + 4);
-          bs0 = half ? dA.y : dA.x; bs1 = half ? dA.w : dA.z; bs2 = half ? dB.y : dB.x; bs3 = half ? dB.w : dB.z;
+          if constexpr (BX) {
+            const float dx[8] = {dA.x, dA.y, dA.z, dA.w, dB.x, dB.y, dB.z, dB.w};
+            kp_bf16x8 q01, q2;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+              __bf16 p1, p2, p3;
+              kp_split3(dx[c], p1, p2, p3);
+              q01[c] = half ? p2 : p1;
+              q2[c] = half ? p1 : p3;
+            }
+            b01 = __builtin_bit_cast(kp_u32x4, q01);
+            b2 = __builtin_bit_cast(kp_u32x4, q2);
+          } else {
+            bs0 = half ? dA.y : dA.x; bs1 = half ? dA.w : dA.z; bs2 = half ? dB.y : dB.x; bs3 = half ? dB.w : dB.z;
+          }
           float* base = tile_lds + par * KP_ZA_FLOATS;
           float* wz = base + ((n & 1) * 32 + half) * 20 + (n >> 1);                // + 2r*20
           float* wa = base + 64 * 20 + ((n & 1) * 32 + half) * 20 + (n >> 1);
@@ -267,14 +373,32 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
           int opaque = 0;                               // the image reads are loop invariant: keep them inside the stage
           asm volatile("" : "+v"(opaque));
           const float4* wp = wj + lane + opaque;
-          auto issue = [&](f32x16& J, const float4& a) {
+          // (BX) row h's pieces: [3h][j], [3h + 1][j] and, for the third MFMA, [3h][j] (lower half-lanes) / [3h + 2][j]
+          const kp_u32x4* wpb = reinterpret_cast<const kp_u32x4*>(lds) + (lane & 31) + opaque;
+          const int third = half ? 64 : 0;
+          struct RowImage { float4 a; kp_u32x4 m0, m1, m2; };
+          auto image = [&](int h) {
+            RowImage r;
+            if constexpr (BX) { r.m0 = wpb[h * 96]; r.m1 = wpb[h * 96 + 32]; r.m2 = wpb[h * 96 + third]; }
+            else r.a = wp[h * 64];
+            return r;
+          };
+          auto issue = [&](f32x16& J, const RowImage& a) {
             __builtin_amdgcn_sched_barrier(0);           // everything that still reads the old J stays above
-            asm volatile("s_nop 1\n\t"                                       // (operands may be fresh VALU results)
-                         "v_mfma_f32_32x32x2_f32 %0, %1, %5, 0\n\t"
-                         "v_mfma_f32_32x32x2_f32 %0, %2, %6, %0\n\t"
-                         "v_mfma_f32_32x32x2_f32 %0, %3, %7, %0\n\t"
-                         "v_mfma_f32_32x32x2_f32 %0, %4, %8, %0"
-                         : "=&v"(J) : "v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "v"(bs0), "v"(bs1), "v"(bs2), "v"(bs3));
+            if constexpr (BX) {
+              asm volatile("s_nop 1\n\t"                                     // (operands may be fresh VALU results)
+                           "v_mfma_f32_32x32x16_bf16 %0, %3, %5, 0\n\t"      // smallest terms first (K3bj's order)
+                           "v_mfma_f32_32x32x16_bf16 %0, %2, %4, %0\n\t"
+                           "v_mfma_f32_32x32x16_bf16 %0, %1, %4, %0"
+                           : "=&v"(J) : "v"(a.m0), "v"(a.m1), "v"(a.m2), "v"(b01), "v"(b2));
+            } else {
+              asm volatile("s_nop 1\n\t"                                     // (operands may be fresh VALU results)
+                           "v_mfma_f32_32x32x2_f32 %0, %1, %5, 0\n\t"
+                           "v_mfma_f32_32x32x2_f32 %0, %2, %6, %0\n\t"
+                           "v_mfma_f32_32x32x2_f32 %0, %3, %7, %0\n\t"
+                           "v_mfma_f32_32x32x2_f32 %0, %4, %8, %0"
+                           : "=&v"(J) : "v"(a.a.x), "v"(a.a.y), "v"(a.a.z), "v"(a.a.w), "v"(bs0), "v"(bs1), "v"(bs2), "v"(bs3));
+            }
             __builtin_amdgcn_sched_barrier(0);
           };
           auto consume = [&](const f32x16& J, float ah) {
@@ -293,22 +417,49 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
             return p2[0] + p2[1];
           };
           f32x16 Je, Jo;                                 // rows 2r / 2r + 1 in flight
-          float4 a_cur = wp[0], a_nxt = wp[64];
+          if constexpr (BX) {
+            // one row image in flight (12 registers): requested right after the previous row's issue, a consume ahead
+            // of its own (the chain wave has no room for two).  Hazards: the ds_read that overwrites the image registers
+            // follows the three MFMAs that read them as SrcA.  gfx950 has a write-after-read hazard only on an MFMA's SrcC
+            // (read over its passes); SrcA / SrcB are read when the MFMA issues, so the overwrite needs no wait states.
+            // SrcC here is J, which nothing else writes until its consume; the consume reads J after the next row's
+            // MFMAs have issued behind it in the in-order pipe, as in the f32 form.
+            RowImage img = image(0);
+            issue(Je, img);
+            img = image(1);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              issue(Jo, img);
+              img = image(2 * r + 2);                    // row 2r + 2 (r = 15: the bias rows)
+              asm volatile("" : "+v"(Je));
+              float ae = ast[r], ao = ast[r];
+              kp_swap32(ae, ao);
+              float X = consume(Je, ae);
+              issue(Je, img);
+              if (r < 15) img = image(2 * r + 3);
+              asm volatile("" : "+v"(Jo));
+              float Y = consume(Jo, ao);
+              kp_swap32(X, Y);
+              f[r] = X + Y;
+            }
+          } else {
+          RowImage a_cur = image(0), a_nxt = image(1);
           issue(Je, a_cur);
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            a_cur = wp[(2 * r + 2) * 64];                // image of row 2r + 2 (r = 15: the bias rows)
+            a_cur = image(2 * r + 2);                    // image of row 2r + 2 (r = 15: the bias rows)
             issue(Jo, a_nxt);
             asm volatile("" : "+v"(Je));
             float ae = ast[r], ao = ast[r];
             kp_swap32(ae, ao);
             float X = consume(Je, ae);
-            if (r < 15) a_nxt = wp[(2 * r + 3) * 64];
+            if (r < 15) a_nxt = image(2 * r + 3);
             issue(Je, a_cur);
             asm volatile("" : "+v"(Jo));
             float Y = consume(Jo, ao);
             kp_swap32(X, Y);                             // ... and each half-lane collects the f of the unit it owns
             f[r] = X + Y;
+          }
           }
           // Je: (b dX)_h for the units this lane owns.  16-pass MFMA result -> VALU read: wait states
           asm volatile("s_nop 15\n\ts_nop 7" : "+v"(Je));
@@ -657,31 +808,35 @@ int launch_adjoint_jacobian_pair(const void* coeffs, const void* knots, int64_t 
                                  const void* bias, const void* z_saved, const void* grad_out, const void* sgrid,
                                  const int64_t* seg_off, int64_t n_out, void* grad_z0, void* grad_W, void* grad_b, int64_t B,
                                  int64_t C, int64_t H, const int64_t* stage_index, const void* stage_frac, float* partial,
-                                 hipStream_t s, int method) {
+                                 hipStream_t s, int method, bool bx) {
   const Dims dims{(int)H, (int)C};
   const unsigned blocks = (unsigned)((B + 127) / 128);
-  const size_t lds = (size_t)KP_LDS_FLOATS * sizeof(float);
+  const size_t lds = (size_t)(bx ? KP_LDS_FLOATS_BX : KP_LDS_FLOATS) * sizeof(float);
   // bit 0: priority 3 for the chain waves, bit 1: for the helper waves (the trace build reads CDE_K3P_FLAGS once: experiments)
 #ifdef CDE_PHASE_TRACE
   static const int flags = [] { const char* e = getenv("CDE_K3P_FLAGS"); return e ? atoi(e) : 1; }();
 #else
   constexpr int flags = 1;
 #endif
-#define CDE_ADJ_P(D, M)                                                                                              \
+#define CDE_ADJ_P(D, M, X)                                                                                           \
   do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)rk4_adjoint_jacobian_pair<TT, D, M>,                                      \
+    (void)hipFuncSetAttribute((const void*)rk4_adjoint_jacobian_pair<TT, D, M, X>,                                   \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-    rk4_adjoint_jacobian_pair<TT, D, M><<<blocks, 512, lds, s>>>(                                                    \
+    rk4_adjoint_jacobian_pair<TT, D, M, X><<<blocks, 512, lds, s>>>(                                                 \
         (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias,                 \
         (const float*)z_saved, (const float*)grad_out, (const TT*)sgrid, seg_off, n_out, (float*)grad_z0, partial,   \
         B, stage_index, (const float*)stage_frac, dims, flags);                                                      \
   } while (0)
 #define CDE_ADJ_PD(M)                                                                                                \
   do {                                                                                                               \
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ_P(CDE_PATH_CUBIC, M); else CDE_ADJ_P(CDE_PATH_LINEAR, M);                   \
+    if (degree == CDE_PATH_CUBIC) CDE_ADJ_P(CDE_PATH_CUBIC, M, false); else CDE_ADJ_P(CDE_PATH_LINEAR, M, false);     \
   } while (0)
   if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (method == CDE_METHOD_RK4) CDE_ADJ_PD(CDE_METHOD_RK4);
+  if (bx && method != CDE_METHOD_RK4) return CDE_ERR_UNSUPPORTED;
+  if (bx) {
+    if (degree == CDE_PATH_CUBIC) CDE_ADJ_P(CDE_PATH_CUBIC, CDE_METHOD_RK4, true);
+    else CDE_ADJ_P(CDE_PATH_LINEAR, CDE_METHOD_RK4, true);
+  } else if (method == CDE_METHOD_RK4) CDE_ADJ_PD(CDE_METHOD_RK4);
   else if (method == CDE_METHOD_MIDPOINT) CDE_ADJ_PD(CDE_METHOD_MIDPOINT);
   else if (method == CDE_METHOD_EULER) CDE_ADJ_PD(CDE_METHOD_EULER);
   else return CDE_ERR_UNSUPPORTED;
@@ -693,9 +848,11 @@ int launch_adjoint_jacobian_pair(const void* coeffs, const void* knots, int64_t 
 }
 template int launch_adjoint_jacobian_pair<float>(const void*, const void*, int64_t, int, const void*, const void*, const void*,
                                                  const void*, const void*, const int64_t*, int64_t, void*, void*, void*,
-                                                 int64_t, int64_t, int64_t, const int64_t*, const void*, float*, hipStream_t, int);
+                                                 int64_t, int64_t, int64_t, const int64_t*, const void*, float*, hipStream_t, int,
+                                                 bool);
 template int launch_adjoint_jacobian_pair<double>(const void*, const void*, int64_t, int, const void*, const void*, const void*,
                                                   const void*, const void*, const int64_t*, int64_t, void*, void*, void*,
-                                                  int64_t, int64_t, int64_t, const int64_t*, const void*, float*, hipStream_t, int);
+                                                  int64_t, int64_t, int64_t, const int64_t*, const void*, float*, hipStream_t, int,
+                                                 bool);
 
 }  // namespace cde

@@ -1356,7 +1356,7 @@ static bool k3_form_jacobian() {
 template <typename TT>
 int launch_adjoint_jacobian_pair(const void*, const void*, int64_t, int, const void*, const void*, const void*, const void*,
                                  const void*, const int64_t*, int64_t, void*, void*, void*, int64_t, int64_t, int64_t,
-                                 const int64_t*, const void*, float*, hipStream_t, int method);
+                                 const int64_t*, const void*, float*, hipStream_t, int method, bool bx = false);
 constexpr bool K3_PAIR_DEFAULT = true;       // 5.26 -> 5.01 ms on the headline workload (profiles/r05_k3_pair_b.log)
 static bool k3_form_pair() {
   const int64_t e = option(CDE_OPT_K3_WAVES);

@@ -43,7 +43,17 @@ Request = collections.namedtuple("Request", [
                          # torchdiffeq's adjoint error norm which the adaptive backward K4a carries since round 6
 ])
 
-Choice = collections.namedtuple("Choice", ["path", "reason"])
+# form: which arithmetic a fused rk4 solve of the affine field takes -- "bf16x3" (the weight GEMMs on the bf16 pipe as
+# three-piece splits: the default for the headline field above 16384 series), "bf16x3_forward" (the same forward, the
+# exact-f32 adjoint: control gradients), "exact" (the f32 kernels, e.g. variant="mfma"); "" for every other path
+# (an attribute beside the tuple, so a Choice still compares equal to its (path, reason))
+class Choice(collections.namedtuple("Choice", ["path", "reason"])):
+    form = ""
+
+    def with_form(self, form):
+        c = Choice(*self)
+        c.form = form
+        return c
 
 FUSED_PATHS = (
     "rk4",                    # K2 / K3 (+ split, wide, generic variants behind CDE_VARIANT_AUTO), incl. time / control gradients
