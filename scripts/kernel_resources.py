@@ -30,7 +30,7 @@ for line in out.splitlines():
 names = subprocess.run(["c++filt"] + [r["name"] for r in rows], stdout=subprocess.PIPE, text=True).stdout.splitlines()
 print("%-6s %-6s %-7s %-8s %-4s %-8s %s" % ("VGPR", "AGPR", "spill", "scratch", "occ", "LDS", "kernel"))
 for r, n in zip(rows, names):
-    n = re.sub(r"\(.*", "", n).replace("void cde::", "")
+    n = re.sub(r"\(.*", "", n.replace("(anonymous namespace)::", "")).replace("void cde::", "")
     if flt in n:
         print("%-6s %-6s %-7s %-8s %-4s %-8s %s" % (r.get("VGPRs"), r.get("AGPRs"), r.get("VGPRs Spill"), r.get("ScratchSize [bytes/lane]"),
                                                       r.get("Occupancy [waves/SIMD]"), r.get("LDS Size [bytes/block]"), n))

@@ -27,9 +27,11 @@ if PHASE_TRACE:
     HIPCC_FLAGS.append("-DCDE_PHASE_TRACE")
 # per-file additions.  rk4_split.hip: keep MFMA accumulators in VGPRs -- its tiles are consumed by VALU code right
 # away, and on gfx950 every v_accvgpr_read costs matrix-pipe time (f32 MFMA and VALU do not overlap within a wave).
+# rk4_adjoint_pair.hip: no SLP vectorizer -- it packs the scalar bf16 splits and the chain wave's FMAs into v_pk_* f32
+# instructions, which cost matrix-pipe time beside the partner wave's MFMAs and, in K3p, pushed both forms into scratch.
 EXTRA_FLAGS = {"rk4_split.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "rk4_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-               "rk4_adjoint_pair.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+               "rk4_adjoint_pair.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
                "dopri5_adjoint.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 F32, F64 = 0, 1

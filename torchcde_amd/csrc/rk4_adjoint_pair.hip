@@ -17,7 +17,7 @@
 //               control: it owns the stage table, the coefficient rows and the knot widths, forms dX/dt of every stage
 //               and leaves it (plain for the chain wave, weighted by the quadrature weight for itself) in a three-slot LDS
 //               ring.  That takes 30 registers and ~50 vector instructions per stage off the chain wave, which then fits
-//               256 registers (12 bytes of scratch, touched once per RK step).
+//               256 registers without scratch (all of its vector arithmetic non-packed f32).
 // One s_barrier per stage orders everything: the chain wave writes (z, a) buffer s & 1 and reads ring slot s % 3 before
 // barrier s; the helper reads both between barriers s and s + 1 and writes slot (s + 2) % 3; the chain wave's next write to
 // buffer s & 1 comes after barrier s + 1.  The matrix pipe sees the chain wave's dependent row chains and the helper's
@@ -71,6 +71,20 @@ __device__ __forceinline__ void kp_split3(float x, __bf16& a, __bf16& b, __bf16&
   const float r1 = x - (float)a;
   b = (__bf16)r1;
   c = (__bf16)(r1 - (float)b);
+}
+// kp_split3 of two values at once, the pieces already packed as the MFMA operands take them: word m holds piece m + 1 of
+// x0 in its low and of x1 in its high half.  One v_cvt_pk_bf16_f32 per piece pair (the same rounding as the scalar cast,
+// which converts one value per instruction and then needs a second instruction to pack two pieces into a word).  A vector
+// conversion, not inline asm: the compiler then sees the VALU write and gives the MFMA that reads the word its wait states.
+using kp_bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+__device__ __forceinline__ unsigned kp_cvt_pk_bf16(float lo, float hi) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, kp_bf16x2));
+}
+__device__ __forceinline__ void kp_split3x2(float x0, float x1, unsigned& a, unsigned& b, unsigned& c) {
+  a = kp_cvt_pk_bf16(x0, x1);
+  const float r0 = x0 - __uint_as_float(a << 16), r1 = x1 - __uint_as_float(a & 0xffff0000u);
+  b = kp_cvt_pk_bf16(r0, r1);
+  c = kp_cvt_pk_bf16(r0 - __uint_as_float(b << 16), r1 - __uint_as_float(b & 0xffff0000u));
 }
 // piece m of the 8 channel weights of row h at k slot j (hidden unit k = rho(j)); row MH: the bias rows
 __device__ __forceinline__ kp_u32x4 kp_wjb_image(const float* __restrict__ W, const float* __restrict__ bias, int h, int m, int j,
@@ -224,25 +238,30 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
         const float4 z0 = zt4[2 * g], z1 = zt4[2 * g + 1], a0 = at4[2 * g], a1 = at4[2 * g + 1];
         const float zv[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
         const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-        kp_bf16x8 zp1, zp2, zp3;
+        kp_u32x4 zw1, zw2, zw3;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          __bf16 p1, p2, p3;
-          kp_split3(zv[j], p1, p2, p3);
-          zp1[j] = p1; zp2[j] = p2; zp3[j] = p3;
+        for (int i = 0; i < 4; ++i) {
+          unsigned p1, p2, p3;
+          kp_split3x2(zv[2 * i], zv[2 * i + 1], p1, p2, p3);
+          zw1[i] = p1; zw2[i] = p2; zw3[i] = p3;
         }
+        const kp_bf16x8 zp1 = __builtin_bit_cast(kp_bf16x8, zw1), zp2 = __builtin_bit_cast(kp_bf16x8, zw2),
+                        zp3 = __builtin_bit_cast(kp_bf16x8, zw3);
 #pragma unroll
         for (int c = 0; c < MC; ++c) {
           const float4 e0 = dw4[c * 8 + 2 * g], e1 = dw4[c * 8 + 2 * g + 1];
           const float ev[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
-          kp_bf16x8 vp1, vp2, vp3;
+          kp_u32x4 vw1, vw2, vw3;
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            __bf16 p1, p2, p3;
-            kp_split3(ev[j] * av[j], p1, p2, p3);
-            vp1[j] = p1; vp2[j] = p2; vp3[j] = p3;
-            gbp[c >> 1][c & 1] = __builtin_fmaf(ev[j], av[j], gbp[c >> 1][c & 1]);
+          for (int i = 0; i < 4; ++i) {
+            unsigned p1, p2, p3;
+            kp_split3x2(ev[2 * i] * av[2 * i], ev[2 * i + 1] * av[2 * i + 1], p1, p2, p3);
+            vw1[i] = p1; vw2[i] = p2; vw3[i] = p3;
+            gbp[c >> 1][c & 1] = __builtin_fmaf(ev[2 * i], av[2 * i], gbp[c >> 1][c & 1]);
+            gbp[c >> 1][c & 1] = __builtin_fmaf(ev[2 * i + 1], av[2 * i + 1], gbp[c >> 1][c & 1]);
           }
+          const kp_bf16x8 vp1 = __builtin_bit_cast(kp_bf16x8, vw1), vp2 = __builtin_bit_cast(kp_bf16x8, vw2),
+                          vp3 = __builtin_bit_cast(kp_bf16x8, vw3);
           __builtin_amdgcn_sched_barrier(0);
           f32x16 acc = accW[c];
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vp3, zp1, acc, 0, 0, 0);
@@ -339,16 +358,13 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
           const float4 dB = *reinterpret_cast<const float4*>(ring_dx + rs * 256 + n * 8 + 4);
           if constexpr (BX) {
             const float dx[8] = {dA.x, dA.y, dA.z, dA.w, dB.x, dB.y, dB.z, dB.w};
-            kp_bf16x8 q01, q2;
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
-              __bf16 p1, p2, p3;
-              kp_split3(dx[c], p1, p2, p3);
-              q01[c] = half ? p2 : p1;
-              q2[c] = half ? p1 : p3;
+            for (int i = 0; i < 4; ++i) {                // channels 2i, 2i + 1 per word
+              unsigned p1, p2, p3;
+              kp_split3x2(dx[2 * i], dx[2 * i + 1], p1, p2, p3);
+              b01[i] = half ? p2 : p1;
+              b2[i] = half ? p1 : p3;
             }
-            b01 = __builtin_bit_cast(kp_u32x4, q01);
-            b2 = __builtin_bit_cast(kp_u32x4, q2);
           } else {
             bs0 = half ? dA.y : dA.x; bs1 = half ? dA.w : dA.z; bs2 = half ? dB.y : dB.x; bs3 = half ? dB.w : dB.z;
           }
@@ -367,9 +383,9 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
         // (K3j's code: rows issued one ahead of their use, explicit wait states after the last issue).
         f32x16 f, va;
         {
-          f32x2 va2[8];
+          float vs[16];                                 // a^T J, non-packed (packed f32 beside the partner's MFMAs costs pipe time)
 #pragma unroll
-          for (int j = 0; j < 8; ++j) va2[j] = f32x2{0.f, 0.f};
+          for (int j = 0; j < 16; ++j) vs[j] = 0.f;
           int opaque = 0;                               // the image reads are loop invariant: keep them inside the stage
           asm volatile("" : "+v"(opaque));
           const float4* wp = wj + lane + opaque;
@@ -401,20 +417,25 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
             }
             __builtin_amdgcn_sched_barrier(0);
           };
+          // f_h's share: four partial sums (even / odd register pairs, low / high element), (p0 + q0) + (p1 + q1) -- the
+          // packed form's order, element by element, so the sums are bitwise K3j's / K3bj's
           auto consume = [&](const f32x16& J, float ah) {
-            const f32x2 ah2 = {ah, ah};
-            f32x2 p2 = {0.f, 0.f}, q2 = {0.f, 0.f};
+            float p0 = 0.f, p1 = 0.f, q0 = 0.f, q1 = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-              const f32x2 m = {J[2 * j], J[2 * j + 1]};
-              if (j & 1) q2 = __builtin_elementwise_fma(m, f32x2{yst[2 * j], yst[2 * j + 1]}, q2);
-              else p2 = __builtin_elementwise_fma(m, f32x2{yst[2 * j], yst[2 * j + 1]}, p2);
-              va2[j] = __builtin_elementwise_fma(m, ah2, va2[j]);
+              if (j & 1) {
+                q0 = __builtin_fmaf(J[2 * j], yst[2 * j], q0);
+                q1 = __builtin_fmaf(J[2 * j + 1], yst[2 * j + 1], q1);
+              } else {
+                p0 = __builtin_fmaf(J[2 * j], yst[2 * j], p0);
+                p1 = __builtin_fmaf(J[2 * j + 1], yst[2 * j + 1], p1);
+              }
+              vs[2 * j] = __builtin_fmaf(J[2 * j], ah, vs[2 * j]);
+              vs[2 * j + 1] = __builtin_fmaf(J[2 * j + 1], ah, vs[2 * j + 1]);
             }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(va2[j]));
-            p2 = p2 + q2;
-            return p2[0] + p2[1];
+            for (int j = 0; j < 16; ++j) asm volatile("" : "+v"(vs[j]));
+            return (p0 + q0) + (p1 + q1);
           };
           f32x16 Je, Jo;                                 // rows 2r / 2r + 1 in flight
           if constexpr (BX) {
@@ -466,36 +487,40 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             f[r] += Je[r];
-            va[r] = va2[r >> 1][r & 1];
+            va[r] = vs[r];
           }
         }
 
-        // ---- reverse-time dynamics: dy/ds = -f, da/ds = +a^T df/dz.  3/8 rule in two slots per variable
-        const f32x16 ky = -f, ka = va;
+        // ---- reverse-time dynamics: dy/ds = -f, da/ds = +a^T df/dz.  3/8 rule in two slots per variable; element by
+        // element in scalar (non-packed) instructions, each expression in its original order
         const float third = (float)(1.0 / 3.0);
-        if constexpr (METHOD == CDE_METHOD_EULER) {                    // y1 = y0 + ds * k
-          yst = y0 + ds * ky;
-          ast = a0 + ds * ka;
-        } else if constexpr (METHOD == CDE_METHOD_MIDPOINT) {          // mid = y0 + k1 * half_ds; y1 = y0 + ds * k(mid)
-          const float half_ds = 0.5f * ds;
-          if (stage == 0) { yst = y0 + ky * half_ds; ast = a0 + ka * half_ds; }
-          else { yst = y0 + ds * ky; ast = a0 + ds * ka; }
-        } else if (stage == 0) {
-          ky1 = ky; ka1 = ka;
-          yst = y0 + ds * ky1 * third;
-          ast = a0 + ds * ka1 * third;
-        } else if (stage == 1) {
-          ky2 = ky; ka2 = ka;
-          yst = y0 + ds * (ky2 - ky1 * third);
-          ast = a0 + ds * (ka2 - ka1 * third);
-        } else if (stage == 2) {
-          yst = y0 + ds * (ky1 - ky2 + ky);
-          ast = a0 + ds * (ka1 - ka2 + ka);
-          ky1 = ky1 + 3.f * (ky2 + ky);
-          ka1 = ka1 + 3.f * (ka2 + ka);
-        } else {
-          yst = y0 + (ky1 + ky) * ds * 0.125f;
-          ast = a0 + (ka1 + ka) * ds * 0.125f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float ky = -f[r], ka = va[r];
+          if constexpr (METHOD == CDE_METHOD_EULER) {                  // y1 = y0 + ds * k
+            yst[r] = y0[r] + ds * ky;
+            ast[r] = a0[r] + ds * ka;
+          } else if constexpr (METHOD == CDE_METHOD_MIDPOINT) {        // mid = y0 + k1 * half_ds; y1 = y0 + ds * k(mid)
+            const float half_ds = 0.5f * ds;
+            if (stage == 0) { yst[r] = y0[r] + ky * half_ds; ast[r] = a0[r] + ka * half_ds; }
+            else { yst[r] = y0[r] + ds * ky; ast[r] = a0[r] + ds * ka; }
+          } else if (stage == 0) {
+            ky1[r] = ky; ka1[r] = ka;
+            yst[r] = y0[r] + ds * ky * third;
+            ast[r] = a0[r] + ds * ka * third;
+          } else if (stage == 1) {
+            ky2[r] = ky; ka2[r] = ka;
+            yst[r] = y0[r] + ds * (ky - ky1[r] * third);
+            ast[r] = a0[r] + ds * (ka - ka1[r] * third);
+          } else if (stage == 2) {
+            yst[r] = y0[r] + ds * (ky1[r] - ky2[r] + ky);
+            ast[r] = a0[r] + ds * (ka1[r] - ka2[r] + ka);
+            ky1[r] = ky1[r] + 3.f * (ky2[r] + ky);
+            ka1[r] = ka1[r] + 3.f * (ka2[r] + ka);
+          } else {
+            yst[r] = y0[r] + (ky1[r] + ky) * ds * 0.125f;
+            ast[r] = a0[r] + (ka1[r] + ka) * ds * 0.125f;
+          }
         }
       }
       y0 = yst; a0 = ast;
