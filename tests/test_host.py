@@ -1055,7 +1055,7 @@ def test_reverse_mode_recurrences_of_the_rk4_backprop_kernel_equal_autograd_thro
         with torch.no_grad():
             assert torch.allclose(gx, coeffs.grad, rtol=1e-6, atol=1e-9)
             # the knot times: frac = t - knot_j, so dL/d knot_j = - sum over the stages in interval j of gdx . d2X/dt2 -- which is
-            # a contraction of the coefficient gradient itself (cdeint.py: _plan_time_gradients)
+            # a contraction of the coefficient gradient itself (cdeint.py: _time_gradients)
             per_interval = (coeffs[..., 2 * C:3 * C] * gx[..., C:2 * C] + 2 * coeffs[..., 3 * C:] * gx[..., 2 * C:3 * C]).sum((0, 2))
             assert torch.allclose(torch.cat([-per_interval, per_interval.new_zeros(1)]), knots.grad, rtol=1e-6, atol=1e-9)
 

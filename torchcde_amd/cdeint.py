@@ -208,7 +208,24 @@ def _grids_for(t_host, step_size, adjoint_step_size, device):
     return hit
 
 
-def _plan_time_gradients(plan, z_saved, grad_out, weight, bias, grad_x, t, want_t, want_knots):
+def _field_values(act, weights, z):
+    """F(z) of a fused field, (..., H * C): Linear(H, H * C) -- weights (W, b) -- or the two-layer Linear -> relu -> Linear --
+    weights (W1, b1, W2, b2) -- followed by the field's activation."""
+    if len(weights) == 4:
+        z = torch.nn.functional.linear(z, weights[0], weights[1]).relu()
+    y = torch.nn.functional.linear(z, weights[-2], weights[-1])
+    return y.tanh() if act == _lib.ACT_TANH else y
+
+
+def _weight_args(weights):
+    """The weight arguments of the C ABI: (W, b) of the affine field, or (W1, b1, width, W2, b2) of the two-layer one."""
+    if len(weights) == 2:
+        return _lib.ptr(weights[0]), _lib.ptr(weights[1])
+    w1, b1, w2, b2 = weights
+    return _lib.ptr(w1), _lib.ptr(b1), w1.size(0), _lib.ptr(w2), _lib.ptr(b2)
+
+
+def _time_gradients(plan, z_saved, grad_out, weights, grad_x, t, want_t, want_knots):
     """Gradients with respect to times from what the adjoint sweep already produced (torchdiffeq's odeint_adjoint,
     SURVEY appendix A.4, for f(t, z) = F(z) dX/dt(t)):
       dL/dt_i (i >= 1) = f(t_i, z_i) . dL/dz_i                       -- one field evaluation per output time
@@ -220,27 +237,22 @@ def _plan_time_gradients(plan, z_saved, grad_out, weight, bias, grad_x, t, want_
     (interpolation_linear.py:189): with G_j = dL/d(slope_j), dL/dh_j = -G_j . slope_j / h_j, and G_j / h_j is minus the
     running sum of the knot-value gradient the sweep produced (dL/dx_j = G_{j-1} / h_{j-1} - G_j / h_j telescopes)."""
     B, H, C = plan.B, plan.H, plan.C
-    dev = plan.device
     coeffs = plan.coeffs                                              # (B, rows, width)
     if plan.degree == _lib.PATH_CUBIC:
-        two_c, three_d = coeffs[..., 2 * C:3 * C], coeffs[..., 3 * C:]
-        q = (two_c * grad_x[..., C:2 * C] + 2 * three_d * grad_x[..., 2 * C:3 * C]).sum(-1)      # (B, intervals)
-        per_interval = q.sum(0)
+        per_interval = (coeffs[..., 2 * C:3 * C] * grad_x[..., C:2 * C]
+                        + 2 * coeffs[..., 3 * C:] * grad_x[..., 2 * C:3 * C]).sum(-1).sum(0)      # (intervals,)
     else:
-        per_interval = torch.zeros(coeffs.size(1) - 1, dtype=coeffs.dtype, device=dev)
+        per_interval = torch.zeros(coeffs.size(1) - 1, dtype=coeffs.dtype, device=plan.device)
     grad_t = grad_knots = None
     if want_t:
         zs = z_saved.reshape(B, plan.n_out, H)
         go = grad_out.reshape(B, plan.n_out, H)
         vals = [None] * plan.n_out
-        total = torch.zeros((), dtype=coeffs.dtype, device=dev)
+        total = torch.zeros((), dtype=coeffs.dtype, device=plan.device)
         for i in range(1, plan.n_out):
-            y = torch.nn.functional.linear(zs[:, i], weight, bias)
-            if plan.act == _lib.ACT_TANH:
-                y = y.tanh()
+            y = _field_values(plan.act, weights, zs[:, i])
             dX = plan.path.derivative(plan.t_out[i]).reshape(B, C)
-            f = (y.view(B, H, C) * dX.unsqueeze(1)).sum(-1)
-            vals[i] = (f * go[:, i]).sum()
+            vals[i] = ((y.view(B, H, C) * dX.unsqueeze(1)).sum(-1) * go[:, i]).sum()
             total = total + vals[i]
         vals[0] = per_interval.sum() - total
         # on `t`'s own device: cdeint accepts a CPU `t` next to GPU data (as the reference does)
@@ -290,58 +302,46 @@ class _Plan:
         self.stage_index = None
         self.stage_frac = None
 
-    time_gradients = _plan_time_gradients
+    time_gradients = _time_gradients
 
-    # forward: K2
-    def run_forward(self, z0, weight, bias):
-        lib = _lib.load()
-        out = torch.empty(self.B, self.n_out, self.H, dtype=self.dtype, device=self.device)
-        n_stage = 4 * max(self.grid.numel() - 1, 0)
-        self.stage_index = torch.empty(max(n_stage, 1), dtype=torch.int64, device=self.device)
-        self.stage_frac = torch.empty(max(n_stage, 1), dtype=self.dtype, device=self.device)
-        z0c = z0.detach().reshape(self.B, self.H).contiguous()
-        w = weight.detach().contiguous()
-        b = bias.detach().contiguous()
-        begin = self._mark()
-        if self.method != _lib.METHOD_RK4:
-            _lib.check(lib.cde_fixed_forward_linear(
-                self.method, _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w),
-                _lib.ptr(b), _lib.ptr(z0c), _lib.ptr(self.grid), self.grid.numel(), _lib.ptr(self.t_out), self.n_out,
-                _lib.ptr(out), self.B, self.C, self.H, _lib.dtype_enum(self.dtype), _lib.dtype_enum(self.time_dtype),
-                _lib.ptr(self.stage_index), _lib.ptr(self.stage_frac), _lib.stream_ptr(self.device)),
-                "cde_fixed_forward_linear")
-        else:
-            _lib.check(lib.cde_rk4_forward_linear(
-                _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(b),
-                self.act, _lib.ptr(z0c), _lib.ptr(self.grid), self.grid.numel(), _lib.ptr(self.t_out), self.n_out,
-                _lib.ptr(out), self.B, self.C, self.H, _lib.dtype_enum(self.dtype), _lib.dtype_enum(self.time_dtype),
-                self.variant, _lib.ptr(self.stage_index), _lib.ptr(self.stage_frac), _lib.stream_ptr(self.device)),
-                "cde_rk4_forward_linear")
+    def _log(self, kind, begin):
         if begin is not None:
-            self.owner.event_log.append(("forward", begin, self._mark()))
-        return out
+            self.owner.event_log.append((kind, begin, self._mark()))
 
-    # adjoint=False: K2 that also stores every stage state, and the reverse-mode sweep over them (K3d)
-    def run_forward_stages(self, z0, weight, bias):
+    def _parameter_gradients(self):
+        """dL/dW and dL/db as two views of ONE flat buffer: a data-parallel caller can all-reduce that buffer in a single
+        collective without gather/scatter copies (torchcde_amd.distributed.allreduce_gradients)."""
+        n_w = self.H * self.C * self.H
+        flat = torch.empty(n_w + self.H * self.C, dtype=self.dtype, device=self.device)
+        return flat[:n_w].view(self.H * self.C, self.H), flat[n_w:]
+
+    # forward: K2.  stages (adjoint=False): K2 also stores every stage state for the reverse-mode sweep (K3d), and
+    # (out, stages) is returned
+    def run_forward(self, z0, weight, bias, stages=False):
         lib = _lib.load()
         out = torch.empty(self.B, self.n_out, self.H, dtype=self.dtype, device=self.device)
         n_steps = max(self.grid.numel() - 1, 0)
         self.stage_index = torch.empty(max(4 * n_steps, 1), dtype=torch.int64, device=self.device)
         self.stage_frac = torch.empty(max(4 * n_steps, 1), dtype=self.dtype, device=self.device)
-        stages = torch.empty(self.B, max(n_steps, 1), 4, 32, dtype=torch.float32, device=self.device)
         z0c = z0.detach().reshape(self.B, self.H).contiguous()
         w = weight.detach().contiguous()
         b = bias.detach().contiguous()
+        head = (_lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(b))
+        grid = (_lib.ptr(z0c), _lib.ptr(self.grid), self.grid.numel(), _lib.ptr(self.t_out), self.n_out, _lib.ptr(out))
+        shape = (self.B, self.C, self.H, _lib.dtype_enum(self.dtype), _lib.dtype_enum(self.time_dtype))
+        tail = (_lib.ptr(self.stage_index), _lib.ptr(self.stage_frac), _lib.stream_ptr(self.device))
+        stages = torch.empty(self.B, max(n_steps, 1), 4, 32, dtype=torch.float32, device=self.device) if stages else None
         begin = self._mark()
-        _lib.check(lib.cde_rk4_forward_linear_stages(
-            _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(b), self.act,
-            _lib.ptr(z0c), _lib.ptr(self.grid), self.grid.numel(), _lib.ptr(self.t_out), self.n_out, _lib.ptr(out),
-            _lib.ptr(stages), self.B, self.C, self.H, _lib.dtype_enum(self.dtype), _lib.dtype_enum(self.time_dtype),
-            _lib.ptr(self.stage_index), _lib.ptr(self.stage_frac), _lib.stream_ptr(self.device)),
-            "cde_rk4_forward_linear_stages")
-        if begin is not None:
-            self.owner.event_log.append(("forward", begin, self._mark()))
-        return out, stages
+        if stages is not None:
+            _lib.check(lib.cde_rk4_forward_linear_stages(*head, self.act, *grid, _lib.ptr(stages), *shape, *tail),
+                       "cde_rk4_forward_linear_stages")
+        elif self.method != _lib.METHOD_RK4:
+            _lib.check(lib.cde_fixed_forward_linear(self.method, *head, *grid, *shape, *tail), "cde_fixed_forward_linear")
+        else:
+            _lib.check(lib.cde_rk4_forward_linear(*head, self.act, *grid, *shape, self.variant, *tail),
+                       "cde_rk4_forward_linear")
+        self._log("forward", begin)
+        return out if stages is None else (out, stages)
 
     def run_backprop(self, stages, grad_out, weight, bias, want_control=False):
         lib = _lib.load()
@@ -349,92 +349,69 @@ class _Plan:
         nbytes = lib.cde_rk4_backprop_workspace_bytes(self.B)
         workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
         grad_z0 = torch.empty(self.B, self.H, dtype=self.dtype, device=self.device)
-        n_w = self.H * self.C * self.H
-        flat = torch.empty(n_w + self.H * self.C, dtype=self.dtype, device=self.device)     # one buffer: see run_adjoint
-        grad_w, grad_b = flat[:n_w].view(self.H * self.C, self.H), flat[n_w:]
+        grad_w, grad_b = self._parameter_gradients()
         go = grad_out.detach().reshape(self.B, self.n_out, self.H).contiguous()
-        w = weight.detach().contiguous()
-        bvec = bias.detach().contiguous()
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        head = (_lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(b),
+                self.act, _lib.ptr(stages), _lib.ptr(go), self.n_out, _lib.ptr(step_dt), n_steps, _lib.ptr(node_ptr),
+                _lib.ptr(node_out), _lib.ptr(node_weight), _lib.ptr(grad_z0), _lib.ptr(grad_w), _lib.ptr(grad_b))
+        tail = (self.B, self.C, self.H, _lib.dtype_enum(self.dtype), _lib.ptr(self.stage_index), _lib.ptr(self.stage_frac),
+                _lib.ptr(workspace), workspace.numel(), _lib.stream_ptr(self.device))
         begin = self._mark()
         grad_x = None
         if want_control:
             # the control's tensors require a gradient (autograd reaches them through X.derivative at every stage)
             grad_x = torch.zeros_like(self.coeffs)          # (B, rows, width) like the packed coefficients
-            _lib.check(lib.cde_rk4_backprop_linear_dcontrol(
-                _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(bvec),
-                self.act, _lib.ptr(stages), _lib.ptr(go), self.n_out, _lib.ptr(step_dt), n_steps, _lib.ptr(node_ptr),
-                _lib.ptr(node_out), _lib.ptr(node_weight), _lib.ptr(grad_z0), _lib.ptr(grad_w), _lib.ptr(grad_b),
-                _lib.ptr(grad_x), self.B, self.C, self.H, _lib.dtype_enum(self.dtype), _lib.ptr(self.stage_index),
-                _lib.ptr(self.stage_frac), _lib.ptr(workspace), workspace.numel(), _lib.stream_ptr(self.device)),
-                "cde_rk4_backprop_linear_dcontrol")
+            _lib.check(lib.cde_rk4_backprop_linear_dcontrol(*head, _lib.ptr(grad_x), *tail), "cde_rk4_backprop_linear_dcontrol")
         else:
-            _lib.check(lib.cde_rk4_backprop_linear(
-                _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(bvec),
-                self.act, _lib.ptr(stages), _lib.ptr(go), self.n_out, _lib.ptr(step_dt), n_steps, _lib.ptr(node_ptr),
-                _lib.ptr(node_out), _lib.ptr(node_weight), _lib.ptr(grad_z0), _lib.ptr(grad_w), _lib.ptr(grad_b), self.B,
-                self.C, self.H, _lib.dtype_enum(self.dtype), _lib.ptr(self.stage_index), _lib.ptr(self.stage_frac),
-                _lib.ptr(workspace), workspace.numel(), _lib.stream_ptr(self.device)), "cde_rk4_backprop_linear")
-        if begin is not None:
-            self.owner.event_log.append(("backprop", begin, self._mark()))
+            _lib.check(lib.cde_rk4_backprop_linear(*head, *tail), "cde_rk4_backprop_linear")
+        self._log("backprop", begin)
         return grad_z0, grad_w, grad_b, grad_x
 
     # backward: K3
     def run_adjoint(self, z_saved, grad_out, weight, bias, want_control=False):
         lib = _lib.load()
-        sgrid, seg_off, n_sgrid = self.grids.sgrid, self.grids.seg_off, self.grids.n_sgrid
+        g = self.grids
         dt = _lib.dtype_enum(self.dtype)
         variant = _lib.VARIANT_MFMA if want_control else self.variant
         fixed = self.method != _lib.METHOD_RK4
-        nbytes = (lib.cde_fixed_adjoint_workspace_bytes(self.B, n_sgrid) if fixed else
-                  lib.cde_rk4_adjoint_workspace_bytes(self.B, self.C, self.H, n_sgrid, dt, variant))
+        nbytes = (lib.cde_fixed_adjoint_workspace_bytes(self.B, g.n_sgrid) if fixed else
+                  lib.cde_rk4_adjoint_workspace_bytes(self.B, self.C, self.H, g.n_sgrid, dt, variant))
         workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
         grad_z0 = torch.empty(self.B, self.H, dtype=self.dtype, device=self.device)
-        # weight and bias gradients are two views of ONE flat buffer: a data-parallel caller can all-reduce that
-        # buffer in a single collective without gather/scatter copies (torchcde_amd.distributed.allreduce_gradients)
-        n_w = self.H * self.C * self.H
-        flat = torch.empty(n_w + self.H * self.C, dtype=self.dtype, device=self.device)
-        grad_w, grad_b = flat[:n_w].view(self.H * self.C, self.H), flat[n_w:]
+        grad_w, grad_b = self._parameter_gradients()
         zs = z_saved.detach().contiguous()
         go = grad_out.detach().reshape(self.B, self.n_out, self.H).contiguous()
-        w = weight.detach().contiguous()
-        b = bias.detach().contiguous()
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        head = (_lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(b))
+        sweep = (_lib.ptr(zs), _lib.ptr(go), _lib.ptr(g.sgrid), g.n_sgrid, _lib.ptr(g.seg_off))
+        grads = (_lib.ptr(grad_z0), _lib.ptr(grad_w), _lib.ptr(grad_b))
+        shape = (self.B, self.C, self.H, dt, _lib.dtype_enum(self.time_dtype))
+        tail = (_lib.ptr(workspace), workspace.numel(), _lib.stream_ptr(self.device))
         begin = self._mark()
         grad_x = None
         if fixed:
-            _lib.check(lib.cde_fixed_adjoint_linear(
-                self.method, _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w),
-                _lib.ptr(b), _lib.ptr(zs), _lib.ptr(go), _lib.ptr(sgrid), n_sgrid, _lib.ptr(seg_off), self.n_out,
-                _lib.ptr(grad_z0), _lib.ptr(grad_w), _lib.ptr(grad_b), self.B, self.C, self.H, dt,
-                _lib.dtype_enum(self.time_dtype), _lib.ptr(workspace), workspace.numel(), _lib.stream_ptr(self.device)),
-                "cde_fixed_adjoint_linear")
+            _lib.check(lib.cde_fixed_adjoint_linear(self.method, *head, *sweep, self.n_out, *grads, *shape, *tail),
+                       "cde_fixed_adjoint_linear")
         elif want_control:
             grad_x = torch.zeros_like(self.coeffs)          # (B, rows, width) like the packed coefficients
-            _lib.check(lib.cde_rk4_adjoint_linear_dcontrol(
-                _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(b),
-                self.act, _lib.ptr(zs), _lib.ptr(go), _lib.ptr(sgrid), n_sgrid, _lib.ptr(seg_off), self.n_out,
-                _lib.ptr(grad_z0), _lib.ptr(grad_w), _lib.ptr(grad_b), _lib.ptr(grad_x), self.B, self.C, self.H, dt,
-                _lib.dtype_enum(self.time_dtype), _lib.ptr(workspace), workspace.numel(),
-                _lib.stream_ptr(self.device)), "cde_rk4_adjoint_linear_dcontrol")
+            _lib.check(lib.cde_rk4_adjoint_linear_dcontrol(*head, self.act, *sweep, self.n_out, *grads, _lib.ptr(grad_x),
+                                                           *shape, *tail), "cde_rk4_adjoint_linear_dcontrol")
         else:
-            _lib.check(lib.cde_rk4_adjoint_linear(
-                _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(b),
-                self.act, _lib.ptr(zs), _lib.ptr(go), _lib.ptr(sgrid), n_sgrid, _lib.ptr(seg_off),
-                ctypes.cast(self.grids.seg_off_c, ctypes.c_void_p), self.n_out,
-                _lib.ptr(grad_z0), _lib.ptr(grad_w), _lib.ptr(grad_b), self.B, self.C, self.H, dt,
-                _lib.dtype_enum(self.time_dtype), self.variant, _lib.ptr(workspace), workspace.numel(),
-                _lib.stream_ptr(self.device)), "cde_rk4_adjoint_linear")
-        if begin is not None:
-            self.owner.event_log.append(("adjoint", begin, self._mark()))
+            _lib.check(lib.cde_rk4_adjoint_linear(*head, self.act, *sweep, ctypes.cast(g.seg_off_c, ctypes.c_void_p),
+                                                  self.n_out, *grads, *shape, self.variant, *tail), "cde_rk4_adjoint_linear")
+        self._log("adjoint", begin)
         return grad_z0, grad_w, grad_b, grad_x
 
 
-def _output_layer_gradients(acc2, H, C, width):
-    """(dL/dW2, dL/db2) from the reduced images: (halves, 256, 132), rows = the padded (hidden unit, channel) layout of the G2
-    rows -- 32 units x 8 channels, or 16 x 16 per half (two halves: hidden units 0..15 and 16..31) -- bias in column 128."""
+def _mlp_gradients(acc1, acc2, H, C, width):
+    """(dL/dW1, dL/db1, dL/dW2, dL/db2) from the reduced images.  acc1: (128, >= 33), hidden units x (H inputs, bias in
+    column 32).  acc2: (halves, 256, >= 129), rows = the padded (hidden unit, channel) layout of the G2 rows -- 32 units x 8
+    channels, or 16 x 16 per half (two halves: hidden units 0..15 and 16..31) -- bias in column 128."""
     units, channels = (32, 8) if C <= 8 else (16, 16)
-    w = acc2[:, :, :width].reshape(acc2.size(0) * units, channels, width)[:H, :C].reshape(H * C, width)
-    b = acc2[:, :, 128].reshape(acc2.size(0) * units, channels)[:H, :C].reshape(H * C)
-    return w, b
+    w2 = acc2[:, :, :width].reshape(acc2.size(0) * units, channels, width)[:H, :C].reshape(H * C, width)
+    b2 = acc2[:, :, 128].reshape(acc2.size(0) * units, channels)[:H, :C].reshape(H * C)
+    return acc1[:width, :H].contiguous(), acc1[:width, 32].contiguous(), w2, b2
 
 
 class _MlpPlan:
@@ -447,48 +424,83 @@ class _MlpPlan:
         coeffs, knots, _ = path._native_inputs()
         self.coeffs, self.knots = coeffs, knots
         self.n_intervals, self.degree = path._n_intervals(), path._degree
-        self.field, self.batch, self.B, self.H, self.C = field, batch, coeffs.size(0), H, C
+        self.field, self.act, self.batch, self.B, self.H, self.C = field, field.act, batch, coeffs.size(0), H, C
         self.path = path
         self.device = coeffs.device
         self.grids = _grids_for(_to_host(t), step_size, step_size if adjoint_step_size is None else adjoint_step_size,
                                 self.device)
-        self.n_out = self.grids.n_out
+        self.n_out, self.t_out = self.grids.n_out, self.grids.t_out
 
     def _weights(self, saved=None):
         f = self.field
         tensors = (f.hidden.weight, f.hidden.bias, f.output.weight, f.output.bias) if saved is None else saved
         return tuple(p.detach().contiguous() for p in tensors)
 
-    def run(self, z0):
+    # stages (adjoint=False): K2m also stores every stage state for K3m's sweep as reverse mode through the steps, and
+    # (out, stages) is returned
+    def run(self, z0, stages=False):
         lib = _lib.load()
-        g, f = self.grids, self.field
+        g = self.grids
         out = torch.empty(self.B, g.n_out, self.H, dtype=torch.float32, device=self.device)
-        n_stage = 4 * max(g.grid.numel() - 1, 0)
-        stage_index = torch.empty(max(n_stage, 1), dtype=torch.int64, device=self.device)
-        stage_frac = torch.empty(max(n_stage, 1), dtype=torch.float32, device=self.device)
+        n_steps = max(g.grid.numel() - 1, 0)
+        stage_index = torch.empty(max(4 * n_steps, 1), dtype=torch.int64, device=self.device)
+        stage_frac = torch.empty(max(4 * n_steps, 1), dtype=torch.float32, device=self.device)
         z0c = z0.detach().reshape(self.B, self.H).contiguous()
-        w1, b1, w2, b2 = self._weights()
-        _lib.check(lib.cde_rk4_forward_mlp(
-            _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w1), _lib.ptr(b1),
-            w1.size(0), _lib.ptr(w2), _lib.ptr(b2), f.act, _lib.ptr(z0c), _lib.ptr(g.grid), g.grid.numel(),
-            _lib.ptr(g.t_out), g.n_out, _lib.ptr(out), self.B, self.C, self.H, _lib.dtype_enum(torch.float32),
-            _lib.dtype_enum(g.time_dtype), _lib.ptr(stage_index), _lib.ptr(stage_frac), _lib.stream_ptr(self.device)),
-            "cde_rk4_forward_mlp")
+        weights = self._weights()
+        head = (_lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, *_weight_args(weights), self.act,
+                _lib.ptr(z0c), _lib.ptr(g.grid), g.grid.numel(), _lib.ptr(g.t_out), g.n_out, _lib.ptr(out))
+        tail = (self.B, self.C, self.H, _lib.dtype_enum(torch.float32), _lib.dtype_enum(g.time_dtype), _lib.ptr(stage_index),
+                _lib.ptr(stage_frac), _lib.stream_ptr(self.device))
+        if stages:
+            stages = torch.empty(self.B, max(n_steps, 1), 4, 32, dtype=torch.float32, device=self.device)
+            _lib.check(lib.cde_rk4_forward_mlp_stages(*head, _lib.ptr(stages), *tail), "cde_rk4_forward_mlp_stages")
+            return out.reshape(*self.batch, g.n_out, self.H), stages
+        _lib.check(lib.cde_rk4_forward_mlp(*head, *tail), "cde_rk4_forward_mlp")
         return out.reshape(*self.batch, g.n_out, self.H)
 
-    def run_adjoint(self, z_saved, grad_out, want_control=False, weights=None):
+    def _sweep_and_reduce(self, width, longest, sweeps):
+        """The sweep's per-stage factor rows, reduced chunk by chunk into the parameter gradients by the split-K MFMA
+        reduction (cde_mlp_grad_reduce; the bias gradients are the column sums of the same factors).  `sweeps(chunk, rows)`
+        is a generator that launches the sweep over at most `chunk` steps at a time into rows = (U, G2, G1, Z) and yields
+        the number of steps of each launch; `longest`: the most steps one launch can take (0: none)."""
+        lib = _lib.load()
+        B, dev = self.B, self.device
+        upper = _mlp_upper_half(self.H, self.C)     # 32 units x 16 channels: the sweep leaves the upper unit groups' dL/dY2
+        halves = 2 if upper else 1                  # rows BEHIND the lower groups' in G2 (rows n .. 2n - 1); each half is
+        acc2 = torch.zeros(halves, 256, 132, dtype=torch.float32, device=dev)            # reduced into its own image
+        acc1 = torch.zeros(128, 36, dtype=torch.float32, device=dev)
+        if longest > 0:
+            row_bytes = (132 + 256 * halves + 128 + 36) * 4
+            chunk = max(1, min(longest, self.scratch_budget // (row_bytes * 4 * B)))
+            rows = chunk * 4 * B
+            U = torch.zeros(rows, 132, dtype=torch.float32, device=dev)
+            U[:, 128] = 1
+            Z = torch.zeros(rows, 36, dtype=torch.float32, device=dev)
+            Z[:, 32] = 1
+            G2 = torch.empty(halves * rows, 256, dtype=torch.float32, device=dev)
+            G1 = torch.empty(rows, 128, dtype=torch.float32, device=dev)
+            reduce_ws = torch.empty(lib.cde_mlp_grad_reduce_workspace_bytes(), dtype=torch.uint8, device=dev)
+            stream = _lib.stream_ptr(dev)
+            for steps in sweeps(chunk, (_lib.ptr(U), _lib.ptr(G2), _lib.ptr(G1), _lib.ptr(Z))):
+                n = 4 * steps * B
+                for half in range(halves):
+                    _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G2[half * n:]), _lib.ptr(U), n, 2, _lib.ptr(acc2[half]),
+                                                       _lib.ptr(reduce_ws), reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
+                _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G1), _lib.ptr(Z), n, 1, _lib.ptr(acc1), _lib.ptr(reduce_ws),
+                                                   reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
+        return _mlp_gradients(acc1, acc2, self.H, self.C, width)
+
+    def run_adjoint(self, z_saved, grad_out, w1, b1, w2, b2, want_control=False):
         """torchdiffeq's odeint_adjoint backward for this field: per output interval (last to first) the augmented
-        state is integrated in reversed time by K3m in chunks of steps; each chunk's per-stage factors (in HBM) are
-        reduced into the parameter gradients by the split-K MFMA reduction (cde_mlp_grad_reduce; the bias gradients are
-        the column sums of the same factors).
-        ``weights``: the parameter tensors saved by the forward pass (an in-place update between forward and backward
+        state is integrated in reversed time by K3m in chunks of steps, each chunk's factors reduced into the parameter
+        gradients (_sweep_and_reduce).
+        The weights: the parameter tensors saved by the forward pass (an in-place update between forward and backward
         then trips autograd's version check instead of silently using the new values)."""
         lib = _lib.load()
-        g, f = self.grids, self.field
+        g = self.grids
         B, H, C = self.B, self.H, self.C
         dev, f32 = self.device, _lib.dtype_enum(torch.float32)
-        w1, b1, w2, b2 = self._weights(weights)
-        width = w1.size(0)
+        weights = self._weights((w1, b1, w2, b2))
         nbytes = lib.cde_rk4_adjoint_mlp_workspace_bytes(g.n_sgrid)
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         stream = _lib.stream_ptr(dev)
@@ -499,82 +511,41 @@ class _MlpPlan:
         # .contiguous() would hand the kernel the caller's own output / gradient tensors
         y = z_saved[:, -1].clone(memory_format=torch.contiguous_format)
         a = grad_out[:, -1].to(torch.float32).clone(memory_format=torch.contiguous_format)
-        upper = _mlp_upper_half(H, C)     # 32 units x 16 channels: the sweep leaves the upper unit groups' dL/dY2 rows BEHIND
-        halves = 2 if upper else 1        # the lower groups' in G2 (rows n .. 2n - 1); each half is reduced into its own image
-        acc2 = torch.zeros(halves, 256, 132, dtype=torch.float32, device=dev)
-        acc1 = torch.zeros(128, 36, dtype=torch.float32, device=dev)
         grad_x = torch.zeros_like(self.coeffs) if want_control else None     # accumulated by the sweep launches
         if g.n_sgrid > 1:
             _lib.check(lib.cde_rk4_adjoint_mlp_prepare(
-                _lib.ptr(self.knots), self.n_intervals, _lib.ptr(g.sgrid), g.n_sgrid, _lib.ptr(w1), _lib.ptr(b1), width,
-                _lib.ptr(w2), _lib.ptr(b2), C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream),
-                "cde_rk4_adjoint_mlp_prepare")
-            row_bytes = (132 + 256 * halves + 128 + 36) * 4
-            longest = max(g.seg_off_host[p + 1] - 1 - g.seg_off_host[p] for p in range(self.n_out - 1))
-            chunk = max(1, min(longest, self.scratch_budget // (row_bytes * 4 * B)))
-            rows = chunk * 4 * B
-            U = torch.zeros(rows, 132, dtype=torch.float32, device=dev)
-            U[:, 128] = 1
-            Z = torch.zeros(rows, 36, dtype=torch.float32, device=dev)
-            Z[:, 32] = 1
-            G2 = torch.empty(halves * rows, 256, dtype=torch.float32, device=dev)
-            G1 = torch.empty(rows, 128, dtype=torch.float32, device=dev)
-            reduce_ws = torch.empty(lib.cde_mlp_grad_reduce_workspace_bytes(), dtype=torch.uint8, device=dev)
-        for p in range(self.n_out - 1):
-            k, k_end = g.seg_off_host[p], g.seg_off_host[p + 1] - 1
-            while k < k_end:
-                ke = min(k_end, k + chunk)
-                _lib.check(lib.cde_rk4_adjoint_mlp_sweep(
-                    _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, f.act, _lib.ptr(y),
-                    _lib.ptr(a), _lib.ptr(g.sgrid), g.n_sgrid, k, ke, _lib.ptr(U), _lib.ptr(G2), _lib.ptr(G1),
-                    _lib.ptr(Z), _lib.ptr(grad_x), B, C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream),
-                    "cde_rk4_adjoint_mlp_sweep")
-                n = 4 * (ke - k) * B
-                for half in range(halves):
-                    _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G2[half * n:]), _lib.ptr(U), n, 2, _lib.ptr(acc2[half]),
-                                                       _lib.ptr(reduce_ws), reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
-                _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G1), _lib.ptr(Z), n, 1, _lib.ptr(acc1), _lib.ptr(reduce_ws),
-                                                   reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
-                k = ke
-            i_out = self.n_out - 1 - p
-            y.copy_(z_saved[:, i_out - 1])                 # torchdiffeq: re-seed z from the stored forward solution
-            a += grad_out[:, i_out - 1]                    # and add the incoming gradient at that output time
-        grad_w2, grad_b2 = _output_layer_gradients(acc2, H, C, width)
-        grad_w1 = acc1[:width, :H].contiguous()
-        grad_b1 = acc1[:width, 32].contiguous()
-        return a.reshape(*self.batch, H), grad_w1, grad_b1, grad_w2, grad_b2, grad_x
+                _lib.ptr(self.knots), self.n_intervals, _lib.ptr(g.sgrid), g.n_sgrid, *_weight_args(weights), C, H, f32, tdt,
+                _lib.ptr(workspace), nbytes, stream), "cde_rk4_adjoint_mlp_prepare")
 
-    # adjoint=False: K2m that also stores every stage state, and K3m's sweep as reverse mode through the steps
-    def run_with_stages(self, z0):
-        lib = _lib.load()
-        g, f = self.grids, self.field
-        out = torch.empty(self.B, g.n_out, self.H, dtype=torch.float32, device=self.device)
-        n_steps = max(g.grid.numel() - 1, 0)
-        stage_index = torch.empty(max(4 * n_steps, 1), dtype=torch.int64, device=self.device)
-        stage_frac = torch.empty(max(4 * n_steps, 1), dtype=torch.float32, device=self.device)
-        stages = torch.empty(self.B, max(n_steps, 1), 4, 32, dtype=torch.float32, device=self.device)
-        z0c = z0.detach().reshape(self.B, self.H).contiguous()
-        w1, b1, w2, b2 = self._weights()
-        _lib.check(lib.cde_rk4_forward_mlp_stages(
-            _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w1), _lib.ptr(b1),
-            w1.size(0), _lib.ptr(w2), _lib.ptr(b2), f.act, _lib.ptr(z0c), _lib.ptr(g.grid), g.grid.numel(),
-            _lib.ptr(g.t_out), g.n_out, _lib.ptr(out), _lib.ptr(stages), self.B, self.C, self.H,
-            _lib.dtype_enum(torch.float32), _lib.dtype_enum(g.time_dtype), _lib.ptr(stage_index), _lib.ptr(stage_frac),
-            _lib.stream_ptr(self.device)), "cde_rk4_forward_mlp_stages")
-        return out.reshape(*self.batch, g.n_out, self.H), stages
+        def sweeps(chunk, rows):
+            for p in range(self.n_out - 1):
+                k, k_end = g.seg_off_host[p], g.seg_off_host[p + 1] - 1
+                while k < k_end:
+                    ke = min(k_end, k + chunk)
+                    _lib.check(lib.cde_rk4_adjoint_mlp_sweep(
+                        _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, self.act, _lib.ptr(y),
+                        _lib.ptr(a), _lib.ptr(g.sgrid), g.n_sgrid, k, ke, *rows, _lib.ptr(grad_x), B, C, H, f32, tdt,
+                        _lib.ptr(workspace), nbytes, stream), "cde_rk4_adjoint_mlp_sweep")
+                    yield ke - k
+                    k = ke
+                i_out = self.n_out - 1 - p
+                y.copy_(z_saved[:, i_out - 1])                 # torchdiffeq: re-seed z from the stored forward solution
+                a.add_(grad_out[:, i_out - 1])                 # and add the incoming gradient at that output time
+        longest = max((g.seg_off_host[p + 1] - 1 - g.seg_off_host[p] for p in range(self.n_out - 1)), default=0)
+        grads = self._sweep_and_reduce(weights[0].size(0), longest if g.n_sgrid > 1 else 0, sweeps)
+        return (a.reshape(*self.batch, H),) + grads + (grad_x,)
 
-    def run_backprop(self, stages, grad_out, weights, want_control=False):
+    def run_backprop(self, stages, grad_out, w1, b1, w2, b2, want_control=False):
         """Reverse mode through the 3/8-rule steps (the gradient `loss.backward()` through torchdiffeq's own operations
         gives, reference solver.py:144 with adjoint=False): the sweep walks the forward grid backwards in chunks of steps
         that end on the grid nodes an output gradient lands on (the transpose of torchdiffeq's linear output
         interpolation, `_Grids.backprop_lists`); each chunk's factor rows go through the same split-K reduction as the
         continuous adjoint's."""
         lib = _lib.load()
-        g, f = self.grids, self.field
+        g = self.grids
         B, H, C = self.B, self.H, self.C
         dev, f32 = self.device, _lib.dtype_enum(torch.float32)
-        w1, b1, w2, b2 = self._weights(weights)
-        width = w1.size(0)
+        weights = self._weights((w1, b1, w2, b2))
         _, _, _, _, n_steps = g.backprop_lists()
         nodes = g.backprop_nodes
         n_grid = n_steps + 1
@@ -584,11 +555,7 @@ class _MlpPlan:
         def land(m):                                                # output gradients that land on grid node m
             for j, wgt in nodes[m]:
                 gy.add_(go[:, j], alpha=wgt)
-        land(n_steps)
-        upper = _mlp_upper_half(H, C)     # 32 units x 16 channels: the sweep leaves the upper unit groups' dL/dY2 rows BEHIND
-        halves = 2 if upper else 1        # the lower groups' in G2 (rows n .. 2n - 1); each half is reduced into its own image
-        acc2 = torch.zeros(halves, 256, 132, dtype=torch.float32, device=dev)
-        acc1 = torch.zeros(128, 36, dtype=torch.float32, device=dev)
+        land(n_steps)                                               # (a single output time: node 0 is node n_steps)
         grad_x = torch.zeros_like(self.coeffs) if want_control else None     # accumulated by the sweep launches
         if n_steps > 0:
             stream = _lib.stream_ptr(dev)
@@ -596,19 +563,13 @@ class _MlpPlan:
             nbytes = lib.cde_rk4_adjoint_mlp_workspace_bytes(n_grid)
             workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             _lib.check(lib.cde_rk4_backprop_mlp_prepare(
-                _lib.ptr(self.knots), self.n_intervals, _lib.ptr(g.grid), n_grid, _lib.ptr(w1), _lib.ptr(b1), width,
-                _lib.ptr(w2), _lib.ptr(b2), C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream),
-                "cde_rk4_backprop_mlp_prepare")
-            row_bytes = (132 + 256 * halves + 128 + 36) * 4
-            chunk = max(1, min(n_steps, self.scratch_budget // (row_bytes * 4 * B)))
-            rows = chunk * 4 * B
-            U = torch.zeros(rows, 132, dtype=torch.float32, device=dev)
-            U[:, 128] = 1
-            Z = torch.zeros(rows, 36, dtype=torch.float32, device=dev)
-            Z[:, 32] = 1
-            G2 = torch.empty(halves * rows, 256, dtype=torch.float32, device=dev)
-            G1 = torch.empty(rows, 128, dtype=torch.float32, device=dev)
-            reduce_ws = torch.empty(lib.cde_mlp_grad_reduce_workspace_bytes(), dtype=torch.uint8, device=dev)
+                _lib.ptr(self.knots), self.n_intervals, _lib.ptr(g.grid), n_grid, *_weight_args(weights), C, H, f32, tdt,
+                _lib.ptr(workspace), nbytes, stream), "cde_rk4_backprop_mlp_prepare")
+
+        def sweeps(chunk, rows):
+            head = (_lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, self.act, _lib.ptr(stages),
+                    _lib.ptr(gy), _lib.ptr(g.grid), n_grid)
+            tail = (B, C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream)
             k_hi = n_steps
             while k_hi > 0:
                 k_lo = max(0, k_hi - chunk)
@@ -617,106 +578,18 @@ class _MlpPlan:
                         k_lo = m
                         break
                 if want_control:
-                    _lib.check(lib.cde_rk4_backprop_mlp_sweep_dcontrol(
-                        _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, f.act, _lib.ptr(stages),
-                        _lib.ptr(gy), _lib.ptr(g.grid), n_grid, k_lo, k_hi, _lib.ptr(U), _lib.ptr(G2), _lib.ptr(G1),
-                        _lib.ptr(Z), _lib.ptr(grad_x), B, C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream),
-                        "cde_rk4_backprop_mlp_sweep_dcontrol")
+                    _lib.check(lib.cde_rk4_backprop_mlp_sweep_dcontrol(*head, k_lo, k_hi, *rows, _lib.ptr(grad_x), *tail),
+                               "cde_rk4_backprop_mlp_sweep_dcontrol")
                 else:
-                    _lib.check(lib.cde_rk4_backprop_mlp_sweep(
-                        _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, f.act, _lib.ptr(stages),
-                        _lib.ptr(gy), _lib.ptr(g.grid), n_grid, k_lo, k_hi, _lib.ptr(U), _lib.ptr(G2), _lib.ptr(G1),
-                        _lib.ptr(Z), B, C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream), "cde_rk4_backprop_mlp_sweep")
-                n = 4 * (k_hi - k_lo) * B
-                for half in range(halves):
-                    _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G2[half * n:]), _lib.ptr(U), n, 2, _lib.ptr(acc2[half]),
-                                                       _lib.ptr(reduce_ws), reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
-                _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G1), _lib.ptr(Z), n, 1, _lib.ptr(acc1), _lib.ptr(reduce_ws),
-                                                   reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
+                    _lib.check(lib.cde_rk4_backprop_mlp_sweep(*head, k_lo, k_hi, *rows, *tail), "cde_rk4_backprop_mlp_sweep")
+                yield k_hi - k_lo
                 land(k_lo)
                 k_hi = k_lo
-        else:
-            pass                                                    # a single output time: node 0 is node n_steps, landed above
-        grad_w2, grad_b2 = _output_layer_gradients(acc2, H, C, width)
-        grad_w1 = acc1[:width, :H].contiguous()
-        grad_b1 = acc1[:width, 32].contiguous()
-        return gy.reshape(*self.batch, H), grad_w1, grad_b1, grad_w2, grad_b2, grad_x
+        grads = self._sweep_and_reduce(weights[0].size(0), n_steps, sweeps)
+        return (gy.reshape(*self.batch, H),) + grads + (grad_x,)
 
     def time_gradients(self, z_saved, grad_out, weights, grad_x, t, want_t=True, want_knots=False):
-        """Time gradients from what the sweep produced (as _plan_time_gradients for the one-layer fields):
-        dL/dt_i = f(t_i, z_i) . dL/dz_i for i >= 1, dL/dt_0 = int a^T F(z) d2X/dt2 dt - sum_i dL/dt_i; the integral is a
-        contraction of the control gradient with the cubic's (2c, 3d) rows and vanishes for a piecewise-linear control;
-        dL/d knot_j = - its part over interval j (cubic), or through the widths of a piecewise-linear control."""
-        B, H, C, f = self.B, self.H, self.C, self.field
-        co = self.coeffs
-        if self.degree == _lib.PATH_CUBIC:
-            per_interval = (co[..., 2 * C:3 * C] * grad_x[..., C:2 * C]
-                            + 2 * co[..., 3 * C:] * grad_x[..., 2 * C:3 * C]).sum(-1).sum(0)
-        else:
-            per_interval = torch.zeros(co.size(1) - 1, dtype=torch.float32, device=self.device)
-        integral = per_interval.sum()
-        grad_knots = None
-        if want_knots and self.degree == _lib.PATH_CUBIC:
-            grad_knots = torch.cat([-per_interval, per_interval.new_zeros(1)])
-        elif want_knots:
-            knots, values = self.knots.double(), co.double()
-            slopes = (values[:, 1:] - values[:, :-1]) / (knots[1:] - knots[:-1]).unsqueeze(-1)
-            dh = (grad_x.double().cumsum(1)[:, :-1] * slopes).sum((0, 2))            # dL/dh_j
-            zero = dh.new_zeros(1)
-            grad_knots = (torch.cat([zero, dh]) - torch.cat([dh, zero])).to(co.dtype)
-        if not want_t:
-            return None, grad_knots
-        w1, b1, w2, b2 = self._weights(weights)
-        zs = z_saved.detach().reshape(B, self.n_out, H)
-        go = grad_out.detach().reshape(B, self.n_out, H)
-        vals = [None] * self.n_out
-        total = torch.zeros((), dtype=torch.float32, device=self.device)
-        for i in range(1, self.n_out):
-            pre = torch.nn.functional.linear(torch.nn.functional.linear(zs[:, i], w1, b1).relu(), w2, b2)
-            if f.act == _lib.ACT_TANH:
-                pre = pre.tanh()
-            dX = self.path.derivative(self.grids.t_out[i]).reshape(B, C)
-            vals[i] = ((pre.view(B, H, C) * dX.unsqueeze(1)).sum(-1) * go[:, i]).sum()
-            total = total + vals[i]
-        vals[0] = integral - total
-        grad_t = torch.stack(vals).to(device=t.device, dtype=t.dtype) if self.n_out > 1 else torch.zeros_like(t)
-        return grad_t, grad_knots
-
-
-class _FusedMlpRK4(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, z0, w1, b1, w2, b2, plan, want_x, t, knots, *control):
-        out = plan.run(z0)
-        ctx.plan, ctx.want_x, ctx.t_like, ctx.has_knots = plan, want_x, t, knots is not None
-        ctx.save_for_backward(out, w1, b1, w2, b2)
-        return out
-
-    @staticmethod
-    @_once_differentiable
-    def backward(ctx, grad_out):
-        out, *weights = ctx.saved_tensors
-        plan = ctx.plan
-        need = ctx.needs_input_grad
-        want_t = ctx.t_like is not None and need[7]
-        want_knots = ctx.has_knots and need[8]
-        grad_z0, gw1, gb1, gw2, gb2, grad_x = plan.run_adjoint(out, grad_out, ctx.want_x, weights)
-        grad_t = grad_knots = None
-        if want_t or want_knots:
-            if grad_x is None and (plan.degree == _lib.PATH_CUBIC or want_knots):
-                # the time terms come out of the control-gradient sweep: run IN ADDITION, so that the other gradients are
-                # bitwise the same whether or not a time requires grad (the reference's "detach trick" invariance,
-                # test/test_tricks.py:111-131), as _FusedRK4 does
-                grad_x = plan.run_adjoint(out, grad_out, True, weights)[5]
-            grad_t, grad_knots = plan.time_gradients(out, grad_out, weights, grad_x, ctx.t_like, want_t, want_knots)
-            grad_knots = _with_fit_chain(plan, grad_knots, grad_x)
-        control_grads = ()
-        if ctx.want_x:
-            C = plan.C
-            gx = grad_x.reshape(*plan.batch, grad_x.size(-2), grad_x.size(-1))
-            pieces = (gx[..., C:2 * C], gx[..., 2 * C:3 * C], gx[..., 3 * C:]) if plan.degree == _lib.PATH_CUBIC else (gx,)
-            control_grads = tuple(g if n else None for g, n in zip(pieces, need[9:]))
-        return (grad_z0 if need[0] else None, gw1 if need[1] else None, gb1 if need[2] else None,
-                gw2 if need[3] else None, gb2 if need[4] else None, None, None, grad_t, grad_knots) + control_grads
+        return _time_gradients(self, z_saved, grad_out, self._weights(weights), grad_x, t, want_t, want_knots)
 
 
 def _mlp_upper_half(H, C):
@@ -739,54 +612,6 @@ def _mlp_fusable(field, H, C, z0, packed):
     return (z0.dtype == packed.dtype == w1.dtype == w2.dtype == torch.float32
             and ((H <= 32 and C <= 8) or (H <= 16 and C <= 16) or upper)
             and w1.size(0) <= 128 and tuple(w1.shape) == (w1.size(0), H) and tuple(w2.shape) == (H * C, w1.size(0)))
-
-
-class _FusedRK4(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, z0, weight, bias, plan, wants, t, knots, *control):
-        # `control`: the path's differentiable buffer views (cubic: b, 2c, 3d; linear: the knot values) when the
-        # gradient w.r.t. the coefficients was requested through adjoint_params -- only their gradient slots are used.
-        # `t` / `knots`: the output times / the path's knot times when THEIR gradient is wanted (else None).
-        out = plan.run_forward(z0, weight, bias)
-        ctx.plan, ctx.wants = plan, wants
-        ctx.has_t, ctx.has_knots = t is not None, knots is not None
-        ctx.save_for_backward(out, weight, bias, *((t,) if t is not None else ()))
-        return out.reshape(*plan.batch, plan.n_out, plan.H)
-
-    @staticmethod
-    @_once_differentiable
-    def backward(ctx, grad_out):
-        plan = ctx.plan
-        if not plan.adjoint:
-            raise NotImplementedError(
-                "torchcde_amd: backpropagating through the solver's internal operations (adjoint=False) is not "
-                "implemented on the native path; use adjoint=True (continuous adjoint, the reference's default).")
-        z_saved, weight, bias, *rest = ctx.saved_tensors
-        want_w, want_b, want_x = ctx.wants
-        want_t = ctx.has_t and ctx.needs_input_grad[5]
-        want_knots = ctx.has_knots and ctx.needs_input_grad[6]
-        times = want_t or want_knots
-        grad_z0, grad_w, grad_b, grad_x = plan.run_adjoint(z_saved, grad_out, weight, bias, want_x)
-        grad_t = grad_knots = None
-        if times:
-            if grad_x is None:
-                # The time terms come out of the control-gradient sweep.  It is run IN ADDITION to the sweep above, so
-                # that dL/dz0, dL/dW, dL/db are bitwise the same whether or not a time requires grad (the reference's
-                # "detach trick" invariance, test/test_tricks.py:111-131); requesting time gradients is rare.
-                grad_x = plan.run_adjoint(z_saved, grad_out, weight, bias, True)[3]
-            grad_t, grad_knots = plan.time_gradients(z_saved, grad_out, weight, bias, grad_x, rest[0] if ctx.has_t else None,
-                                                     want_t, want_knots)
-            grad_knots = _with_fit_chain(plan, grad_knots, grad_x)
-        control_grads = ()
-        if want_x:
-            C = plan.C
-            gx = grad_x.reshape(*plan.batch, grad_x.size(-2), grad_x.size(-1))
-            pieces = (gx[..., C:2 * C], gx[..., 2 * C:3 * C], gx[..., 3 * C:]) if plan.degree == _lib.PATH_CUBIC else (gx,)
-            control_grads = tuple(g if need else None for g, need in zip(pieces, ctx.needs_input_grad[7:]))
-        return (grad_z0.reshape(*plan.batch, plan.H) if ctx.needs_input_grad[0] else None,
-                grad_w.view_as(weight) if (ctx.needs_input_grad[1] and want_w) else None,
-                grad_b.view_as(bias) if (ctx.needs_input_grad[2] and want_b) else None,
-                None, None, grad_t, grad_knots) + control_grads
 
 
 def _reaches(tensor, leaf):
@@ -824,84 +649,156 @@ def _knot_fit_chain(X):
     return (buffers, tuple(X._control_buffers()), X._t) if buffers else None
 
 
+def _control_pieces(plan, grad_x):
+    """dL/d(packed coefficients), (B, rows, width), as gradients of the path's buffer views: b, 2c, 3d of a cubic (its `a`
+    rows are never read by the derivative), the knot values of a piecewise-linear control."""
+    C = plan.C
+    gx = grad_x.reshape(*plan.batch, grad_x.size(-2), grad_x.size(-1))
+    pieces = (gx[..., C:2 * C], gx[..., 2 * C:3 * C], gx[..., 3 * C:]) if plan.degree == _lib.PATH_CUBIC else (gx,)
+    return pieces
+
+
 def _with_fit_chain(plan, grad_knots, grad_x):
     """dL/d(knot times) plus the fit's chain (see _knot_fit_chain); `grad_x`: dL/d(packed coefficients) of the sweep."""
     chain = getattr(plan, "fit_chain", None)
     if chain is None or grad_knots is None or grad_x is None:
         return grad_knots
     reaching, buffers, knots = chain
-    C = plan.C
-    gx = grad_x.reshape(*plan.batch, grad_x.size(-2), grad_x.size(-1))
-    pieces = (gx[..., C:2 * C], gx[..., 2 * C:3 * C], gx[..., 3 * C:]) if plan.degree == _lib.PATH_CUBIC else (gx,)
-    pairs = [(b, g.to(b.dtype)) for b, g in zip(buffers, pieces) if any(b is r for r in reaching)]
+    pairs = [(b, g.to(b.dtype)) for b, g in zip(buffers, _control_pieces(plan, grad_x)) if any(b is r for r in reaching)]
     (extra,) = torch.autograd.grad([b for b, _ in pairs], [knots], [g.contiguous() for _, g in pairs], retain_graph=True,
                                    allow_unused=True)
     return grad_knots if extra is None else grad_knots + extra.to(device=grad_knots.device, dtype=grad_knots.dtype)
 
 
-def _control_gradients(plan, grad_x, want_x, want_knots, need, knot_gradient):
-    """(dL/d knot times, *dL/d the path's buffer views) of a reverse-mode sweep: the sweep leaves dL/d(packed coefficients)
-    in `grad_x`; the knot times follow from it by the chain rule of `frac = t - t_j` / of the widths (plan.time_gradients)."""
-    grad_knots = knot_gradient() if want_knots else None
-    if not want_x:
-        return (grad_knots,)
-    C = plan.C
-    gx = grad_x.reshape(*plan.batch, grad_x.size(-2), grad_x.size(-1))
-    pieces = (gx[..., C:2 * C], gx[..., 2 * C:3 * C], gx[..., 3 * C:]) if plan.degree == _lib.PATH_CUBIC else (gx,)
-    return (grad_knots,) + tuple(g if n else None for g, n in zip(pieces, need))
+# ------------------------------------------------------------------------------------------ autograd glue
+# Every fused Function takes (z0, *params, plan, wants, t, knots, *control): the field's parameters ((W, b), or the two-layer
+# field's (W1, b1, W2, b2)); `wants`: which parameter gradients adjoint_params asks for (None: all); `t` / `knots`: the
+# output times / the path's knot times when THEIR gradient is wanted (else None); `control`: the path's differentiable
+# buffer views (cubic: b, 2c, 3d; linear: the knot values) when the gradient w.r.t. the coefficients is wanted -- only
+# their gradient slots are used.  bench.py and the tests tell the protocols apart by the Functions' class names.
+def _keep(ctx, plan, wants, t, knots, control, *saved):
+    ctx.plan, ctx.wants, ctx.want_x, ctx.knots = plan, wants, len(control) > 0, knots
+    ctx.save_for_backward(*saved, t)
 
 
-class _FusedMlpRK4Backprop(torch.autograd.Function):
-    """cdeint(..., method='rk4', adjoint=False) for the examples' two-layer field: as _FusedRK4Backprop, on K2m / K3m."""
+def _gradients(ctx, grads, grad_t, grad_knots, grad_x):
+    """The backward result of a fused Function: the sweep's (dL/dz0, *parameter gradients) masked by needs_input_grad and
+    `wants`, dL/dt, dL/d knots plus the fit's chain (_with_fit_chain), dL/d the path's buffer views."""
+    plan, need, wants = ctx.plan, ctx.needs_input_grad, ctx.wants
+    grads = (grads[0].reshape(*plan.batch, plan.H),) + tuple(grads[1:])
+    grads = tuple(g if need[i] and (i == 0 or wants is None or wants[i - 1]) else None for i, g in enumerate(grads))
+    control = ()
+    if ctx.want_x:
+        control = tuple(g if n else None for g, n in zip(_control_pieces(plan, grad_x), need[len(grads) + 4:]))
+    return grads + (None, None, grad_t, _with_fit_chain(plan, grad_knots, grad_x)) + control
+
+
+@_once_differentiable
+def _adjoint_backward(ctx, grad_out):
+    """Fixed-grid solves: the continuous adjoint sweep, and the time gradients from the control-gradient sweep."""
+    plan, need = ctx.plan, ctx.needs_input_grad
+    z_saved, *weights, t = ctx.saved_tensors
+    n = 1 + len(weights)
+    want_t, want_knots = need[n + 2], need[n + 3]
+    *grads, grad_x = plan.run_adjoint(z_saved, grad_out, *weights, want_control=ctx.want_x)
+    grad_t = grad_knots = None
+    if want_t or want_knots:
+        # The time terms come out of the control-gradient sweep.  It is run IN ADDITION to the sweep above, so that dL/dz0
+        # and the parameter gradients are bitwise the same whether or not a time requires grad (the reference's "detach
+        # trick" invariance, test/test_tricks.py:111-131); requesting time gradients is rare.  (The two-layer field skips it
+        # where the time terms do not read it: dL/dt alone of a piecewise-linear control.)
+        if grad_x is None and (isinstance(plan, _Plan) or plan.degree == _lib.PATH_CUBIC or want_knots):
+            grad_x = plan.run_adjoint(z_saved, grad_out, *weights, want_control=True)[-1]
+        grad_t, grad_knots = plan.time_gradients(z_saved, grad_out, weights, grad_x, t, want_t, want_knots)
+    return _gradients(ctx, grads, grad_t, grad_knots, grad_x)
+
+
+@_once_differentiable
+def _backprop_backward(ctx, grad_out):
+    """adjoint=False: reverse mode through the stored stages; dL/d(packed coefficients) comes out of the same sweep, the
+    knot times follow from it by the chain rule of `frac = t - t_j` / of the widths (plan.time_gradients)."""
+    plan, need = ctx.plan, ctx.needs_input_grad
+    stages, *weights, _ = ctx.saved_tensors
+    want_knots = need[len(weights) + 4]
+    *grads, grad_x = plan.run_backprop(stages, grad_out, *weights, want_control=ctx.want_x or want_knots)
+    grad_knots = plan.time_gradients(None, None, weights, grad_x, None, False, True)[1] if want_knots else None
+    return _gradients(ctx, grads, None, grad_knots, grad_x)
+
+
+@_once_differentiable
+def _dopri5_backward(ctx, grad_out):
+    """The adaptive adjoint (K4a / K4am): dL/dt and the control gradients are blocks of its augmented state."""
+    plan, need = ctx.plan, ctx.needs_input_grad
+    z_saved, *weights, t = ctx.saved_tensors
+    n = 1 + len(weights)
+    want_t, want_knots = need[n + 2], need[n + 3]
+    res = plan.run_adjoint(z_saved, grad_out, *weights, want_t=want_t, want_control=ctx.want_x, want_knots=want_knots)
+    # on `t`'s own device: cdeint accepts a CPU `t` next to GPU data
+    grad_t = res[n].to(device=t.device, dtype=t.dtype) if want_t else None
+    grad_x = grad_knots = None
+    if ctx.want_x:
+        grad_x, grad_knots = res[-2], res[-1]
+        if grad_knots is not None:
+            grad_knots = grad_knots.to(device=ctx.knots.device, dtype=ctx.knots.dtype)
+    return _gradients(ctx, res[:n], grad_t, grad_knots, grad_x)
+
+
+class _FusedRK4(torch.autograd.Function):
+    """Fixed-grid solve (rk4, midpoint, euler) of the affine field: K2 forward, continuous-adjoint K3 backward."""
 
     @staticmethod
-    def forward(ctx, z0, w1, b1, w2, b2, plan, want_x, knots, *control):
-        # `control` / `knots`: the path's differentiable buffer views / its knot times when autograd must reach them (with
-        # adjoint=False it does so through X.derivative at every stage) -- only their gradient slots are used
-        out, stages = plan.run_with_stages(z0)
-        ctx.plan, ctx.want_x, ctx.has_knots = plan, want_x, knots is not None
-        ctx.save_for_backward(stages, w1, b1, w2, b2)
+    def forward(ctx, z0, weight, bias, plan, wants, t, knots, *control):
+        out = plan.run_forward(z0, weight, bias)
+        _keep(ctx, plan, wants, t, knots, control, out, weight, bias)
+        return out.reshape(*plan.batch, plan.n_out, plan.H)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.plan.adjoint:
+            raise NotImplementedError(
+                "torchcde_amd: backpropagating through the solver's internal operations (adjoint=False) is not "
+                "implemented on the native path; use adjoint=True (continuous adjoint, the reference's default).")
+        return _adjoint_backward(ctx, grad_out)
+
+
+class _FusedMlpRK4(torch.autograd.Function):
+    """The same for the two-layer field: K2m forward, K3m backward."""
+
+    @staticmethod
+    def forward(ctx, z0, w1, b1, w2, b2, plan, wants, t, knots, *control):
+        out = plan.run(z0)
+        _keep(ctx, plan, wants, t, knots, control, out, w1, b1, w2, b2)
         return out
 
-    @staticmethod
-    @_once_differentiable
-    def backward(ctx, grad_out):
-        stages, *weights = ctx.saved_tensors
-        plan, need = ctx.plan, ctx.needs_input_grad
-        want_knots = ctx.has_knots and need[7]
-        grad_z0, g1w, g1b, g2w, g2b, grad_x = plan.run_backprop(stages, grad_out, weights, ctx.want_x or want_knots)
-        return (grad_z0 if need[0] else None, g1w if need[1] else None, g1b if need[2] else None,
-                g2w if need[3] else None, g2b if need[4] else None, None, None) + _control_gradients(
-                    plan, grad_x, ctx.want_x, want_knots, need[8:], lambda: plan.time_gradients(
-                        None, None, weights, grad_x, None, False, True)[1])
+    backward = staticmethod(_adjoint_backward)
 
 
 class _FusedRK4Backprop(torch.autograd.Function):
     """cdeint(..., method='rk4', adjoint=False) for the affine field: torchdiffeq.odeint under autograd (reference
     solver.py:226-227 with adjoint=False) -- the forward kernel stores the state handed to every field evaluation, the
     backward is reverse-mode differentiation of the 3/8-rule steps themselves (csrc/rk4_backprop.hip), i.e. the gradient
-    of the discrete solve, as `loss.backward()` through torchdiffeq's own operations gives it."""
+    of the discrete solve, as `loss.backward()` through torchdiffeq's own operations gives it.  (`knots` / `control`: with
+    adjoint=False autograd reaches them through X.derivative at every stage.)"""
 
     @staticmethod
-    def forward(ctx, z0, weight, bias, plan, want_x, knots, *control):
-        # `control` / `knots`: as for _FusedMlpRK4Backprop
-        out, stages = plan.run_forward_stages(z0, weight, bias)
-        ctx.plan, ctx.want_x, ctx.has_knots = plan, want_x, knots is not None
-        ctx.save_for_backward(weight, bias, stages)
+    def forward(ctx, z0, weight, bias, plan, wants, t, knots, *control):
+        out, stages = plan.run_forward(z0, weight, bias, stages=True)
+        _keep(ctx, plan, wants, t, knots, control, stages, weight, bias)
         return out.reshape(*plan.batch, plan.n_out, plan.H)
 
+    backward = staticmethod(_backprop_backward)
+
+
+class _FusedMlpRK4Backprop(torch.autograd.Function):
+    """cdeint(..., method='rk4', adjoint=False) for the examples' two-layer field: as _FusedRK4Backprop, on K2m / K3m."""
+
     @staticmethod
-    @_once_differentiable
-    def backward(ctx, grad_out):
-        plan, need = ctx.plan, ctx.needs_input_grad
-        weight, bias, stages = ctx.saved_tensors
-        want_knots = ctx.has_knots and need[5]
-        grad_z0, grad_w, grad_b, grad_x = plan.run_backprop(stages, grad_out, weight, bias, ctx.want_x or want_knots)
-        return (grad_z0.reshape(*plan.batch, plan.H) if need[0] else None,
-                grad_w.view_as(weight) if need[1] else None,
-                grad_b if need[2] else None, None, None) + _control_gradients(
-                    plan, grad_x, ctx.want_x, want_knots, need[6:], lambda: plan.time_gradients(
-                        None, None, weight, bias, grad_x, None, False, True)[1])
+    def forward(ctx, z0, w1, b1, w2, b2, plan, wants, t, knots, *control):
+        out, stages = plan.run(z0, stages=True)
+        _keep(ctx, plan, wants, t, knots, control, stages, w1, b1, w2, b2)
+        return out
+
+    backward = staticmethod(_backprop_backward)
 
 
 # ------------------------------------------------------------------------------------------ dopri5 (K4)
@@ -913,6 +810,12 @@ last_dispatch = dispatch.last      # () -> (Choice(path, reason), Request) of th
 #   event_log                  bench.py: a list that receives the HIP events around the rk4 C-ABI calls
 _DOPRI_CHUNK = 48          # attempt kernels queued between two looks at the done flag
 _WORKSPACE_HEAD = 1 << 20  # bytes at the start of an adaptive workspace that hold the controller blocks and partial sums
+
+
+def _status(workspace, at):
+    """The controller status block at byte `at` of an adaptive workspace (one synchronising copy)."""
+    size = ctypes.sizeof(_lib.DopriStatus)
+    return _lib.DopriStatus.from_buffer_copy(workspace[at:at + size].cpu().numpy().tobytes())
 
 
 class _Dopri5Plan:
@@ -974,379 +877,52 @@ class _Dopri5Plan:
                 jb = torch.sort(_to_host(torch.as_tensor(jump_b)).to(torch.float64).reshape(-1)).values
                 self.jump_s, self.n_jump_s = (-jb).flip(0).contiguous().to(self.device), jb.numel()
 
-    def _run_shared(self, lib, shared, out, z0c, w, b, dt, workspace, w1=None, b1=None):
-        """One controller for all shards: per attempted step the pending error sums are all-reduced before the launch
-        that consumes them (torchcde_amd.distributed.shared_step_control)."""
-        reduce, global_batch = shared
-        sums = torch.zeros(2, dtype=torch.float64, device=self.device)
-        size = ctypes.sizeof(_lib.DopriStatus)
-        stream = _lib.stream_ptr(self.device)
-        launched = 0
-        while True:
-            for _ in range(_DOPRI_CHUNK):
-                if self.hidden is None:
-                    _lib.check(lib.cde_dopri5_pending_sums(_lib.ptr(workspace), workspace.numel(), self.B, self.C, self.H, dt,
-                                                           self.variant, self.act, launched, _lib.ptr(sums), stream),
-                               "cde_dopri5_pending_sums")
-                    reduce(sums)
-                    _lib.check(lib.cde_dopri5_advance_sharded(
-                        _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(b),
-                        self.act, _lib.ptr(z0c), _lib.ptr(self.t_out), self.n_out, _lib.ptr(self.jump_t), self.n_jump,
-                        self.rtol, self.atol, self.safety, self.ifactor, self.dfactor, _lib.ptr(out), self.B, self.C, self.H,
-                        dt, self.variant, _lib.ptr(workspace), workspace.numel(), launched, _lib.ptr(sums), global_batch,
-                        stream), "cde_dopri5_advance_sharded")
-                else:                                                  # the two-layer field (round 4)
-                    _lib.check(lib.cde_dopri5_pending_sums_mlp(_lib.ptr(workspace), workspace.numel(), self.B, self.C, self.H,
-                                                               dt, launched, _lib.ptr(sums), stream),
-                               "cde_dopri5_pending_sums_mlp")
-                    reduce(sums)
-                    _lib.check(lib.cde_dopri5_advance_mlp_sharded(
-                        _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w1), _lib.ptr(b1),
-                        w1.size(0), _lib.ptr(w), _lib.ptr(b), self.act, _lib.ptr(z0c), _lib.ptr(self.t_out), self.n_out,
-                        _lib.ptr(self.jump_t), self.n_jump, self.rtol, self.atol, self.safety, self.ifactor, self.dfactor,
-                        _lib.ptr(out), self.B, self.C, self.H, dt, _lib.ptr(workspace), workspace.numel(), launched,
-                        _lib.ptr(sums), global_batch, stream), "cde_dopri5_advance_mlp_sharded")
-                launched += 1
-            raw = workspace[(launched & 1) * size:(launched & 1) * size + size].cpu().numpy().tobytes()
-            status = _lib.DopriStatus.from_buffer_copy(raw)
-            if status.phase == 4:
-                break
-            if launched > 2_000_000:
-                raise RuntimeError("torchcde_amd: dopri5 did not reach t[-1] after %d attempted steps" % launched)
-        last_dopri5_stats = self.owner.dopri5            # (updated in place: callers may hold the dict itself)
-        last_dopri5_stats.clear()
-        last_dopri5_stats.update(n_accept=status.n_accept, n_reject=status.n_reject, launches=launched)
-        if self.record:
-            off = lib.cde_dopri5_trace_offset(self.B, self.C, self.H, dt)
-            n = min(status.n_accept, 4096)
-            last_dopri5_stats["steps"] = workspace[off:off + 24 * n].view(torch.float64).view(n, 3).cpu()
-        return out
-
-    def run_adjoint(self, z_saved, grad_out, weight, bias, want_t=False, want_control=False, want_knots=False):
-        """K4a: torchdiffeq's odeint_adjoint backward for the adaptive solve -- default mixed norm (or "seminorm"), dense
-        output at the interval ends -- one attempt kernel + one reduction kernel per attempted step
-        (csrc/dopri5_adjoint.hip), output intervals from the last to the first.
-        want_t: the output times require a gradient (torchdiffeq's time_vjps): dL/dt_i = f(t_i, z_i) . dL/dz_i for i >= 1
-        (one field evaluation per output time, here); vjp_t -- which K4a integrates and measures in its error norm anyway --
-        starts every interval at its carried value minus that term, and is dL/dt_0 after the last one.
-        want_control: adjoint_params names the coefficient tensor (self.control_numel elements): dL/dcoeffs, packed layout,
-        and (want_knots: the knot times are there too; else None) dL/d knots are appended to the result -- more blocks of
-        the mixed norm, accumulated on the device (cde_dopri5_adjoint_advance_dcontrol)."""
-        lib = _lib.load()
-        B, H, C, dev = self.B, self.H, self.C, self.device
-        z_saved = z_saved.detach().reshape(B, self.n_out, H)
-        grad_out = grad_out.detach().reshape(B, self.n_out, H).to(torch.float32)
-        w, b = weight.detach().contiguous(), bias.detach().contiguous()
-        n_w = H * C * H
-        flat = torch.zeros(n_w + H * C, dtype=torch.float32, device=dev)       # one buffer: a single all-reduce upstream
-        grad_w, grad_b = flat[:n_w].view(H * C, H), flat[n_w:]
-        a = grad_out[:, -1].contiguous()
-        grad_x = torch.zeros_like(self.coeffs) if want_control else None
-        grad_k = torch.zeros_like(self.knots) if (want_control and want_knots) else None
-        tail = (grad_x, grad_k) if want_control else ()
-        if self.n_out == 1:
-            return ((a, grad_w, grad_b, torch.zeros(1, dtype=torch.float32, device=dev)) if want_t else (a, grad_w, grad_b)) + tail
-        if want_control and self.shared is not None:
-            raise NotImplementedError("torchcde_amd: control gradients through the adaptive backward have no shared-controller form")
-        nbytes = (lib.cde_dopri5_adjoint_dcontrol_workspace_bytes if want_control else lib.cde_dopri5_adjoint_workspace_bytes)(B, C, H)
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        workspace[:_WORKSPACE_HEAD].zero_()     # controller blocks + partial sums: defined before the first launch reads them
-        size = ctypes.sizeof(_lib.DopriStatus)
-        stride = lib.cde_dopri5_adjoint_status_stride()
-        a_out = torch.empty(B, H, dtype=torch.float32, device=dev)
-        shared = self.shared
-        reduced = None
-        # "seminorm": the parameter blocks are not part of the decision -- only the 8 state sums travel between the shards
-        state_only = shared is not None and self.adj_norm_kind == 1
-        if shared is not None:
-            reduced = torch.zeros(8 if state_only else lib.cde_dopri5_adjoint_reduced_count(), dtype=torch.float64, device=dev)
-        stream = _lib.stream_ptr(dev)
-        stats = dict(n_accept=0, n_reject=0, launches=0)
-        steps, attempts = [], []
-        time_terms = [None] * self.n_out
-        carry = None
-        if want_t:
-            off = lib.cde_dopri5_adjoint_carry_offset(B, C, H)
-            workspace[off:off + 256].zero_()                          # the whole carry block (the kernel leaves it alone: bit 1)
-            carry = workspace[off:off + 8].view(torch.float64)        # vjp_t, carried across the intervals on the device
-        if want_t:
-            # torchdiffeq: func_eval = func(t[i], y[i]); dLd_cur_t = func_eval . grad_y[i]; aug_state[0] -= dLd_cur_t -- the
-            # field at ALL output times in one batched evaluation before the loop (ADVICE round 4)
-            pre = torch.nn.functional.linear(z_saved[:, 1:], w, b)                            # (B, T - 1, H * C)
-            if self.act == _lib.ACT_TANH:
-                pre = pre.tanh()
-            dX = self.path.derivative(self.t_out[1:]).reshape(B, self.n_out - 1, C)
-            f_all = (pre.view(B, self.n_out - 1, H, C) * dX.unsqueeze(2)).sum(-1)
-            terms = (f_all * grad_out[:, 1:]).sum((0, 2))
-            if shared is not None:
-                # one controller for all shards: vjp_t is a quantity of the WHOLE batch (it is in the error norm), so the
-                # terms it starts every interval from are summed over the shards; every rank returns the global dL/dt
-                terms64 = terms.to(torch.float64)
-                shared[0](terms64)
-                terms = terms64.to(torch.float32)
-            for i in range(1, self.n_out):
-                time_terms[i] = terms[i - 1]
-        for i in range(self.n_out - 1, 0, -1):
-            y = z_saved[:, i].contiguous()
-            s0, s1 = -float(self.t_host[i]), -float(self.t_host[i - 1])
-            if want_t:
-                carry.copy_((carry.to(torch.float32) - time_terms[i]).to(torch.float64))
-            launched = 0
-            while True:
-                def advance(first, count, sums_ptr, global_batch):
-                    head = (_lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w),
-                            _lib.ptr(b), self.act, _lib.ptr(y), _lib.ptr(a), s0, s1, _lib.ptr(self.jump_s), self.n_jump_s,
-                            self.adjoint_rtol, self.adjoint_atol, self.adj_safety, self.adj_ifactor, self.adj_dfactor,
-                            self.adj_norm_kind, _lib.ptr(a_out), B, C, H, _lib.dtype_enum(torch.float32),
-                            int(i == self.n_out - 1) | (2 if want_t else 0), _lib.ptr(workspace), workspace.numel(), first,
-                            count)
-                    if want_control:
-                        _lib.check(lib.cde_dopri5_adjoint_advance_dcontrol(*head, _lib.ptr(grad_x), int(self.control_numel),
-                                                                           _lib.ptr(grad_k), stream),
-                                   "cde_dopri5_adjoint_advance_dcontrol")
-                    else:
-                        _lib.check(lib.cde_dopri5_adjoint_advance(*head, sums_ptr, global_batch, stream),
-                                   "cde_dopri5_adjoint_advance")
-                if shared is None:
-                    advance(launched, _DOPRI_CHUNK, None, 0)
-                    launched += _DOPRI_CHUNK
-                else:
-                    # one controller for all shards: per attempted step the state sums AND the gradient images of the
-                    # attempt are all-reduced, then every shard commits / measures the parameter blocks on the same numbers
-                    for _ in range(_DOPRI_CHUNK):
-                        advance(launched, 1, _lib.ptr(reduced) if launched else None, shared[1])
-                        launched += 1
-                        if state_only:
-                            _lib.check(lib.cde_dopri5_adjoint_state_sums(_lib.ptr(workspace), workspace.numel(), B, C, H,
-                                                                         launched, _lib.ptr(reduced), stream),
-                                       "cde_dopri5_adjoint_state_sums")
-                            shared[0](reduced)
-                            _lib.check(lib.cde_dopri5_adjoint_apply_state_sums(_lib.ptr(workspace), workspace.numel(), B, C,
-                                                                               H, launched, _lib.ptr(reduced), stream),
-                                       "cde_dopri5_adjoint_apply_state_sums")
-                            continue
-                        _lib.check(lib.cde_dopri5_adjoint_pending_sums(_lib.ptr(workspace), workspace.numel(), B, C, H,
-                                                                       launched, _lib.ptr(reduced), stream),
-                                   "cde_dopri5_adjoint_pending_sums")
-                        shared[0](reduced)
-                        _lib.check(lib.cde_dopri5_adjoint_apply_reduced(
-                            _lib.ptr(workspace), workspace.numel(), B, C, H, self.adjoint_rtol, self.adjoint_atol, launched,
-                            _lib.ptr(reduced), stream), "cde_dopri5_adjoint_apply_reduced")
-                at = (launched & 1) * stride
-                raw = workspace[at:at + size].cpu().numpy().tobytes()
-                status = _lib.DopriStatus.from_buffer_copy(raw)
-                if status.phase == 4:
-                    break
-                if launched > 2_000_000:
-                    raise RuntimeError("torchcde_amd: the dopri5 adjoint did not reach t = %g after %d attempted steps"
-                                       % (-s1, launched))
-            stats["n_accept"] += status.n_accept
-            stats["n_reject"] += status.n_reject
-            stats["launches"] += launched
-            if self.record:
-                off = lib.cde_dopri5_adjoint_trace_offset(B, C, H)
-                n = min(status.n_accept, 4096)
-                steps.append(workspace[off:off + 24 * n].view(torch.float64).view(n, 3).cpu())
-                off = lib.cde_dopri5_adjoint_attempt_trace_offset(B, C, H)
-                n = min(status.n_accept + status.n_reject, 16384)
-                attempts.append(workspace[off:off + 40 * n].view(torch.float64).view(n, 5).cpu())
-            a = a_out + grad_out[:, i - 1]
-        _lib.check(lib.cde_dopri5_adjoint_finish(_lib.ptr(workspace), workspace.numel(), _lib.ptr(grad_w), _lib.ptr(grad_b),
-                                                 B, C, H, int(shared is not None and not state_only), stream),
-                   "cde_dopri5_adjoint_finish")
-        last_dopri5_adjoint_stats = self.owner.dopri5_adjoint
-        last_dopri5_adjoint_stats.clear()
-        last_dopri5_adjoint_stats.update(stats)
-        if self.record:
-            last_dopri5_adjoint_stats["steps"] = steps           # one (n, 3) tensor per output interval, last first
-            last_dopri5_adjoint_stats["attempts"] = attempts     # (t0, t1, on_jump, accepted, ratio) of EVERY attempt
-        if want_t:
-            time_terms[0] = carry.to(torch.float32).reshape(())       # time_vjps[0] = the carried vjp_t
-            return (a, grad_w, grad_b, torch.stack(time_terms)) + tail
-        return (a, grad_w, grad_b) + tail
-
-    def run_adjoint_mlp(self, z_saved, grad_out, w1, b1, w2, b2, want_t=False, want_control=False, want_knots=False):
-        """K4am: the same backward for the two-layer field (csrc/dopri5_mlp_adjoint.hip): per attempted step the attempt
-        kernel, the split-K reduction of its gradient factors and the commit / norm kernel, queued by one C-ABI call.
-        want_t: output-time gradients, as in run_adjoint."""
-        lib = _lib.load()
-        B, H, C, dev = self.B, self.H, self.C, self.device
-        z_saved = z_saved.detach().reshape(B, self.n_out, H)
-        grad_out = grad_out.detach().reshape(B, self.n_out, H).to(torch.float32)
-        w1, b1, w2, b2 = (p.detach().contiguous() for p in (w1, b1, w2, b2))
-        width = w1.size(0)
-        a = grad_out[:, -1].contiguous()
-        # control gradients (as run_adjoint): dL/dcoeffs (packed layout) and, when the knot times are in adjoint_params too,
-        # dL/d knots (else None) are appended to the result
-        grad_x = torch.zeros_like(self.coeffs) if want_control else None
-        grad_k = torch.zeros_like(self.knots) if (want_control and want_knots) else None
-        tail = (grad_x, grad_k) if want_control else ()
-        if self.n_out == 1:
-            zeros = (a, torch.zeros_like(w1), torch.zeros_like(b1), torch.zeros_like(w2), torch.zeros_like(b2))
-            return (zeros + (torch.zeros(1, dtype=torch.float32, device=dev),) if want_t else zeros) + tail
-        if want_control and self.shared is not None:
-            raise NotImplementedError("torchcde_amd: control gradients through the adaptive backward have no shared-controller form")
-        nbytes = (lib.cde_dopri5_adjoint_mlp_dcontrol_workspace_bytes if want_control else lib.cde_dopri5_adjoint_mlp_workspace_bytes)(B, C, H)
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        workspace[:_WORKSPACE_HEAD].zero_()
-        size = ctypes.sizeof(_lib.DopriStatus)
-        stride = lib.cde_dopri5_adjoint_status_stride()
-        a_out = torch.empty(B, H, dtype=torch.float32, device=dev)
-        stream = _lib.stream_ptr(dev)
-        shared = self.shared
-        reduced = None
-        state_only = shared is not None and self.adj_norm_kind == 1      # "seminorm": only the 8 state sums travel
-        if shared is not None:
-            reduced = torch.zeros(8 if state_only else lib.cde_dopri5_adjoint_mlp_reduced_count(), dtype=torch.float64,
-                                  device=dev)
-        stats = dict(n_accept=0, n_reject=0, launches=0)
-        steps, attempts = [], []
-        time_terms = [None] * self.n_out
-        carry = None
-        if want_t:
-            off = lib.cde_dopri5_adjoint_mlp_carry_offset(B, C, H)
-            workspace[off:off + 256].zero_()
-            carry = workspace[off:off + 8].view(torch.float64)
-        if want_t:                              # torchdiffeq: aug_state[0] -= func(t[i], y[i]) . grad_y[i], all output times at once
-            pre = torch.nn.functional.linear(torch.nn.functional.linear(z_saved[:, 1:], w1, b1).relu(), w2, b2)
-            if self.act == _lib.ACT_TANH:
-                pre = pre.tanh()
-            dX = self.path.derivative(self.t_out[1:]).reshape(B, self.n_out - 1, C)
-            terms = ((pre.view(B, self.n_out - 1, H, C) * dX.unsqueeze(2)).sum(-1) * grad_out[:, 1:]).sum((0, 2))
-            if shared is not None:                # (as in run_adjoint: the time terms of the whole batch)
-                terms64 = terms.to(torch.float64)
-                shared[0](terms64)
-                terms = terms64.to(torch.float32)
-            for i in range(1, self.n_out):
-                time_terms[i] = terms[i - 1]
-        for i in range(self.n_out - 1, 0, -1):
-            y = z_saved[:, i].contiguous()
-            s0, s1 = -float(self.t_host[i]), -float(self.t_host[i - 1])
-            if want_t:
-                carry.copy_((carry.to(torch.float32) - time_terms[i]).to(torch.float64))
-            launched = 0
-            while True:
-                if shared is None:
-                    head = (_lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w1), _lib.ptr(b1),
-                            width, _lib.ptr(w2), _lib.ptr(b2), self.act, _lib.ptr(y), _lib.ptr(a), s0, s1, _lib.ptr(self.jump_s),
-                            self.n_jump_s, self.adjoint_rtol, self.adjoint_atol, self.adj_safety, self.adj_ifactor,
-                            self.adj_dfactor, self.adj_norm_kind, _lib.ptr(a_out), B, C, H, _lib.dtype_enum(torch.float32),
-                            int(i == self.n_out - 1) | (2 if want_t else 0), _lib.ptr(workspace), workspace.numel(), launched,
-                            _DOPRI_CHUNK)
-                    if want_control:
-                        _lib.check(lib.cde_dopri5_adjoint_mlp_advance_dcontrol(*head, _lib.ptr(grad_x), int(self.control_numel),
-                                                                               _lib.ptr(grad_k), stream),
-                                   "cde_dopri5_adjoint_mlp_advance_dcontrol")
-                    else:
-                        _lib.check(lib.cde_dopri5_adjoint_mlp_advance(*head, stream), "cde_dopri5_adjoint_mlp_advance")
-                    launched += _DOPRI_CHUNK
-                else:
-                    # one controller for all shards (round 4): per attempted step ONE attempt launch, then this shard's
-                    # state sums + S / E gradient images are all-reduced and every shard commits / measures the
-                    # parameter blocks on the same (global) numbers
-                    for _ in range(_DOPRI_CHUNK):
-                        _lib.check(lib.cde_dopri5_adjoint_mlp_advance_sharded(
-                            _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w1),
-                            _lib.ptr(b1), width, _lib.ptr(w2), _lib.ptr(b2), self.act, _lib.ptr(y), _lib.ptr(a), s0, s1,
-                            _lib.ptr(self.jump_s), self.n_jump_s, self.adjoint_rtol, self.adjoint_atol, self.adj_safety,
-                            self.adj_ifactor, self.adj_dfactor, self.adj_norm_kind, _lib.ptr(a_out), B, C, H,
-                            _lib.dtype_enum(torch.float32), int(i == self.n_out - 1) | (2 if want_t else 0), _lib.ptr(workspace),
-                            workspace.numel(), launched, _lib.ptr(reduced) if launched else None, shared[1], stream),
-                            "cde_dopri5_adjoint_mlp_advance_sharded")
-                        launched += 1
-                        if state_only:
-                            _lib.check(lib.cde_dopri5_adjoint_mlp_state_sums(_lib.ptr(workspace), workspace.numel(), B, C, H,
-                                                                             launched, _lib.ptr(reduced), stream),
-                                       "cde_dopri5_adjoint_mlp_state_sums")
-                            shared[0](reduced)
-                            _lib.check(lib.cde_dopri5_adjoint_mlp_apply_state_sums(
-                                _lib.ptr(workspace), workspace.numel(), B, C, H, launched, _lib.ptr(reduced), stream),
-                                "cde_dopri5_adjoint_mlp_apply_state_sums")
-                            continue
-                        _lib.check(lib.cde_dopri5_adjoint_mlp_pending_sums(_lib.ptr(workspace), workspace.numel(), B, C, H,
-                                                                           launched, _lib.ptr(reduced), stream),
-                                   "cde_dopri5_adjoint_mlp_pending_sums")
-                        shared[0](reduced)
-                        _lib.check(lib.cde_dopri5_adjoint_mlp_apply_reduced(
-                            _lib.ptr(workspace), workspace.numel(), B, C, H, self.adjoint_rtol, self.adjoint_atol, launched,
-                            _lib.ptr(reduced), stream), "cde_dopri5_adjoint_mlp_apply_reduced")
-                at = (launched & 1) * stride
-                status = _lib.DopriStatus.from_buffer_copy(workspace[at:at + size].cpu().numpy().tobytes())
-                if status.phase == 4:
-                    break
-                if launched > 2_000_000:
-                    raise RuntimeError("torchcde_amd: the dopri5 adjoint did not reach t = %g after %d attempted steps"
-                                       % (-s1, launched))
-            stats["n_accept"] += status.n_accept
-            stats["n_reject"] += status.n_reject
-            stats["launches"] += launched
-            if self.record:
-                off = lib.cde_dopri5_adjoint_mlp_trace_offset(B, C, H, 0)
-                n = min(status.n_accept, 4096)
-                steps.append(workspace[off:off + 24 * n].view(torch.float64).view(n, 3).cpu())
-                off = lib.cde_dopri5_adjoint_mlp_trace_offset(B, C, H, 1)
-                n = min(status.n_accept + status.n_reject, 16384)
-                attempts.append(workspace[off:off + 40 * n].view(torch.float64).view(n, 5).cpu())
-            a = a_out + grad_out[:, i - 1]
-        off = lib.cde_dopri5_adjoint_mlp_gradient_offset(B, C, H)
-        totals = workspace[off:off + 4 * (256 * 129 + 128 * 33)].view(torch.float32)
-        acc2, acc1 = totals[:256 * 129].view(1, 256, 129), totals[256 * 129:].view(128, 33)
-        off = lib.cde_dopri5_adjoint_mlp_gradient_upper_offset(B, C, H)
-        if off:                                                  # 32 units x 16 channels: hidden units 16..31, a second image
-            acc2 = torch.cat([acc2, workspace[off:off + 4 * 256 * 129].view(torch.float32).view(1, 256, 129)])
-        grad_w2, grad_b2 = _output_layer_gradients(acc2, H, C, width)
-        grad_w1 = acc1[:width, :H].contiguous()
-        grad_b1 = acc1[:width, 32].contiguous()
-        last_dopri5_adjoint_stats = self.owner.dopri5_adjoint
-        last_dopri5_adjoint_stats.clear()
-        last_dopri5_adjoint_stats.update(stats)
-        if self.record:
-            last_dopri5_adjoint_stats["steps"] = steps
-            last_dopri5_adjoint_stats["attempts"] = attempts
-        if want_t:
-            time_terms[0] = carry.to(torch.float32).reshape(())
-            return (a, grad_w1, grad_b1, grad_w2, grad_b2, torch.stack(time_terms)) + tail
-        return (a, grad_w1, grad_b1, grad_w2, grad_b2) + tail
-
     def run(self, z0, weight, bias):
+        """K4: the adaptive forward, `weight` / `bias` of the layer that produces the (H, C) matrix (of a two-layer field
+        the second; the first is its `hidden` Linear).  _DOPRI_CHUNK attempts are queued between two looks at the status
+        block; under one controller for all shards (torchcde_amd.distributed.shared_step_control) each attempt's pending
+        error sums are all-reduced before the launch that consumes them."""
         lib = _lib.load()
         out = torch.empty(self.B, self.n_out, self.H, dtype=self.dtype, device=self.device)
         z0c = z0.detach().reshape(self.B, self.H).contiguous()
         if self.n_out == 1:
             out[:, 0] = z0c
             return out
-        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        mlp = self.hidden is not None
+        weights = ((self.hidden.weight, self.hidden.bias) if mlp else ()) + (weight, bias)
+        weights = tuple(p.detach().contiguous() for p in weights)
         dt = _lib.dtype_enum(self.dtype)
         nbytes = lib.cde_dopri5_workspace_bytes(self.B, self.C, self.H, dt)
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         workspace[:_WORKSPACE_HEAD].zero_()     # controller blocks + partial sums (a sharded run all-reduces them from launch 0)
-        size = ctypes.sizeof(_lib.DopriStatus)
-        launched = 0
-        if self.hidden is not None:
-            w1, b1 = self.hidden.weight.detach().contiguous(), self.hidden.bias.detach().contiguous()
+        variant = () if mlp else (self.variant,)
+        suffix = "_mlp" if mlp else ""
+        head = (_lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, *_weight_args(weights), self.act,
+                _lib.ptr(z0c), _lib.ptr(self.t_out), self.n_out, _lib.ptr(self.jump_t), self.n_jump, self.rtol, self.atol,
+                self.safety, self.ifactor, self.dfactor, _lib.ptr(out), self.B, self.C, self.H, dt, *variant,
+                _lib.ptr(workspace), workspace.numel())
+        stream = _lib.stream_ptr(self.device)
         shared = self.shared
-        if shared is not None:
-            if self.hidden is not None:
-                return self._run_shared(lib, shared, out, z0c, w, b, dt, workspace, w1, b1)
-            return self._run_shared(lib, shared, out, z0c, w, b, dt, workspace)
+        if shared is None:
+            advance = "cde_dopri5_advance" + suffix
+        else:
+            reduce, global_batch = shared
+            sums = torch.zeros(2, dtype=torch.float64, device=self.device)
+            pending = "cde_dopri5_pending_sums" + suffix
+            advance = "cde_dopri5_advance" + suffix + "_sharded"
+            pending_head = (_lib.ptr(workspace), workspace.numel(), self.B, self.C, self.H, dt, *variant) + (() if mlp else (self.act,))
+        launched = 0
         while True:
-            if self.hidden is None:
-                _lib.check(lib.cde_dopri5_advance(
-                    _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(b),
-                    self.act, _lib.ptr(z0c), _lib.ptr(self.t_out), self.n_out, _lib.ptr(self.jump_t), self.n_jump,
-                    self.rtol, self.atol, self.safety, self.ifactor, self.dfactor, _lib.ptr(out), self.B, self.C, self.H,
-                    dt, self.variant, _lib.ptr(workspace), workspace.numel(), launched, _DOPRI_CHUNK,
-                    _lib.stream_ptr(self.device)), "cde_dopri5_advance")
+            if shared is None:
+                _lib.check(getattr(lib, advance)(*head, launched, _DOPRI_CHUNK, stream), advance)
+                launched += _DOPRI_CHUNK
             else:
-                _lib.check(lib.cde_dopri5_advance_mlp(
-                    _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w1), _lib.ptr(b1),
-                    w1.size(0), _lib.ptr(w), _lib.ptr(b), self.act, _lib.ptr(z0c), _lib.ptr(self.t_out), self.n_out,
-                    _lib.ptr(self.jump_t), self.n_jump, self.rtol, self.atol, self.safety, self.ifactor, self.dfactor,
-                    _lib.ptr(out), self.B, self.C, self.H, dt, _lib.ptr(workspace), workspace.numel(), launched,
-                    _DOPRI_CHUNK, _lib.stream_ptr(self.device)), "cde_dopri5_advance_mlp")
-            launched += _DOPRI_CHUNK
-            raw = workspace[(launched & 1) * size:(launched & 1) * size + size].cpu().numpy().tobytes()   # one sync per chunk
-            status = _lib.DopriStatus.from_buffer_copy(raw)
+                for _ in range(_DOPRI_CHUNK):
+                    _lib.check(getattr(lib, pending)(*pending_head, launched, _lib.ptr(sums), stream), pending)
+                    reduce(sums)
+                    _lib.check(getattr(lib, advance)(*head, launched, _lib.ptr(sums), global_batch, stream), advance)
+                    launched += 1
+            status = _status(workspace, (launched & 1) * ctypes.sizeof(_lib.DopriStatus))   # one sync per chunk
             if status.phase == 4:
                 break
             if launched > 2_000_000:
@@ -1361,46 +937,170 @@ class _Dopri5Plan:
             last_dopri5_stats["steps"] = workspace[off:off + 24 * n].view(torch.float64).view(n, 3).cpu()
         return out
 
+    def run_adjoint(self, z_saved, grad_out, *weights, want_t=False, want_control=False, want_knots=False):
+        """torchdiffeq's odeint_adjoint backward for the adaptive solve -- default mixed norm (or "seminorm"), dense output at
+        the interval ends -- output intervals from the last to the first.  `weights`: W, b of the affine field (K4a,
+        csrc/dopri5_adjoint.hip: one attempt kernel + one reduction kernel per attempted step) or W1, b1, W2, b2 of the
+        two-layer one (K4am, csrc/dopri5_mlp_adjoint.hip: per attempted step the attempt kernel, the split-K reduction of
+        its gradient factors and the commit / norm kernel, queued by one C-ABI call).  Returns (dL/dz0, *parameter
+        gradients[, dL/dt][, dL/dcoeffs, dL/d knots]).
+        want_t: the output times require a gradient (torchdiffeq's time_vjps): dL/dt_i = f(t_i, z_i) . dL/dz_i for i >= 1
+        (one batched field evaluation, here); vjp_t -- which the kernels integrate and measure in their error norm anyway --
+        starts every interval at its carried value minus that term, and is dL/dt_0 after the last one.
+        want_control: adjoint_params names the coefficient tensor (self.control_numel elements): dL/dcoeffs, packed layout,
+        and (want_knots: the knot times are there too; else None) dL/d knots are appended to the result -- more blocks of
+        the mixed norm, accumulated on the device (cde_dopri5_adjoint[_mlp]_advance_dcontrol)."""
+        lib = _lib.load()
+        B, H, C, dev = self.B, self.H, self.C, self.device
+        mlp = len(weights) == 4
+        prefix = "cde_dopri5_adjoint_mlp_" if mlp else "cde_dopri5_adjoint_"
+        z_saved = z_saved.detach().reshape(B, self.n_out, H)
+        grad_out = grad_out.detach().reshape(B, self.n_out, H).to(torch.float32)
+        weights = tuple(p.detach().contiguous() for p in weights)
+        if not mlp:
+            n_w = H * C * H
+            flat = torch.zeros(n_w + H * C, dtype=torch.float32, device=dev)       # one buffer: a single all-reduce upstream
+            grads = (flat[:n_w].view(H * C, H), flat[n_w:])
+        a = grad_out[:, -1].contiguous()
+        grad_x = torch.zeros_like(self.coeffs) if want_control else None
+        grad_k = torch.zeros_like(self.knots) if (want_control and want_knots) else None
+        tail = (grad_x, grad_k) if want_control else ()
+        if self.n_out == 1:
+            zeros = tuple(torch.zeros_like(p) for p in weights) if mlp else grads
+            return (a,) + zeros + ((torch.zeros(1, dtype=torch.float32, device=dev),) if want_t else ()) + tail
+        if want_control and self.shared is not None:
+            raise NotImplementedError("torchcde_amd: control gradients through the adaptive backward have no shared-controller form")
+        nbytes = getattr(lib, prefix + ("dcontrol_workspace_bytes" if want_control else "workspace_bytes"))(B, C, H)
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        workspace[:_WORKSPACE_HEAD].zero_()     # controller blocks + partial sums: defined before the first launch reads them
+        stride = lib.cde_dopri5_adjoint_status_stride()
+        a_out = torch.empty(B, H, dtype=torch.float32, device=dev)
+        shared = self.shared
+        reduced = None
+        # "seminorm": the parameter blocks are not part of the decision -- only the 8 state sums travel between the shards
+        state_only = shared is not None and self.adj_norm_kind == 1
+        if shared is not None:
+            reduced = torch.zeros(8 if state_only else getattr(lib, prefix + "reduced_count")(), dtype=torch.float64,
+                                  device=dev)
+        stream = _lib.stream_ptr(dev)
+        stats = dict(n_accept=0, n_reject=0, launches=0)
+        steps, attempts = [], []
+        time_terms = [None] * self.n_out
+        carry = None
+        if want_t:
+            off = getattr(lib, prefix + "carry_offset")(B, C, H)
+            workspace[off:off + 256].zero_()                          # the whole carry block (the kernel leaves it alone: bit 1)
+            carry = workspace[off:off + 8].view(torch.float64)        # vjp_t, carried across the intervals on the device
+            # torchdiffeq: func_eval = func(t[i], y[i]); dLd_cur_t = func_eval . grad_y[i]; aug_state[0] -= dLd_cur_t -- the
+            # field at ALL output times in one batched evaluation before the loop (ADVICE round 4)
+            pre = _field_values(self.act, weights, z_saved[:, 1:])                          # (B, T - 1, H * C)
+            dX = self.path.derivative(self.t_out[1:]).reshape(B, self.n_out - 1, C)
+            terms = ((pre.view(B, self.n_out - 1, H, C) * dX.unsqueeze(2)).sum(-1) * grad_out[:, 1:]).sum((0, 2))
+            if shared is not None:
+                # one controller for all shards: vjp_t is a quantity of the WHOLE batch (it is in the error norm), so the
+                # terms it starts every interval from are summed over the shards; every rank returns the global dL/dt
+                terms64 = terms.to(torch.float64)
+                shared[0](terms64)
+                terms = terms64.to(torch.float32)
+            for i in range(1, self.n_out):
+                time_terms[i] = terms[i - 1]
+        # the entry points: one attempt-chunk launch per look at the status block; under one controller for all shards
+        # one attempt per launch, after which this shard's state sums (and, mixed norm, the S / E gradient images of the
+        # attempt) are all-reduced and every shard commits / measures the parameter blocks on the same (global) numbers
+        if shared is None:
+            advance = prefix + ("advance_dcontrol" if want_control else "advance")
+            extra = ((_lib.ptr(grad_x), int(self.control_numel), _lib.ptr(grad_k)) if want_control else
+                     () if mlp else (None, 0))
+        else:
+            advance = prefix + ("advance_sharded" if mlp else "advance")        # (the affine entry point takes the sums)
+            count = () if mlp else (1,)
+            gather, apply = ("state_sums", "apply_state_sums") if state_only else ("pending_sums", "apply_reduced")
+            gather, apply = prefix + gather, prefix + apply
+            tolerances = () if state_only else (self.adjoint_rtol, self.adjoint_atol)
+            ws_head = (_lib.ptr(workspace), workspace.numel(), B, C, H)
+        if mlp:
+            trace_offset = lambda which: lib.cde_dopri5_adjoint_mlp_trace_offset(B, C, H, which)         # noqa: E731
+        else:
+            trace_offset = lambda which: (lib.cde_dopri5_adjoint_trace_offset,                            # noqa: E731
+                                          lib.cde_dopri5_adjoint_attempt_trace_offset)[which](B, C, H)
+        w_args = _weight_args(weights)
+        for i in range(self.n_out - 1, 0, -1):
+            y = z_saved[:, i].contiguous()
+            s0, s1 = -float(self.t_host[i]), -float(self.t_host[i - 1])
+            if want_t:
+                carry.copy_((carry.to(torch.float32) - time_terms[i]).to(torch.float64))
+            head = (_lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, *w_args, self.act, _lib.ptr(y),
+                    _lib.ptr(a), s0, s1, _lib.ptr(self.jump_s), self.n_jump_s, self.adjoint_rtol, self.adjoint_atol,
+                    self.adj_safety, self.adj_ifactor, self.adj_dfactor, self.adj_norm_kind, _lib.ptr(a_out), B, C, H,
+                    _lib.dtype_enum(torch.float32), int(i == self.n_out - 1) | (2 if want_t else 0), _lib.ptr(workspace),
+                    workspace.numel())
+            launched = 0
+            while True:
+                if shared is None:
+                    _lib.check(getattr(lib, advance)(*head, launched, _DOPRI_CHUNK, *extra, stream), advance)
+                    launched += _DOPRI_CHUNK
+                else:
+                    for _ in range(_DOPRI_CHUNK):
+                        _lib.check(getattr(lib, advance)(*head, launched, *count, _lib.ptr(reduced) if launched else None,
+                                                         shared[1], stream), advance)
+                        launched += 1
+                        _lib.check(getattr(lib, gather)(*ws_head, launched, _lib.ptr(reduced), stream), gather)
+                        shared[0](reduced)
+                        _lib.check(getattr(lib, apply)(*ws_head, *tolerances, launched, _lib.ptr(reduced), stream), apply)
+                status = _status(workspace, (launched & 1) * stride)
+                if status.phase == 4:
+                    break
+                if launched > 2_000_000:
+                    raise RuntimeError("torchcde_amd: the dopri5 adjoint did not reach t = %g after %d attempted steps"
+                                       % (-s1, launched))
+            stats["n_accept"] += status.n_accept
+            stats["n_reject"] += status.n_reject
+            stats["launches"] += launched
+            if self.record:
+                off = trace_offset(0)
+                n = min(status.n_accept, 4096)
+                steps.append(workspace[off:off + 24 * n].view(torch.float64).view(n, 3).cpu())
+                off = trace_offset(1)
+                n = min(status.n_accept + status.n_reject, 16384)
+                attempts.append(workspace[off:off + 40 * n].view(torch.float64).view(n, 5).cpu())
+            a = a_out + grad_out[:, i - 1]
+        if mlp:
+            off = lib.cde_dopri5_adjoint_mlp_gradient_offset(B, C, H)
+            totals = workspace[off:off + 4 * (256 * 129 + 128 * 33)].view(torch.float32)
+            acc2, acc1 = totals[:256 * 129].view(1, 256, 129), totals[256 * 129:].view(128, 33)
+            off = lib.cde_dopri5_adjoint_mlp_gradient_upper_offset(B, C, H)
+            if off:                                                  # 32 units x 16 channels: hidden units 16..31, a second image
+                acc2 = torch.cat([acc2, workspace[off:off + 4 * 256 * 129].view(torch.float32).view(1, 256, 129)])
+            grads = _mlp_gradients(acc1, acc2, H, C, weights[0].size(0))
+        else:
+            _lib.check(lib.cde_dopri5_adjoint_finish(_lib.ptr(workspace), workspace.numel(), _lib.ptr(grads[0]),
+                                                     _lib.ptr(grads[1]), B, C, H, int(shared is not None and not state_only),
+                                                     stream), "cde_dopri5_adjoint_finish")
+        last_dopri5_adjoint_stats = self.owner.dopri5_adjoint
+        last_dopri5_adjoint_stats.clear()
+        last_dopri5_adjoint_stats.update(stats)
+        if self.record:
+            last_dopri5_adjoint_stats["steps"] = steps           # one (n, 3) tensor per output interval, last first
+            last_dopri5_adjoint_stats["attempts"] = attempts     # (t0, t1, on_jump, accepted, ratio) of EVERY attempt
+        if want_t:
+            time_terms[0] = carry.to(torch.float32).reshape(())       # time_vjps[0] = the carried vjp_t
+            return (a,) + grads + (torch.stack(time_terms),) + tail
+        return (a,) + grads + tail
+
+    run_adjoint_mlp = run_adjoint     # (the two-layer field's weights W1, b1, W2, b2: the same driver)
+
 
 class _FusedDopri5(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, z0, weight, bias, plan, wants, t=None, knots=None, *control):
-        # `control`: the path's buffers the control derivative reads, present (and differentiable inputs) only when the
-        # coefficient tensor is among adjoint_params -- K4a then integrates dL/dcoeffs as one more block of the adjoint state
-        # (`knots`: the path's knot times when they are in adjoint_params too: a fourth block)
-        out = plan.run(z0, weight, bias)
-        ctx.plan, ctx.wants = plan, wants
-        ctx.t_like = t
-        ctx.want_x = len(control) > 0
-        ctx.want_knots = knots is not None
-        ctx.knots_like = knots
-        ctx.save_for_backward(out, weight, bias)
-        return out.reshape(*plan.batch, plan.n_out, plan.H)
+    """dopri5 forward (K4) and torchdiffeq's adaptive adjoint backward (K4a) of the affine field.  (`control` / `knots`:
+    K4a then integrates dL/dcoeffs -- and dL/d knots -- as more blocks of the adjoint state.)"""
 
     @staticmethod
-    @_once_differentiable
-    def backward(ctx, grad_out):
-        plan = ctx.plan
-        out, weight, bias = ctx.saved_tensors
-        want_t = ctx.t_like is not None and ctx.needs_input_grad[5]
-        want_knots = ctx.want_knots and ctx.needs_input_grad[6]
-        res = plan.run_adjoint(out, grad_out, weight, bias, want_t=want_t, want_control=ctx.want_x, want_knots=want_knots)
-        grad_z0, grad_w, grad_b = res[:3]
-        grad_t = None
-        if want_t:                                # on `t`'s own device: cdeint accepts a CPU `t` next to GPU data
-            grad_t = res[3].to(device=ctx.t_like.device, dtype=ctx.t_like.dtype)
-        want_w, want_b = ctx.wants
-        control_grads, grad_knots = (), None
-        if ctx.want_x:
-            grad_x, grad_knots = res[-2], res[-1]
-            if grad_knots is not None:
-                grad_knots = grad_knots.to(device=ctx.knots_like.device, dtype=ctx.knots_like.dtype)
-                grad_knots = _with_fit_chain(plan, grad_knots, grad_x)
-            control_grads = _control_gradients(plan, grad_x, True, False, ctx.needs_input_grad[7:], None)[1:]
-        return (grad_z0.reshape(*plan.batch, plan.H) if ctx.needs_input_grad[0] else None,
-                grad_w.view_as(weight) if (ctx.needs_input_grad[1] and want_w) else None,
-                grad_b.view_as(bias) if (ctx.needs_input_grad[2] and want_b) else None, None, None, grad_t,
-                grad_knots) + control_grads
+    def forward(ctx, z0, weight, bias, plan, wants, t, knots, *control):
+        out = plan.run(z0, weight, bias)
+        _keep(ctx, plan, wants, t, knots, control, out, weight, bias)
+        return out.reshape(*plan.batch, plan.n_out, plan.H)
+
+    backward = staticmethod(_dopri5_backward)
 
 
 class _FusedMlpDopri5(torch.autograd.Function):
@@ -1408,38 +1108,12 @@ class _FusedMlpDopri5(torch.autograd.Function):
     (K4 with the two-layer field) and torchdiffeq's adaptive adjoint backward (K4am)."""
 
     @staticmethod
-    def forward(ctx, z0, w1, b1, w2, b2, plan, t=None, knots=None, *control):
-        # (`control` / `knots`: as in _FusedDopri5 -- the path's buffers / knot times when adjoint_params names them)
+    def forward(ctx, z0, w1, b1, w2, b2, plan, wants, t, knots, *control):
         out = plan.run(z0, w2, b2)
-        ctx.plan = plan
-        ctx.t_like = t
-        ctx.want_x = len(control) > 0
-        ctx.knots_like = knots
-        ctx.save_for_backward(out, w1, b1, w2, b2)
+        _keep(ctx, plan, wants, t, knots, control, out, w1, b1, w2, b2)
         return out.reshape(*plan.batch, plan.n_out, plan.H)
 
-    @staticmethod
-    @_once_differentiable
-    def backward(ctx, grad_out):
-        out, w1, b1, w2, b2 = ctx.saved_tensors
-        plan = ctx.plan
-        need = ctx.needs_input_grad
-        want_t = ctx.t_like is not None and need[6]
-        want_knots = ctx.knots_like is not None and need[7]
-        res = plan.run_adjoint_mlp(out, grad_out, w1, b1, w2, b2, want_t=want_t, want_control=ctx.want_x,
-                                   want_knots=want_knots)
-        grad_z0, gw1, gb1, gw2, gb2 = res[:5]
-        grad_t = res[5].to(device=ctx.t_like.device, dtype=ctx.t_like.dtype) if want_t else None
-        control_grads, grad_knots = (), None
-        if ctx.want_x:
-            grad_x, grad_knots = res[-2], res[-1]
-            if grad_knots is not None:
-                grad_knots = grad_knots.to(device=ctx.knots_like.device, dtype=ctx.knots_like.dtype)
-                grad_knots = _with_fit_chain(plan, grad_knots, grad_x)
-            control_grads = _control_gradients(plan, grad_x, True, False, need[8:], None)[1:]
-        return (grad_z0.reshape(*plan.batch, plan.H) if need[0] else None, gw1 if need[1] else None,
-                gb1 if need[2] else None, gw2 if need[3] else None, gb2 if need[4] else None, None, grad_t,
-                grad_knots) + control_grads
+    backward = staticmethod(_dopri5_backward)
 
 
 # ------------------------------------------------------------------------------------------ front end
@@ -1790,7 +1464,7 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
         control_inputs = X._control_buffers() if want_x else ()
         plan.fit_chain = _knot_fit_chain(X) if want_knots else None
         return _FusedMlpRK4.apply(z0, mlp.hidden.weight, mlp.hidden.bias, mlp.output.weight, mlp.output.bias, plan,
-                                  want_x, t if wants_t else None, X._t if want_knots else None, *control_inputs)
+                                  None, t if wants_t else None, X._t if want_knots else None, *control_inputs)
     if choice.path in ("rk4_backprop", "mlp_rk4_backprop"):
         # adjoint=False: the control tensors autograd must reach (their gradients come out of the same reverse-mode sweep)
         want_x = bool(grad_mode and any(b.requires_grad for b in X._control_buffers()))
@@ -1799,7 +1473,7 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
     if choice.path == "mlp_rk4_backprop":
         plan = _MlpPlan(X, mlp, batch, H, C, t, _parse_fixed_options(fused_options, "solver"))
         return _FusedMlpRK4Backprop.apply(z0, mlp.hidden.weight, mlp.hidden.bias, mlp.output.weight, mlp.output.bias, plan,
-                                          want_x, knots_in, *control_inputs)
+                                          None, None, knots_in, *control_inputs)
     if choice.path == "mlp_rk4_forward":
         with torch.no_grad():
             return _MlpPlan(X, mlp, batch, H, C, t, _parse_fixed_options(fused_options, "solver")).run(z0)
@@ -1816,13 +1490,13 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
         knots_in = X._t if (want_x and any(p is X._t and p.requires_grad for p in given_params)) else None
         plan.fit_chain = _knot_fit_chain(X) if knots_in is not None else None
         return _FusedMlpDopri5.apply(z0, mlp.hidden.weight, mlp.hidden.bias, mlp.output.weight, mlp.output.bias, plan,
-                                     t if wants_t else None, knots_in, *control_inputs)
+                                     None, t if wants_t else None, knots_in, *control_inputs)
 
     # ---- one-layer fields
     weight, bias = field.weight, field.bias
     if choice.path == "rk4_backprop":
         plan = _Plan(X, field, batch, H, C, t, _parse_fixed_options(fused_options, "solver"), None, False, variant)
-        return _FusedRK4Backprop.apply(z0, weight, bias, plan, want_x, knots_in, *control_inputs)
+        return _FusedRK4Backprop.apply(z0, weight, bias, plan, None, None, knots_in, *control_inputs)
     if choice.path in ("dopri5_forward", "dopri5_adjoint"):
         plan = _Dopri5Plan(X, field, batch, H, C, t, kwargs["rtol"], kwargs["atol"], fused_options, variant,
                            kwargs.get("adjoint_rtol"), kwargs.get("adjoint_atol"), fused_adj_opts)
@@ -1862,7 +1536,7 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
                  _lib.FIXED_METHODS[method] if choice.path == "fixed_grid" else _lib.METHOD_RK4)
     control_inputs = X._control_buffers() if want_x else ()
     plan.fit_chain = _knot_fit_chain(X) if want_knots else None
-    return _FusedRK4.apply(z0, weight, bias, plan, (want_w, want_b, want_x), t if wants_t else None,
+    return _FusedRK4.apply(z0, weight, bias, plan, (want_w, want_b), t if wants_t else None,
                            X._t if want_knots else None, *control_inputs)
 
 
