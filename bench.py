@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- series/sec (fwd+adjoint) for cdeint RK4, batch=32768, L=128, C=8, H=32 (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--cpu-sample S]]
     python bench.py --config 4 [--controller local|shared] [--adjoint] [--gpus N]     BASELINE configs[3] (see run_adaptive_config)
     python bench.py --config 5 [--method dopri5|rk4] [--controller local|shared] [--gpus N]   BASELINE configs[4] (see run_logode_config)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -12,7 +12,14 @@ One "step" = one pass of the hot path over one batch of synthetic series already
 by ``z_T.sum().backward()`` (K3: continuous-adjoint reverse sweep, gradients for z0, W, b).  This is
 BASELINE.json configs[2] ("same as [1] with adjoint=True backprop through solver, 1 MI355X"), the
 configuration the metric is quoted on.  Coefficients are fitted once outside the timed region (K1; the
-reference treats it as dataset pre-processing) and its rate is reported separately under "extra".
+reference treats it as dataset pre-processing).
+
+A plain run does only what the headline figure needs: set up, warm up, time the steps, dump (if asked) and print the result
+line, whose `roofline` and `extra` figures come from HIP events recorded inside the timed steps.  ``--full`` also measures,
+after the timed steps, everything else: K1's and K0's own rates, the 1-GPU strong-scaling proxy, the bf16x3 and
+adjoint=False variants, the other vector fields and configurations, and the CPU baseline (their keys under "extra" and
+"cpu_baseline", see `full_measurements`).  The headline figure and what --dump-outputs writes do not depend on it.
+``--config 4`` / ``--config 5`` measure nothing besides their own steps, with or without --full.
 
 Multi-GPU: series are independent, so the batch shards across ranks with NO data-path collective; the only
 communication is the all-reduce of the 8,448 parameter gradients, included in the timed step when N > 1.
@@ -169,6 +176,52 @@ def dump_outputs(directory, batched, shared, distributed, world, rank):
         np.save(os.path.join(directory, name + ".npy"), a)
     _log("dumped %d arrays (%.1f MB) to %s" % (len(arrays), total / 2**20, directory))
     return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def fit_and_fill_ms(cde, x, device):
+    """K1 (the Hermite fit of the headline workload) and K0 (missing-value fill on the survey's irregular workload: 10 % of
+    the entries missing): ms per call from HIP events, 10 and 5 calls after warm-ups."""
+    torch.cuda.synchronize()
+    for _ in range(2):
+        cde.hermite_cubic_coefficients_with_backward_differences(x)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    for _ in range(10):
+        cde.hermite_cubic_coefficients_with_backward_differences(x)
+    ev[1].record()
+    torch.cuda.synchronize()
+    fit_ms = ev[0].elapsed_time(ev[1]) / 10
+    x_nan = x.masked_fill(torch.rand(x.shape, device=device) < 0.1, float("nan"))
+    cde.linear_interpolation_coeffs(x_nan)
+    ev[0].record()
+    for _ in range(5):
+        cde.linear_interpolation_coeffs(x_nan)
+    ev[1].record()
+    torch.cuda.synchronize()
+    return fit_ms, ev[0].elapsed_time(ev[1]) / 5
+
+
+def full_measurements(args, cde, x, X, func, z0, device, world, step_ms):
+    """--full: everything the benchmark measures besides the headline figure, on rank 0 after the timed steps (none of it is
+    part of `value`).  Returns (keys for "extra", the CPU baseline or None)."""
+    fit_ms, fill_ms = fit_and_fill_ms(cde, x, device)
+    extra = {
+        "end_to_end_fit_fwd_adjoint_series_per_s": B * world / ((fit_ms + step_ms) * 1e-3),
+        "hermite_fit_ms": fit_ms,
+        "hermite_fit_series_per_s": B / (fit_ms * 1e-3),
+        "hermite_fit_hbm_gbs": B * 20352 / (fit_ms * 1e-3) / 1e9,
+        "hermite_fit_hbm_frac_of_8TBs": B * 20352 / (fit_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
+        "missing_value_fill_ms_10pct_nan": fill_ms,
+        "missing_value_fill_series_per_s": B / (fill_ms * 1e-3),
+    }
+    if world == 1:
+        extra["strong_scaling_proxy_1gpu"] = strong_scaling_proxy(cde, x, func, z0, step_ms)
+        extra["bf16x3_variant"] = bf16x3_variant(cde, X, func, z0)
+        extra["backprop_mode_adjoint_false"] = backprop_mode(cde, X, func, z0)
+        extra["other_fields"] = other_fields(cde, X, z0, device)
+        extra["other_configs"] = other_configs(cde, device)
+    cpu = cpu_baseline(min(args.cpu_sample, B)) if world == 1 and args.cpu_sample > 0 else None
+    return extra, cpu
 
 
 def cpu_baseline(max_sample, budget_s=20.0):
@@ -793,7 +846,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong: 32768 series in total (32768/N per GPU); weak: 32768 series per GPU")
-    ap.add_argument("--cpu-sample", type=int, default=8192, help="series in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything besides the headline figure (K1 / K0 rates, "
+                         "strong-scaling proxy, bf16x3 and adjoint=False variants, other fields and configs, CPU baseline)")
+    ap.add_argument("--cpu-sample", type=int, default=8192, help="--full: series in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one computed (solution, gradients) to DIR/<name>.npy")
     args = ap.parse_args()
@@ -867,28 +923,8 @@ def main():
     else:
         x, func, z0 = make_workload(device, seed=rank)
 
-    # K1 outside the timed region, timed on its own
-    torch.cuda.synchronize()
-    for _ in range(2):
-        coeffs = cde.hermite_cubic_coefficients_with_backward_differences(x)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev[0].record()
-    for _ in range(10):
-        coeffs = cde.hermite_cubic_coefficients_with_backward_differences(x)
-    ev[1].record()
-    torch.cuda.synchronize()
-    fit_ms = ev[0].elapsed_time(ev[1]) / 10
-    # K0 (missing-value fill) on the survey's irregular workload: 10 % of the entries missing
-    x_nan = x.masked_fill(torch.rand(x.shape, device=device) < 0.1, float("nan"))
-    cde.linear_interpolation_coeffs(x_nan)
-    ev[0].record()
-    for _ in range(5):
-        cde.linear_interpolation_coeffs(x_nan)
-    ev[1].record()
-    torch.cuda.synchronize()
-    fill_ms = ev[0].elapsed_time(ev[1]) / 5
-    del x_nan
-    X = cde.CubicSpline(coeffs)
+    # K1 outside the timed region (its own rate: --full)
+    X = cde.CubicSpline(cde.hermite_cubic_coefficients_with_backward_differences(x))
     t = X.interval
     params = list(func.parameters())
 
@@ -906,7 +942,7 @@ def main():
             last["out"], last["z"] = out, z
         return out
 
-    _log("hermite fit %.3f ms; warm-up" % fit_ms)
+    _log("warm-up")
     # the interpreter's own full collection (~50 ms in a torch process) is not part of the step being timed: run it now, BEFORE
     # the warm-up (the GPU idles meanwhile and needs the warm-up steps to come back to its clocks)
     gc.collect()
@@ -938,7 +974,7 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
-    # written now: the measurements below reuse the field and overwrite its gradients
+    # written now: the --full measurements below reuse the field and overwrite its gradients
     dumped = None
     if args.dump_outputs:
         dumped = dump_outputs(args.dump_outputs, *step_outputs(last["out"], last["z"], func), distributed, world, rank)
@@ -1011,25 +1047,14 @@ def main():
                 "forward_kernel_ms": fwd_avg,
                 "forward_tflops": B * FLOP_FWD / (fwd_avg * 1e-3) / 1e12 if fwd_avg > 0 else None,
                 "forward_only_series_per_s": B / (fwd_avg * 1e-3) if fwd_avg > 0 else None,
-                "end_to_end_fit_fwd_adjoint_series_per_s": B * world / ((fit_ms + elapsed / args.steps * 1e3) * 1e-3),
-                "hermite_fit_ms": fit_ms,
-                "hermite_fit_series_per_s": B / (fit_ms * 1e-3),
-                "hermite_fit_hbm_gbs": B * 20352 / (fit_ms * 1e-3) / 1e9,
-                "hermite_fit_hbm_frac_of_8TBs": B * 20352 / (fit_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                "missing_value_fill_ms_10pct_nan": fill_ms,
-                "missing_value_fill_series_per_s": B / (fill_ms * 1e-3),
             },
             "dumped_outputs": dumped,
         }
-        if world == 1:
-            result["extra"]["strong_scaling_proxy_1gpu"] = strong_scaling_proxy(cde, x, func, z0, elapsed / args.steps * 1e3)
-        if world == 1:
-            result["extra"]["bf16x3_variant"] = bf16x3_variant(cde, X, func, z0)
-            result["extra"]["backprop_mode_adjoint_false"] = backprop_mode(cde, X, func, z0)
-            result["extra"]["other_fields"] = other_fields(cde, X, z0, device)
-            result["extra"]["other_configs"] = other_configs(cde, device)
-        if world == 1 and args.cpu_sample > 0:
-            result["cpu_baseline"] = cpu_baseline(min(args.cpu_sample, B))
+        if args.full:
+            extra, cpu = full_measurements(args, cde, x, X, func, z0, device, world, elapsed / args.steps * 1e3)
+            result["extra"].update(extra)
+            if cpu is not None:
+                result["cpu_baseline"] = cpu
         emit(json.dumps(result))
     if distributed:
         dist.destroy_process_group()

@@ -2,8 +2,8 @@
 # Round-end evidence in one go (every step under its own timeout; databases stay in /tmp, only summaries are copied to
 # gpurun_out/, from where the ones to be judged are committed under profiles/):
 #   <tag>_gpu_tests.log                         python -m pytest tests -m gpu -q
-#   <tag>_bench_n1.json                         python bench.py
-#   <tag>_bench_kernel_stats.csv                rocprofv3 --kernel-trace --stats of `python bench.py --cpu-sample 0`
+#   <tag>_bench_n1.json                         python bench.py --full
+#   <tag>_bench_kernel_stats.csv                rocprofv3 --kernel-trace --stats of `python bench.py --full --cpu-sample 0`
 #   <tag>_k4am_{32,4096}_seminorm_kernel_stats.csv   the example model's default call (K4 forward, K4am backward)
 #   <tag>_phase_k4am_{32,4096}.log              where an attempt's time goes (instrumented library)
 #   <tag>_k4am_pmc_summary.csv                  MFMA-busy / wait / instruction counters of the K4am kernels at 4096 series
@@ -27,7 +27,7 @@ stats() {  # name, command...
 for step in $STEPS; do
   case $step in
     tests) (cd $ROOT && timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -4 > $OUT/${TAG}_gpu_tests.log; cat $OUT/${TAG}_gpu_tests.log | tail -2) ;;
-    bench) (cd $ROOT && timeout 600 python bench.py > $OUT/${TAG}_bench_n1.json 2> /tmp/bench.err || tail -5 /tmp/bench.err; python - <<PY
+    bench) (cd $ROOT && timeout 600 python bench.py --full > $OUT/${TAG}_bench_n1.json 2> $TMPDIR/bench.err || tail -5 $TMPDIR/bench.err; python - <<PY
 import json
 d = json.load(open("$OUT/${TAG}_bench_n1.json"))
 print({k: d[k] for k in ("value", "ms_per_step")}, {k: d["roofline"][k] for k in ("frac", "mfma_frac", "kernel_ms", "traffic")})
@@ -36,7 +36,7 @@ print({k: round(v, 1) if isinstance(v, float) else v for k, v in e.items() if "e
 print(d["extra"]["strong_scaling_proxy_1gpu"])
 PY
 ) ;;
-    stats) stats bench python $ROOT/bench.py --cpu-sample 0 ;;
+    stats) stats bench python $ROOT/bench.py --full --cpu-sample 0 ;;
     k4am) stats k4am_32_seminorm python $ROOT/scripts/prof_default_mlp.py 32 seminorm
           stats k4am_4096_seminorm python $ROOT/scripts/prof_default_mlp.py 4096 seminorm ;;
     phase) (cd $ROOT && CDE_PHASE_TRACE=1 timeout 300 python scripts/phase_trace.py k4am 32 2>&1 | grep -v amdgpu.ids > $OUT/${TAG}_phase_k4am_32.log

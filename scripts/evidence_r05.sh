@@ -5,7 +5,7 @@ set -u
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 timeout 300 python tests/tools/achieved_parity.py 2>/dev/null > $OUT/r05_achieved_parity.json; head -c 600 $OUT/r05_achieved_parity.json; echo
-timeout 600 python bench.py > $OUT/r05_bench_n1.json 2> /tmp/bench.err || tail -5 /tmp/bench.err
+timeout 600 python bench.py --full > $OUT/r05_bench_n1.json 2> $OUT/r05_bench_n1.err || tail -5 $OUT/r05_bench_n1.err
 python - <<PY
 import json
 d = json.load(open("$OUT/r05_bench_n1.json"))

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 timeout 900 python -m pytest tests -x -q -m gpu 2>&1 | tail -6 > $OUT/r05_gpu_tests_final.log; tail -2 $OUT/r05_gpu_tests_final.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee -a $OUT/r05_gpu_tests_final.log
-timeout 600 python bench.py > $OUT/r05_bench_n1.json 2> /tmp/bench.err || tail -5 /tmp/bench.err
+timeout 600 python bench.py --full > $OUT/r05_bench_n1.json 2> $OUT/r05_bench_n1.err || tail -5 $OUT/r05_bench_n1.err
 python - <<PY
 import json
 d = json.load(open("$OUT/r05_bench_n1.json"))

@@ -9,7 +9,7 @@ TAG=${1:-final}
 timeout 1200 python -m pytest tests -x -q -m gpu 2>&1 | tail -6 > $OUT/r06_gpu_tests_$TAG.log; tail -2 $OUT/r06_gpu_tests_$TAG.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee -a $OUT/r06_gpu_tests_$TAG.log
 timeout 300 python tests/tools/achieved_parity.py 2>/dev/null > $OUT/r06_achieved_parity.json; head -c 400 $OUT/r06_achieved_parity.json; echo
-timeout 600 python bench.py > $OUT/r06_bench_n1.json 2> /tmp/bench.err || tail -5 /tmp/bench.err
+timeout 600 python bench.py --full > $OUT/r06_bench_n1.json 2> $OUT/r06_bench_n1.err || tail -5 $OUT/r06_bench_n1.err
 python - <<PY
 import json
 d = json.load(open("$OUT/r06_bench_n1.json"))
