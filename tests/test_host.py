@@ -107,6 +107,17 @@ def test_argument_errors_come_back_as_codes_without_a_gpu():
     assert lib.cde_hermite_bdiff_coeffs(null, null, null, 0, 5, 3, 0, null) == 0       # empty batch is a no-op
     assert lib.cde_path_eval(null, null, null, 3, null, 2, 0, 3, 3, 1, 0, null) == -3
     assert lib.cde_rk4_adjoint_workspace_bytes(32768, 8, 32, 128, 0, 2) > 1024 * 8448 * 4
+    # the fixed-grid solvers: every call of the table is turned away before the first HIP call, with the recorded code
+    from rejected_calls import CALLS, REJECTED, build_args
+    assert set(REJECTED) == set(CALLS)
+    wrong = []
+    for name, by_code in REJECTED.items():
+        for code, cases in by_code.items():
+            for overrides in cases:
+                got = getattr(lib, name)(*build_args(CALLS[name], overrides))
+                if got != code:
+                    wrong.append("%s(%s): %d, expected %d" % (name, overrides, got, code))
+    assert not wrong, "\n".join(wrong)
 
 
 def test_no_cpu_fallback():

@@ -20,7 +20,7 @@ SOURCES = ["interp_kernels.hip", "rk4_generic.hip", "rk4_mfma.hip", "rk4_split.h
            "rk4_bf16x3.hip", "rk4_backprop.hip", "rk4_adjoint_pair.hip", "dopri5.hip", "dopri5_adjoint.hip", "dopri5_mlp_adjoint.hip", "mlp_grad_reduce.hip", "api.hip"]
 HEADERS = [os.path.join(_CSRC, "cde_common.h"), os.path.join(_CSRC, "cde_mfma.h"), os.path.join(_CSRC, "cde_split.h"),
            os.path.join(_CSRC, "cde_dopri.h"), os.path.join(_CSRC, "cde_dopri_adj.h"), os.path.join(_CSRC, "cde_dopri_ctl.h"),
-           os.path.join(_CSRC, "cde_mlp_adj.h"),
+           os.path.join(_CSRC, "cde_mlp_adj.h"), os.path.join(_CSRC, "cde_launch.h"),
            os.path.join(_HERE, "..", "include", "cde_mi355x.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC"]
 if PHASE_TRACE:

@@ -1,92 +1,10 @@
 // api.hip -- C-ABI entry points of the fused solvers: argument checks, stage table, kernel dispatch.
+// Every entry point checks its arguments, names each pointer once in the structs of cde_launch.h and hands those on.
 #include "cde_common.h"
+#include "cde_launch.h"
 
 namespace cde {
 
-// from rk4_generic.hip
-size_t generic_adjoint_workspace_bytes(int64_t B, int64_t C, int64_t H, size_t elem);
-bool generic_applicable(int64_t C, int64_t H, size_t elem, bool adjoint);
-template <typename T, typename TT>
-int launch_forward_generic(const void*, const void*, int64_t, int, const void*, const void*, int, const void*,
-                           const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t, int64_t,
-                           const int64_t*, const void*, hipStream_t);
-template <typename T, typename TT>
-int launch_adjoint_generic(const void*, const void*, int64_t, int, const void*, const void*, int, const void*,
-                           const void*, const void*, const int64_t*, int64_t, void*, void*, void*, int64_t, int64_t,
-                           int64_t, const int64_t*, const void*, void*, hipStream_t);
-// from rk4_mfma.hip
-bool mfma_applicable(int64_t C, int64_t H, int dtype, int act, bool adjoint);
-size_t mfma_adjoint_partial_bytes(int64_t B);
-template <typename TT>
-int launch_forward_mfma(const void*, const void*, int64_t, int, const void*, const void*, int, const void*,
-                        const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t, int64_t, const int64_t*,
-                        const void*, hipStream_t);
-template <typename TT>
-int launch_forward_mlp(const void*, const void*, int64_t, int, const void*, const void*, int64_t, const void*,
-                       const void*, int, const void*, const void*, int64_t, const void*, int64_t, void*, int64_t,
-                       int64_t, int64_t, const int64_t*, const void*, hipStream_t);
-template <typename TT>
-int launch_adjoint_mfma(const void*, const void*, int64_t, int, const void*, const void*, int, const void*,
-                        const void*, const void*, const int64_t*, int64_t, void*, void*, void*, int64_t, int64_t,
-                        int64_t, const int64_t*, const void*, float*, void*, hipStream_t);
-
-// from rk4_split.hip: one workgroup (4 waves) per 16 series -- the latency-oriented variant for small batches
-size_t split_adjoint_partial_bytes(int64_t B);
-template <typename TT>
-int launch_forward_split(const void*, const void*, int64_t, int, const void*, const void*, int, const void*,
-                         const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t, int64_t, const int64_t*,
-                         const void*, hipStream_t);
-template <typename TT>
-int launch_adjoint_split(const void*, const void*, int64_t, int, const void*, const void*, int, const void*,
-                         const void*, const void*, const int64_t*, int64_t, void*, void*, void*, int64_t, int64_t,
-                         int64_t, const int64_t*, const void*, float*, hipStream_t);
-
-bool mlp_shape_ok(int64_t C, int64_t H, int64_t width);        // rk4_mfma.hip
-bool mlp_shape_upper(int64_t C, int64_t H, int64_t width);     // rk4_mfma.hip
-
-// from rk4_wide.hip: affine fields with H <= 64, C <= 8 or H <= 32, C <= 16
-bool wide_applicable(int64_t C, int64_t H, int dtype, int act);
-size_t wide_adjoint_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t n_steps);
-template <typename TT>
-int launch_forward_wide(const void*, const void*, int64_t, int, const void*, const void*, int, const void*, const void*,
-                        int64_t, const void*, int64_t, void*, int64_t, int64_t, int64_t, const int64_t*, const void*,
-                        hipStream_t);
-template <typename TT>
-int launch_adjoint_wide(const void*, const void*, int64_t, int, const void*, const void*, int, const void*, const void*,
-                        const void*, int64_t, const int64_t*, int64_t, void*, void*, void*, int64_t, int64_t, int64_t,
-                        const int64_t*, const void*, void*, hipStream_t);
-
-// from rk4_mfma.hip
-template <typename TT>
-int launch_adjoint_jacobian_bx(const void*, const void*, int64_t, int, const void*, const void*, const void*, const void*,
-                               const void*, const int64_t*, int64_t, void*, void*, void*, int64_t, int64_t, int64_t,
-                               const int64_t*, const void*, float*, hipStream_t);
-// midpoint / euler: K2 and K3p with two stages / one stage per step (rk4_mfma.hip, rk4_adjoint_pair.hip)
-template <typename TT>
-int launch_forward_mfma_method(int, const void*, const void*, int64_t, int, const void*, const void*, const void*, const void*,
-                               int64_t, const void*, int64_t, void*, int64_t, int64_t, int64_t, const int64_t*, const void*,
-                               hipStream_t);
-template <typename TT>
-int launch_adjoint_jacobian_pair(const void*, const void*, int64_t, int, const void*, const void*, const void*, const void*,
-                                 const void*, const int64_t*, int64_t, void*, void*, void*, int64_t, int64_t, int64_t,
-                                 const int64_t*, const void*, float*, hipStream_t, int method, bool bx = false);
-// K2 with the stage states stored (rk4_mfma.hip) and the reverse-mode sweep over them (rk4_backprop.hip): adjoint=False
-template <typename TT>
-int launch_forward_mfma_stages(const void*, const void*, int64_t, int, const void*, const void*, int, const void*, const void*,
-                               int64_t, const void*, int64_t, void*, void*, int64_t, int64_t, int64_t, const int64_t*,
-                               const void*, hipStream_t);
-size_t backprop_workspace_bytes(int64_t B);
-int launch_backprop_jacobian(const void*, const void*, int64_t, int, const void*, const void*, int, const void*, const void*,
-                             int64_t, const float*, int64_t, const int64_t*, const int64_t*, const float*, void*, void*, void*,
-                             int64_t, int64_t, int64_t, const int64_t*, const float*, float*, void* grad_coeffs, hipStream_t);
-// from rk4_bf16x3.hip
-template <typename TT>
-int launch_forward_bf16x3(const void*, const void*, int64_t, int, const void*, const void*, const void*, const void*, int64_t,
-                          const void*, int64_t, void*, int64_t, int64_t, int64_t, const int64_t*, const void*, hipStream_t);
-template <typename TT>
-int launch_adjoint_bf16x3(const void*, const void*, int64_t, int, const void*, const void*, const void*, const void*,
-                          const void*, const int64_t*, int64_t, void*, void*, void*, int64_t, int64_t, int64_t,
-                          const int64_t*, const void*, float*, hipStream_t);
 static bool bf16x3_applicable(int64_t C, int64_t H, int dtype, int act) {
   return dtype == CDE_F32 && act == CDE_ACT_NONE && H >= 1 && H <= 32 && C >= 1 && C <= 8;
 }
@@ -96,25 +14,6 @@ static bool bf16x3_applicable(int64_t C, int64_t H, int dtype, int act) {
 static bool auto_bf16x3(int variant, int64_t B, int64_t C, int64_t H, int dtype, int act) {
   return variant == CDE_VARIANT_AUTO && B > CDE_SPLIT_MAX_BATCH && bf16x3_applicable(C, H, dtype, act);
 }
-
-// from rk4_mlp_adjoint.hip
-size_t mlp_adjoint_image_bytes();
-int launch_mlp_adjoint_images(const void*, const void*, int64_t, const void*, const void*, int64_t, int64_t, float*,
-                              hipStream_t);
-template <typename TT>
-int launch_mlp_adjoint_sweep(const void*, const void*, int64_t, int, int, const float*, void*, void*, const void*,
-                             int64_t, int64_t, const int64_t*, const void*, void*, void*, void*, void*, int64_t,
-                             int64_t, int64_t, void*, hipStream_t);
-
-// adjoint=False for the two-layer field: K2m storing its stage states, K3m's sweep as reverse mode through the steps
-template <typename TT>
-int launch_forward_mlp_stages(const void*, const void*, int64_t, int, const void*, const void*, int64_t, const void*,
-                              const void*, int, const void*, const void*, int64_t, const void*, int64_t, void*, void*, int64_t,
-                              int64_t, int64_t, const int64_t*, const void*, hipStream_t);
-template <typename TT>
-int launch_mlp_backprop_sweep(const void*, const void*, int64_t, int, int, const float*, const void*, int64_t, void*,
-                              const void*, int64_t, int64_t, const int64_t*, const void*, void*, void*, void*, void*, int64_t,
-                              int64_t, int64_t, void* grad_coeffs, hipStream_t);
 
 // Stage table: for solver step k over [grid[k], grid[k+1]] and RK stage j, the control interval
 // and fractional part at the stage time -- what CubicSpline._interpret_t (interpolation_cubic.py:
@@ -141,24 +40,69 @@ __global__ void stage_table_kernel(const T* __restrict__ knots, int64_t n_interv
   frac_out[e] = frac;
 }
 
+// A solve's stage table and what follows it in one allocation: [index: 4 n_steps int64 | frac: 4 n_steps elem | tail],
+// every part 256-byte aligned.  `n_grid` grid points are n_grid - 1 steps (none for an empty grid).
+static inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+struct StageBuffers {
+  int64_t* index; void* frac;
+  operator StageTable() const { return StageTable{index, frac}; }
+};
+struct StageWorkspace {
+  int64_t n_steps; size_t elem;
+  StageWorkspace(int64_t n_grid, size_t elem_bytes) : n_steps(n_grid > 1 ? n_grid - 1 : 0), elem(elem_bytes) {}
+  size_t frac_offset() const { return align256((size_t)(4 * n_steps) * sizeof(int64_t)); }
+  size_t tail_offset() const { return frac_offset() + align256((size_t)(4 * n_steps) * elem); }
+  size_t total(size_t tail_bytes) const { return tail_offset() + tail_bytes; }
+  StageBuffers table(const void* ws) const { return StageBuffers{(int64_t*)ws, (unsigned char*)ws + frac_offset()}; }
+  void* tail(const void* ws) const { return (unsigned char*)ws + tail_offset(); }
+};
+struct Dtypes { int state, time; };
+struct Workspace { void* base; size_t bytes; };
+
 template <typename T, typename TT>
-static int fill_stage_table(const void* knots, int64_t n_intervals, const void* grid, int64_t n_steps, int negate,
-                            int64_t* index_out, void* frac_out, hipStream_t s, int method = CDE_METHOD_RK4) {
+static int fill_stage_table(const Control& x, const void* grid, int64_t n_steps, int negate, int method, StageBuffers to,
+                            hipStream_t s) {
   if (n_steps <= 0) return CDE_OK;
   stage_table_kernel<T, TT><<<(unsigned)((4 * n_steps + 255) / 256), 256, 0, s>>>(
-      (const T*)knots, n_intervals, (const TT*)grid, n_steps, negate, index_out, (T*)frac_out, method);
+      (const T*)x.knots, x.n_intervals, (const TT*)grid, n_steps, negate, to.index, (T*)to.frac, method);
   return check_launch();
 }
 
-static inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+// A dtype code as a type: `f(Type<float>{})` / `f(Type<double>{})`, CDE_ERR_DTYPE for anything else ...
+template <typename T> struct Type { using type = T; };
+template <typename F>
+static int with_type(int dtype, F&& f) {
+  if (dtype == CDE_F32) return f(Type<float>{});
+  if (dtype == CDE_F64) return f(Type<double>{});
+  return CDE_ERR_DTYPE;
+}
+// ... and the state and time dtypes together: `f(Type<T>{}, Type<TT>{})`
+template <typename F>
+static int with_types(Dtypes d, F&& f) {
+  return with_type(d.state, [&](auto t) { return with_type(d.time, [&](auto tt) -> int { return f(t, tt); }); });
+}
 
-static bool pick_mfma(int variant, int64_t C, int64_t H, int dtype, int act, bool adjoint, int* rc) {
-  const bool ok = mfma_applicable(C, H, dtype, act, adjoint);
-  *rc = CDE_OK;
-  if (variant == CDE_VARIANT_MFMA || variant == CDE_VARIANT_SPLIT) { if (!ok) *rc = CDE_ERR_UNSUPPORTED; return ok; }
-  if (variant == CDE_VARIANT_GENERIC) return false;
-  if (variant != CDE_VARIANT_AUTO) { *rc = CDE_ERR_UNSUPPORTED; return false; }
-  return ok;
+// The forward direction of every solver: the stage table of `io.grid` into the caller's buffers, then `launch(T, TT)`.
+template <typename F>
+static int forward_solve(Dtypes d, const Control& x, const ForwardIO& io, int method, StageBuffers to, hipStream_t s,
+                         F&& launch) {
+  return with_types(d, [&](auto t, auto tt) -> int {
+    using T = typename decltype(t)::type;
+    using TT = typename decltype(tt)::type;
+    const int rc = fill_stage_table<T, TT>(x, io.grid, io.n_grid - 1, 0, method, to, s);
+    return rc != CDE_OK ? rc : launch(t, tt);
+  });
+}
+
+// Do the MFMA kernels (rk4_mfma.hip and its relatives) take the solve?  `unsupported`: the variant asks for them and the
+// shape does not fit, or the variant is unknown.
+enum class Mfma { no, yes, unsupported };
+static Mfma pick_mfma(int variant, int64_t C, int64_t H, int dtype, int act) {
+  const bool ok = mfma_applicable(C, H, dtype, act);
+  if (variant == CDE_VARIANT_MFMA || variant == CDE_VARIANT_SPLIT) return ok ? Mfma::yes : Mfma::unsupported;
+  if (variant == CDE_VARIANT_GENERIC) return Mfma::no;
+  if (variant != CDE_VARIANT_AUTO) return Mfma::unsupported;
+  return ok ? Mfma::yes : Mfma::no;
 }
 
 // Among the MFMA kernels: the one-wave-per-series-tile kernels (K2/K3) need B/16 (B/32) waves to fill 1024 SIMDs twice
@@ -174,122 +118,84 @@ static bool pick_split(int variant, int64_t B, bool control_grad, int act = CDE_
 
 // Shapes beyond the 32 x 8 tiles (H <= 64, C <= 8 or H <= 32, C <= 16): the wide tile kernels under AUTO
 static bool pick_wide(int variant, int64_t C, int64_t H, int dtype, int act) {
-  return variant == CDE_VARIANT_AUTO && !mfma_applicable(C, H, dtype, act, false) && wide_applicable(C, H, dtype, act);
+  return variant == CDE_VARIANT_AUTO && !mfma_applicable(C, H, dtype, act) && wide_applicable(C, H, dtype, act);
 }
 
 template <typename T, typename TT>
-static int forward_typed(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                         const void* bias, int act, const void* z0, const void* grid, int64_t n_grid,
-                         const void* t_out, int64_t n_out, void* z_out, int64_t B, int64_t C, int64_t H, int dtype,
-                         int variant, int64_t* stage_index, void* stage_frac, hipStream_t s) {
-  int rc = fill_stage_table<T, TT>(knots, n_intervals, grid, n_grid - 1, 0, stage_index, stage_frac, s);
-  if (rc != CDE_OK) return rc;
-  if (variant == CDE_VARIANT_BF16X3 || auto_bf16x3(variant, B, C, H, dtype, act)) {
-    if (!bf16x3_applicable(C, H, dtype, act)) return CDE_ERR_UNSUPPORTED;
-    return launch_forward_bf16x3<TT>(coeffs, knots, n_intervals, degree, W, bias, z0, grid, n_grid, t_out, n_out, z_out, B, C,
-                                     H, stage_index, stage_frac, s);
+static int forward_typed(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, int dtype, int variant,
+                         const StageTable& st, hipStream_t s) {
+  if (variant == CDE_VARIANT_BF16X3 || auto_bf16x3(variant, n.B, n.C, n.H, dtype, f.act)) {
+    if (!bf16x3_applicable(n.C, n.H, dtype, f.act)) return CDE_ERR_UNSUPPORTED;
+    return launch_forward_bf16x3<TT>(x, f, io, n, st, s);
   }
-  const bool use_mfma = pick_mfma(variant, C, H, dtype, act, false, &rc);
-  if (rc != CDE_OK) return rc;
-  if (use_mfma && pick_split(variant, B, false, act))
-    return launch_forward_split<TT>(coeffs, knots, n_intervals, degree, W, bias, act, z0, grid, n_grid, t_out, n_out,
-                                    z_out, B, C, H, stage_index, stage_frac, s);
-  if (use_mfma)
-    return launch_forward_mfma<TT>(coeffs, knots, n_intervals, degree, W, bias, act, z0, grid, n_grid, t_out, n_out, z_out,
-                                   B, C, H, stage_index, stage_frac, s);
-  if (pick_wide(variant, C, H, dtype, act))
-    return launch_forward_wide<TT>(coeffs, knots, n_intervals, degree, W, bias, act, z0, grid, n_grid, t_out, n_out,
-                                   z_out, B, C, H, stage_index, stage_frac, s);
-  return launch_forward_generic<T, TT>(coeffs, knots, n_intervals, degree, W, bias, act, z0, grid, n_grid, t_out, n_out,
-                                       z_out, B, C, H, stage_index, stage_frac, s);
+  const Mfma mfma = pick_mfma(variant, n.C, n.H, dtype, f.act);
+  if (mfma == Mfma::unsupported) return CDE_ERR_UNSUPPORTED;
+  if (mfma == Mfma::yes && pick_split(variant, n.B, false, f.act)) return launch_forward_split<TT>(x, f, io, n, st, s);
+  if (mfma == Mfma::yes) return launch_forward_mfma<TT>(x, f, io, n, st, s);
+  if (pick_wide(variant, n.C, n.H, dtype, f.act)) return launch_forward_wide<TT>(x, f, io, n, st, s);
+  return launch_forward_generic<T, TT>(x, f, io, n, st, s);
 }
 
+// workspace: [stage_index: 4*(n_sgrid-1) int64][stage_frac: 4*(n_sgrid-1) T][partials]
 template <typename T, typename TT>
-static int adjoint_typed(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                         const void* bias, int act, const void* z_saved, const void* grad_out, const void* sgrid,
-                         int64_t n_sgrid, const int64_t* seg_off, const int64_t* seg_off_host, int64_t n_out,
-                         void* grad_z0, void* grad_W, void* grad_b, int64_t B, int64_t C, int64_t H, int dtype,
-                         int variant, void* workspace, size_t workspace_bytes, void* grad_coeffs, hipStream_t s) {
-  int rc;
-  if (variant == CDE_VARIANT_BF16X3 || (auto_bf16x3(variant, B, C, H, dtype, act) && !grad_coeffs)) {
-    if (!bf16x3_applicable(C, H, dtype, act) || grad_coeffs) return CDE_ERR_UNSUPPORTED;
-    const int64_t n_steps_b = n_sgrid - 1;
-    const size_t off_frac_b = align256((size_t)(4 * n_steps_b) * sizeof(int64_t));
-    const size_t off_part_b = off_frac_b + align256((size_t)(4 * n_steps_b) * sizeof(T));
-    if (workspace_bytes < off_part_b + mfma_adjoint_partial_bytes(B)) return CDE_ERR_WORKSPACE;
-    int64_t* sidx = (int64_t*)workspace;
-    void* sfrac = (unsigned char*)workspace + off_frac_b;
-    rc = fill_stage_table<T, TT>(knots, n_intervals, sgrid, n_steps_b, 1, sidx, sfrac, s);
-    if (rc != CDE_OK) return rc;
+static int adjoint_typed(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, int dtype, int variant,
+                         Workspace ws, hipStream_t s) {
+  const bool bx = variant == CDE_VARIANT_BF16X3 || (auto_bf16x3(variant, n.B, n.C, n.H, dtype, f.act) && !io.grad_coeffs);
+  bool use_split = false, use_mfma = true, use_wide = false;
+  if (bx) {
+    if (!bf16x3_applicable(n.C, n.H, dtype, f.act) || io.grad_coeffs) return CDE_ERR_UNSUPPORTED;
+  } else {
+    const Mfma mfma = pick_mfma(variant, n.C, n.H, dtype, f.act);
+    if (mfma == Mfma::unsupported) return CDE_ERR_UNSUPPORTED;
+    use_mfma = mfma == Mfma::yes;
+    if (io.grad_coeffs && !use_mfma) return CDE_ERR_UNSUPPORTED;      // control gradients: MFMA kernels only
+    use_split = use_mfma && pick_split(variant, n.B, io.grad_coeffs != nullptr, f.act);
+    if (variant == CDE_VARIANT_SPLIT && !use_split) return CDE_ERR_UNSUPPORTED;
+    use_wide = !use_mfma && pick_wide(variant, n.C, n.H, dtype, f.act);
+  }
+  const StageWorkspace layout(io.n_sgrid, sizeof(T));
+  const size_t part_bytes = use_split ? split_adjoint_partial_bytes(n.B)
+                            : use_mfma ? mfma_adjoint_partial_bytes(n.B)
+                            : use_wide ? wide_adjoint_workspace_bytes(n.B, n.C, n.H, io.n_sgrid - 1)
+                                       : generic_adjoint_workspace_bytes(n.B, n.C, n.H, sizeof(T));
+  if (ws.bytes < layout.total(part_bytes)) return CDE_ERR_WORKSPACE;
+  const StageBuffers st = layout.table(ws.base);
+  void* partial = layout.tail(ws.base);
+  const int rc = fill_stage_table<T, TT>(x, io.sgrid, io.n_sgrid - 1, 1, CDE_METHOD_RK4, st, s);
+  if (rc != CDE_OK) return rc;
+  if (bx) {
     // the reverse sweep: K3p with its J rows on the bf16 pipe (rk4_adjoint_pair.hip); CDE_OPT_K3_WAVES = 1 keeps the
     // one-wave form K3bj (rk4_mfma.hip, bitwise the same results), CDE_OPT_K3_FORM = 1 K3b (three GEMMs, two of them on the
     // bf16 pipe)
-    if (cde::option(CDE_OPT_K3_FORM) != 1 && cde::option(CDE_OPT_K3_WAVES) != 1)
-      return launch_adjoint_jacobian_pair<TT>(coeffs, knots, n_intervals, degree, W, bias, z_saved, grad_out, sgrid, seg_off,
-                                              n_out, grad_z0, grad_W, grad_b, B, C, H, sidx, sfrac,
-                                              (float*)((unsigned char*)workspace + off_part_b), s, CDE_METHOD_RK4, true);
-    if (cde::option(CDE_OPT_K3_FORM) != 1)
-      return launch_adjoint_jacobian_bx<TT>(coeffs, knots, n_intervals, degree, W, bias, z_saved, grad_out, sgrid, seg_off,
-                                            n_out, grad_z0, grad_W, grad_b, B, C, H, sidx, sfrac,
-                                            (float*)((unsigned char*)workspace + off_part_b), s);
-    return launch_adjoint_bf16x3<TT>(coeffs, knots, n_intervals, degree, W, bias, z_saved, grad_out, sgrid, seg_off, n_out,
-                                     grad_z0, grad_W, grad_b, B, C, H, sidx, sfrac,
-                                     (float*)((unsigned char*)workspace + off_part_b), s);
+    if (option(CDE_OPT_K3_FORM) == 1) return launch_adjoint_bf16x3<TT>(x, f, io, n, st, (float*)partial, s);
+    if (option(CDE_OPT_K3_WAVES) == 1) return launch_adjoint_jacobian_bx<TT>(x, f, io, n, st, (float*)partial, s);
+    return launch_adjoint_jacobian_pair<TT>(x, f, io, n, st, (float*)partial, s, PairForm{CDE_METHOD_RK4, PairRows::bf16});
   }
-  const bool use_mfma = pick_mfma(variant, C, H, dtype, act, true, &rc);
-  if (rc != CDE_OK) return rc;
-  if (grad_coeffs && !use_mfma) return CDE_ERR_UNSUPPORTED;      // control gradients: MFMA kernels only
-  // workspace: [stage_index: 4*(n_sgrid-1) int64][stage_frac: 4*(n_sgrid-1) T][partials]
-  const int64_t n_steps = n_sgrid - 1;
-  const size_t off_frac = align256((size_t)(4 * n_steps) * sizeof(int64_t));
-  const size_t off_part = off_frac + align256((size_t)(4 * n_steps) * sizeof(T));
-  const bool use_split = use_mfma && pick_split(variant, B, grad_coeffs != nullptr, act);
-  if (variant == CDE_VARIANT_SPLIT && !use_split) return CDE_ERR_UNSUPPORTED;
-  const bool use_wide = !use_mfma && pick_wide(variant, C, H, dtype, act);
-  const size_t part_bytes = use_split ? split_adjoint_partial_bytes(B)
-                            : use_mfma ? mfma_adjoint_partial_bytes(B)
-                            : use_wide ? wide_adjoint_workspace_bytes(B, C, H, n_steps)
-                                       : generic_adjoint_workspace_bytes(B, C, H, sizeof(T));
-  if (workspace_bytes < off_part + part_bytes) return CDE_ERR_WORKSPACE;
-  int64_t* stage_index = (int64_t*)workspace;
-  void* stage_frac = (unsigned char*)workspace + off_frac;
-  void* partial = (unsigned char*)workspace + off_part;
-  rc = fill_stage_table<T, TT>(knots, n_intervals, sgrid, n_steps, 1, stage_index, stage_frac, s);
-  if (rc != CDE_OK) return rc;
-  if (use_split)
-    return launch_adjoint_split<TT>(coeffs, knots, n_intervals, degree, W, bias, act, z_saved, grad_out, sgrid, seg_off,
-                                    n_out, grad_z0, grad_W, grad_b, B, C, H, stage_index, stage_frac, (float*)partial, s);
-  if (use_mfma)
-    return launch_adjoint_mfma<TT>(coeffs, knots, n_intervals, degree, W, bias, act, z_saved, grad_out, sgrid, seg_off, n_out,
-                                   grad_z0, grad_W, grad_b, B, C, H, stage_index, stage_frac, (float*)partial,
-                                   grad_coeffs, s);
-  if (use_wide)
-    return launch_adjoint_wide<TT>(coeffs, knots, n_intervals, degree, W, bias, act, z_saved, grad_out, sgrid, n_sgrid,
-                                   seg_off_host, n_out, grad_z0, grad_W, grad_b, B, C, H, stage_index, stage_frac, partial, s);
-  return launch_adjoint_generic<T, TT>(coeffs, knots, n_intervals, degree, W, bias, act, z_saved, grad_out, sgrid,
-                                       seg_off, n_out, grad_z0, grad_W, grad_b, B, C, H, stage_index, stage_frac,
-                                       partial, s);
+  if (use_split) return launch_adjoint_split<TT>(x, f, io, n, st, (float*)partial, s);
+  if (use_mfma) return launch_adjoint_mfma<TT>(x, f, io, n, st, (float*)partial, s);
+  if (use_wide) return launch_adjoint_wide<TT>(x, f, io, n, st, partial, s);
+  return launch_adjoint_generic<T, TT>(x, f, io, n, st, partial, s);
 }
 
 }  // namespace cde
 
+using namespace cde;
+
 // which arithmetic an rk4 solve of the affine field takes (1: the bf16x3 kernels, 0: the exact-f32 / other kernels) --
 // the rule of forward_typed / adjoint_typed, for the host's dispatch record
 extern "C" int cde_rk4_bf16x3_form(int64_t B, int64_t C, int64_t H, int dtype, int act, int variant) {
-  if (variant == CDE_VARIANT_BF16X3) return cde::bf16x3_applicable(C, H, dtype, act) ? 1 : 0;
-  return cde::auto_bf16x3(variant, B, C, H, dtype, act) ? 1 : 0;
+  if (variant == CDE_VARIANT_BF16X3) return bf16x3_applicable(C, H, dtype, act) ? 1 : 0;
+  return auto_bf16x3(variant, B, C, H, dtype, act) ? 1 : 0;
 }
 
 extern "C" int cde_rk4_supported(int64_t C, int64_t H, int dtype, int act, int adjoint, int variant) {
   if (C < 1 || H < 1 || (dtype != CDE_F32 && dtype != CDE_F64)) return 0;
   if (act != CDE_ACT_NONE && act != CDE_ACT_TANH) return 0;
-  if (variant == CDE_VARIANT_BF16X3) return cde::bf16x3_applicable(C, H, dtype, act) ? 1 : 0;
-  int rc;
-  const bool mfma = cde::pick_mfma(variant, C, H, dtype, act, adjoint != 0, &rc);
-  if (rc != CDE_OK) return 0;
-  if (mfma) return 1;
-  if (cde::pick_wide(variant, C, H, dtype, act)) return 1;
-  return cde::generic_applicable(C, H, dtype == CDE_F64 ? 8 : 4, adjoint != 0) ? 1 : 0;
+  if (variant == CDE_VARIANT_BF16X3) return bf16x3_applicable(C, H, dtype, act) ? 1 : 0;
+  const Mfma mfma = pick_mfma(variant, C, H, dtype, act);
+  if (mfma != Mfma::no) return mfma == Mfma::yes ? 1 : 0;
+  if (pick_wide(variant, C, H, dtype, act)) return 1;
+  return generic_applicable(C, H, dtype == CDE_F64 ? 8 : 4, adjoint != 0) ? 1 : 0;
 }
 
 extern "C" int cde_rk4_forward_linear(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -302,16 +208,15 @@ extern "C" int cde_rk4_forward_linear(const void* coeffs, const void* knots, int
   if (B == 0) return CDE_OK;
   if (!coeffs || !knots || !W || !bias || !z0 || !grid || !t_out || !z_out) return CDE_ERR_NULL;
   if (n_grid > 1 && (!stage_index || !stage_frac)) return CDE_ERR_NULL;
+  const Control x{coeffs, knots, n_intervals, degree};
+  const AffineField f{W, bias, act};
+  const ForwardIO io{z0, grid, n_grid, t_out, n_out, z_out, nullptr};
+  const Shape n{B, C, H};
+  const StageBuffers st{stage_index, stage_frac};
   hipStream_t s = (hipStream_t)stream;
-#define CDE_CALL(T, TT)                                                                                              \
-  return cde::forward_typed<T, TT>(coeffs, knots, n_intervals, degree, W, bias, act, z0, grid, n_grid, t_out, n_out, \
-                                   z_out, B, C, H, dtype, variant, stage_index, stage_frac, s)
-  if (dtype == CDE_F32 && time_dtype == CDE_F32) CDE_CALL(float, float);
-  if (dtype == CDE_F32 && time_dtype == CDE_F64) CDE_CALL(float, double);
-  if (dtype == CDE_F64 && time_dtype == CDE_F64) CDE_CALL(double, double);
-  if (dtype == CDE_F64 && time_dtype == CDE_F32) CDE_CALL(double, float);
-#undef CDE_CALL
-  return CDE_ERR_DTYPE;
+  return forward_solve(Dtypes{dtype, time_dtype}, x, io, CDE_METHOD_RK4, st, s, [&](auto t, auto tt) {
+    return forward_typed<typename decltype(t)::type, typename decltype(tt)::type>(x, f, io, n, dtype, variant, st, s);
+  });
 }
 
 extern "C" int cde_rk4_forward_mlp(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -324,70 +229,51 @@ extern "C" int cde_rk4_forward_mlp(const void* coeffs, const void* knots, int64_
   if (B == 0) return CDE_OK;
   if (!coeffs || !knots || !W1 || !bias1 || !W2 || !bias2 || !z0 || !grid || !t_out || !z_out) return CDE_ERR_NULL;
   if (n_grid > 1 && (!stage_index || !stage_frac)) return CDE_ERR_NULL;
+  const Control x{coeffs, knots, n_intervals, degree};
+  const TwoLayerField f{W1, bias1, width, W2, bias2, act};
+  const ForwardIO io{z0, grid, n_grid, t_out, n_out, z_out, nullptr};
+  const Shape n{B, C, H};
+  const StageBuffers st{stage_index, stage_frac};
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (time_dtype == CDE_F32) {
-    rc = cde::fill_stage_table<float, float>(knots, n_intervals, grid, n_grid - 1, 0, stage_index, stage_frac, s);
-    if (rc != CDE_OK) return rc;
-    return cde::launch_forward_mlp<float>(coeffs, knots, n_intervals, degree, W1, bias1, width, W2, bias2, act, z0, grid,
-                                          n_grid, t_out, n_out, z_out, B, C, H, stage_index, stage_frac, s);
-  }
-  if (time_dtype == CDE_F64) {
-    rc = cde::fill_stage_table<float, double>(knots, n_intervals, grid, n_grid - 1, 0, stage_index, stage_frac, s);
-    if (rc != CDE_OK) return rc;
-    return cde::launch_forward_mlp<double>(coeffs, knots, n_intervals, degree, W1, bias1, width, W2, bias2, act, z0, grid,
-                                           n_grid, t_out, n_out, z_out, B, C, H, stage_index, stage_frac, s);
-  }
-  return CDE_ERR_DTYPE;
+  return forward_solve(Dtypes{dtype, time_dtype}, x, io, CDE_METHOD_RK4, st, s, [&](auto, auto tt) {
+    return launch_forward_mlp<typename decltype(tt)::type>(x, f, io, n, st, s);
+  });
 }
 
 extern "C" size_t cde_rk4_adjoint_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t n_sgrid, int dtype,
                                                   int variant) {
   const size_t elem = dtype == CDE_F64 ? 8 : 4;
-  const int64_t n_steps = n_sgrid > 1 ? n_sgrid - 1 : 0;
-  size_t bytes = cde::align256((size_t)(4 * n_steps) * sizeof(int64_t)) + cde::align256((size_t)(4 * n_steps) * elem);
-  if (variant == CDE_VARIANT_BF16X3) return bytes + cde::mfma_adjoint_partial_bytes(B);
-  int rc;
-  const bool use_mfma = cde::pick_mfma(variant, C, H, dtype, CDE_ACT_NONE, true, &rc);
+  const StageWorkspace layout(n_sgrid, elem);
+  if (variant == CDE_VARIANT_BF16X3) return layout.total(mfma_adjoint_partial_bytes(B));
+  const bool use_mfma = pick_mfma(variant, C, H, dtype, CDE_ACT_NONE) == Mfma::yes;
   // AUTO may resolve to either kernel depending on the activation: reserve the larger need
-  size_t a = cde::mfma_adjoint_partial_bytes(B);
+  size_t a = mfma_adjoint_partial_bytes(B);
   if (variant != CDE_VARIANT_MFMA && variant != CDE_VARIANT_GENERIC) {    // AUTO may resolve to the tile kernels (tanh: at any B)
-    const size_t sp = cde::split_adjoint_partial_bytes(B);
+    const size_t sp = split_adjoint_partial_bytes(B);
     a = sp > a ? sp : a;
   }
-  size_t b = cde::generic_adjoint_workspace_bytes(B, C, H, elem);
-  if (!use_mfma && (cde::pick_wide(variant, C, H, dtype, CDE_ACT_NONE))) {
-    const size_t wb = cde::wide_adjoint_workspace_bytes(B, C, H, n_steps);
+  size_t b = generic_adjoint_workspace_bytes(B, C, H, elem);
+  if (!use_mfma && (pick_wide(variant, C, H, dtype, CDE_ACT_NONE))) {
+    const size_t wb = wide_adjoint_workspace_bytes(B, C, H, layout.n_steps);
     b = wb > b ? wb : b;
   }
-  if (variant == CDE_VARIANT_MFMA || variant == CDE_VARIANT_SPLIT) bytes += a;
-  else if (variant == CDE_VARIANT_GENERIC || !use_mfma) bytes += b;
-  else bytes += (a > b ? a : b);
-  return bytes;
+  if (variant == CDE_VARIANT_MFMA || variant == CDE_VARIANT_SPLIT) return layout.total(a);
+  if (variant == CDE_VARIANT_GENERIC || !use_mfma) return layout.total(b);
+  return layout.total(a > b ? a : b);
 }
 
-static int adjoint_linear_impl(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                               const void* bias, int act, const void* z_saved, const void* grad_out, const void* sgrid,
-                               int64_t n_sgrid, const int64_t* seg_off, const int64_t* seg_off_host, int64_t n_out,
-                               void* grad_z0, void* grad_W, void* grad_b, void* grad_coeffs, int64_t B, int64_t C,
-                               int64_t H, int dtype, int time_dtype, int variant, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || n_intervals < 1 || n_out < 1 || n_sgrid < 0) return CDE_ERR_SHAPE;
-  if (act != CDE_ACT_NONE && act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
-  if (!coeffs || !knots || !W || !bias || !z_saved || !grad_out || !grad_z0 || !grad_W || !grad_b || !workspace)
+static int adjoint_linear_impl(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, Dtypes d,
+                               int variant, Workspace ws, void* stream) {
+  if (n.B < 1 || n.C < 1 || n.H < 1 || x.n_intervals < 1 || io.n_out < 1 || io.n_sgrid < 0) return CDE_ERR_SHAPE;
+  if (f.act != CDE_ACT_NONE && f.act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
+  if (!x.coeffs || !x.knots || !f.W || !f.bias || !io.z_saved || !io.grad_out || !io.grad_z0 || !io.grad_W || !io.grad_b ||
+      !ws.base)
     return CDE_ERR_NULL;
-  if (n_out > 1 && (!sgrid || !seg_off)) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-#define CDE_CALL(T, TT)                                                                                               \
-  return cde::adjoint_typed<T, TT>(coeffs, knots, n_intervals, degree, W, bias, act, z_saved, grad_out, sgrid,        \
-                                   n_sgrid, seg_off, seg_off_host, n_out, grad_z0, grad_W, grad_b, B, C, H, dtype,    \
-                                   variant, workspace, workspace_bytes, grad_coeffs, s)
-  if (dtype == CDE_F32 && time_dtype == CDE_F32) CDE_CALL(float, float);
-  if (dtype == CDE_F32 && time_dtype == CDE_F64) CDE_CALL(float, double);
-  if (dtype == CDE_F64 && time_dtype == CDE_F64) CDE_CALL(double, double);
-  if (dtype == CDE_F64 && time_dtype == CDE_F32) CDE_CALL(double, float);
-#undef CDE_CALL
-  return CDE_ERR_DTYPE;
+  if (io.n_out > 1 && (!io.sgrid || !io.seg_off)) return CDE_ERR_NULL;
+  return with_types(d, [&](auto t, auto tt) {
+    return adjoint_typed<typename decltype(t)::type, typename decltype(tt)::type>(x, f, io, n, d.state, variant, ws,
+                                                                                  (hipStream_t)stream);
+  });
 }
 
 extern "C" int cde_rk4_adjoint_linear(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -396,9 +282,10 @@ extern "C" int cde_rk4_adjoint_linear(const void* coeffs, const void* knots, int
                                       const int64_t* seg_off_host, int64_t n_out, void* grad_z0, void* grad_W,
                                       void* grad_b, int64_t B, int64_t C, int64_t H, int dtype, int time_dtype,
                                       int variant, void* workspace, size_t workspace_bytes, void* stream) {
-  return adjoint_linear_impl(coeffs, knots, n_intervals, degree, W, bias, act, z_saved, grad_out, sgrid, n_sgrid, seg_off,
-                             seg_off_host, n_out, grad_z0, grad_W, grad_b, nullptr, B, C, H, dtype, time_dtype, variant, workspace,
-                             workspace_bytes, stream);
+  return adjoint_linear_impl(Control{coeffs, knots, n_intervals, degree}, AffineField{W, bias, act},
+                             AdjointIO{z_saved, grad_out, sgrid, n_sgrid, seg_off, seg_off_host, n_out, grad_z0, grad_W,
+                                       grad_b, nullptr},
+                             Shape{B, C, H}, Dtypes{dtype, time_dtype}, variant, Workspace{workspace, workspace_bytes}, stream);
 }
 
 extern "C" int cde_rk4_adjoint_linear_dcontrol(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -409,15 +296,17 @@ extern "C" int cde_rk4_adjoint_linear_dcontrol(const void* coeffs, const void* k
                                                int dtype, int time_dtype, void* workspace, size_t workspace_bytes,
                                                void* stream) {
   if (!grad_coeffs) return CDE_ERR_NULL;
-  return adjoint_linear_impl(coeffs, knots, n_intervals, degree, W, bias, act, z_saved, grad_out, sgrid, n_sgrid, seg_off,
-                             nullptr, n_out, grad_z0, grad_W, grad_b, grad_coeffs, B, C, H, dtype, time_dtype, CDE_VARIANT_MFMA,
-                             workspace, workspace_bytes, stream);
+  return adjoint_linear_impl(Control{coeffs, knots, n_intervals, degree}, AffineField{W, bias, act},
+                             AdjointIO{z_saved, grad_out, sgrid, n_sgrid, seg_off, nullptr, n_out, grad_z0, grad_W, grad_b,
+                                       grad_coeffs},
+                             Shape{B, C, H}, Dtypes{dtype, time_dtype}, CDE_VARIANT_MFMA, Workspace{workspace, workspace_bytes},
+                             stream);
 }
 
 // ---------------------------------------------------------------------------------------------- midpoint / euler
 extern "C" int cde_fixed_supported(int method, int64_t C, int64_t H, int dtype, int act) {
   if (method != CDE_METHOD_MIDPOINT && method != CDE_METHOD_EULER) return 0;
-  return (dtype == CDE_F32 && act == CDE_ACT_NONE && cde::mfma_applicable(C, H, dtype, act, true)) ? 1 : 0;
+  return (dtype == CDE_F32 && act == CDE_ACT_NONE && mfma_applicable(C, H, dtype, act)) ? 1 : 0;
 }
 
 extern "C" int cde_fixed_forward_linear(int method, const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -430,28 +319,20 @@ extern "C" int cde_fixed_forward_linear(int method, const void* coeffs, const vo
   if (B == 0) return CDE_OK;
   if (!coeffs || !knots || !W || !bias || !z0 || !grid || !t_out || !z_out) return CDE_ERR_NULL;
   if (n_grid > 1 && (!stage_index || !stage_frac)) return CDE_ERR_NULL;
+  const Control x{coeffs, knots, n_intervals, degree};
+  const AffineField f{W, bias, CDE_ACT_NONE};
+  const ForwardIO io{z0, grid, n_grid, t_out, n_out, z_out, nullptr};
+  const Shape n{B, C, H};
+  const StageBuffers st{stage_index, stage_frac};
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (time_dtype == CDE_F32) {
-    rc = cde::fill_stage_table<float, float>(knots, n_intervals, grid, n_grid - 1, 0, stage_index, stage_frac, s, method);
-    if (rc != CDE_OK) return rc;
-    return cde::launch_forward_mfma_method<float>(method, coeffs, knots, n_intervals, degree, W, bias, z0, grid, n_grid, t_out,
-                                                  n_out, z_out, B, C, H, stage_index, stage_frac, s);
-  }
-  if (time_dtype == CDE_F64) {
-    rc = cde::fill_stage_table<float, double>(knots, n_intervals, grid, n_grid - 1, 0, stage_index, stage_frac, s, method);
-    if (rc != CDE_OK) return rc;
-    return cde::launch_forward_mfma_method<double>(method, coeffs, knots, n_intervals, degree, W, bias, z0, grid, n_grid,
-                                                   t_out, n_out, z_out, B, C, H, stage_index, stage_frac, s);
-  }
-  return CDE_ERR_DTYPE;
+  return forward_solve(Dtypes{dtype, time_dtype}, x, io, method, st, s, [&](auto, auto tt) {
+    return launch_forward_mfma_method<typename decltype(tt)::type>(method, x, f, io, n, st, s);
+  });
 }
 
 // workspace: [stage_index: 4*(n_sgrid-1) int64][stage_frac: 4*(n_sgrid-1) f32][per-wave partial parameter gradients]
 extern "C" size_t cde_fixed_adjoint_workspace_bytes(int64_t B, int64_t n_sgrid) {
-  const int64_t n_steps = n_sgrid > 1 ? n_sgrid - 1 : 0;
-  return cde::align256((size_t)(4 * n_steps) * sizeof(int64_t)) + cde::align256((size_t)(4 * n_steps) * sizeof(float)) +
-         (B > 0 ? cde::mfma_adjoint_partial_bytes(B) : 0);
+  return StageWorkspace(n_sgrid, sizeof(float)).total(B > 0 ? mfma_adjoint_partial_bytes(B) : 0);
 }
 
 extern "C" int cde_fixed_adjoint_linear(int method, const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -466,33 +347,24 @@ extern "C" int cde_fixed_adjoint_linear(int method, const void* coeffs, const vo
     return CDE_ERR_NULL;
   if (n_out > 1 && (!sgrid || !seg_off)) return CDE_ERR_NULL;
   if (workspace_bytes < cde_fixed_adjoint_workspace_bytes(B, n_sgrid)) return CDE_ERR_WORKSPACE;
+  const Control x{coeffs, knots, n_intervals, degree};
+  const AffineField f{W, bias, CDE_ACT_NONE};
+  const AdjointIO io{z_saved, grad_out, sgrid, n_sgrid, seg_off, nullptr, n_out, grad_z0, grad_W, grad_b, nullptr};
+  const Shape n{B, C, H};
+  const StageWorkspace layout(n_sgrid, sizeof(float));
+  const StageBuffers st = layout.table(workspace);
   hipStream_t s = (hipStream_t)stream;
-  const int64_t n_steps = n_sgrid > 1 ? n_sgrid - 1 : 0;
-  unsigned char* base = (unsigned char*)workspace;
-  int64_t* stage_index = (int64_t*)base;
-  void* stage_frac = base + cde::align256((size_t)(4 * n_steps) * sizeof(int64_t));
-  float* partial = (float*)((unsigned char*)stage_frac + cde::align256((size_t)(4 * n_steps) * sizeof(float)));
-  int rc;
-  if (time_dtype == CDE_F32) {
-    rc = cde::fill_stage_table<float, float>(knots, n_intervals, sgrid, n_steps, 1, stage_index, stage_frac, s, method);
+  return with_type(time_dtype, [&](auto tt) -> int {
+    using TT = typename decltype(tt)::type;
+    const int rc = fill_stage_table<float, TT>(x, sgrid, layout.n_steps, 1, method, st, s);
     if (rc != CDE_OK) return rc;
-    return cde::launch_adjoint_jacobian_pair<float>(coeffs, knots, n_intervals, degree, W, bias, z_saved, grad_out, sgrid,
-                                                    seg_off, n_out, grad_z0, grad_W, grad_b, B, C, H, stage_index, stage_frac,
-                                                    partial, s, method);
-  }
-  if (time_dtype == CDE_F64) {
-    rc = cde::fill_stage_table<float, double>(knots, n_intervals, sgrid, n_steps, 1, stage_index, stage_frac, s, method);
-    if (rc != CDE_OK) return rc;
-    return cde::launch_adjoint_jacobian_pair<double>(coeffs, knots, n_intervals, degree, W, bias, z_saved, grad_out, sgrid,
-                                                     seg_off, n_out, grad_z0, grad_W, grad_b, B, C, H, stage_index, stage_frac,
-                                                     partial, s, method);
-  }
-  return CDE_ERR_DTYPE;
+    return launch_adjoint_jacobian_pair<TT>(x, f, io, n, st, (float*)layout.tail(workspace), s, PairForm{method, PairRows::f32});
+  });
 }
 
 // ---------------------------------------------------------------------------------------------- K3d (adjoint=False)
 extern "C" int cde_rk4_backprop_supported(int64_t C, int64_t H, int dtype, int act) {
-  return (dtype == CDE_F32 && (act == CDE_ACT_NONE || act == CDE_ACT_TANH) && cde::mfma_applicable(C, H, dtype, act, true)) ? 1 : 0;
+  return (dtype == CDE_F32 && (act == CDE_ACT_NONE || act == CDE_ACT_TANH) && mfma_applicable(C, H, dtype, act)) ? 1 : 0;
 }
 
 extern "C" int cde_rk4_forward_linear_stages(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -506,44 +378,30 @@ extern "C" int cde_rk4_forward_linear_stages(const void* coeffs, const void* kno
   if (B == 0) return CDE_OK;
   if (!coeffs || !knots || !W || !bias || !z0 || !grid || !t_out || !z_out) return CDE_ERR_NULL;
   if (n_grid > 1 && (!stage_index || !stage_frac || !stages)) return CDE_ERR_NULL;
+  const Control x{coeffs, knots, n_intervals, degree};
+  const AffineField f{W, bias, act};
+  const ForwardIO io{z0, grid, n_grid, t_out, n_out, z_out, stages};
+  const Shape n{B, C, H};
+  const StageBuffers st{stage_index, stage_frac};
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (time_dtype == CDE_F32) {
-    rc = cde::fill_stage_table<float, float>(knots, n_intervals, grid, n_grid - 1, 0, stage_index, stage_frac, s);
-    if (rc != CDE_OK) return rc;
-    return cde::launch_forward_mfma_stages<float>(coeffs, knots, n_intervals, degree, W, bias, act, z0, grid, n_grid, t_out,
-                                                  n_out, z_out, stages, B, C, H, stage_index, stage_frac, s);
-  }
-  if (time_dtype == CDE_F64) {
-    rc = cde::fill_stage_table<float, double>(knots, n_intervals, grid, n_grid - 1, 0, stage_index, stage_frac, s);
-    if (rc != CDE_OK) return rc;
-    return cde::launch_forward_mfma_stages<double>(coeffs, knots, n_intervals, degree, W, bias, act, z0, grid, n_grid, t_out,
-                                                   n_out, z_out, stages, B, C, H, stage_index, stage_frac, s);
-  }
-  return CDE_ERR_DTYPE;
+  return forward_solve(Dtypes{dtype, time_dtype}, x, io, CDE_METHOD_RK4, st, s, [&](auto, auto tt) {
+    return launch_forward_mfma_stages<typename decltype(tt)::type>(x, f, io, n, st, s);
+  });
 }
 
-extern "C" size_t cde_rk4_backprop_workspace_bytes(int64_t B) { return B > 0 ? cde::backprop_workspace_bytes(B) : 0; }
+extern "C" size_t cde_rk4_backprop_workspace_bytes(int64_t B) { return B > 0 ? backprop_workspace_bytes(B) : 0; }
 
-static int rk4_backprop_linear_impl(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
-                                       const void* W, const void* bias, int act, const void* stages, const void* grad_out,
-                                       int64_t n_out,
-                                       const float* step_dt, int64_t n_steps, const int64_t* node_ptr,
-                                       const int64_t* node_out, const float* node_weight, void* grad_z0, void* grad_W,
-                                       void* grad_b, void* grad_coeffs, int64_t B, int64_t C, int64_t H, int dtype,
-                                       const int64_t* stage_index, const void* stage_frac, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || n_intervals < 1 || n_out < 1 || n_steps < 0) return CDE_ERR_SHAPE;
+static int rk4_backprop_linear_impl(const Control& x, const AffineField& f, const BackpropIO& io, const Shape& n, int dtype,
+                                    const StageTable& st, Workspace ws, void* stream) {
+  if (n.B < 1 || n.C < 1 || n.H < 1 || x.n_intervals < 1 || io.n_out < 1 || io.n_steps < 0) return CDE_ERR_SHAPE;
   if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
-  if (!cde_rk4_backprop_supported(C, H, dtype, act)) return CDE_ERR_UNSUPPORTED;
-  if (!coeffs || !knots || !W || !bias || !grad_out || !node_ptr || !node_out || !node_weight || !grad_z0 || !grad_W || !grad_b ||
-      !workspace)
+  if (!cde_rk4_backprop_supported(n.C, n.H, dtype, f.act)) return CDE_ERR_UNSUPPORTED;
+  if (!x.coeffs || !x.knots || !f.W || !f.bias || !io.grad_out || !io.node_ptr || !io.node_out || !io.node_weight ||
+      !io.grad_z0 || !io.grad_W || !io.grad_b || !ws.base)
     return CDE_ERR_NULL;
-  if (n_steps > 0 && (!stages || !step_dt || !stage_index || !stage_frac)) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_rk4_backprop_workspace_bytes(B)) return CDE_ERR_WORKSPACE;
-  return cde::launch_backprop_jacobian(coeffs, knots, n_intervals, degree, W, bias, act, stages, grad_out, n_out, step_dt, n_steps,
-                                       node_ptr, node_out, node_weight, grad_z0, grad_W, grad_b, B, C, H, stage_index,
-                                       (const float*)stage_frac, (float*)workspace, grad_coeffs, (hipStream_t)stream);
+  if (io.n_steps > 0 && (!io.stages || !io.step_dt || !st.index || !st.frac)) return CDE_ERR_NULL;
+  if (ws.bytes < cde_rk4_backprop_workspace_bytes(n.B)) return CDE_ERR_WORKSPACE;
+  return launch_backprop_jacobian(x, f, io, n, st, (float*)ws.base, (hipStream_t)stream);
 }
 
 extern "C" int cde_rk4_backprop_linear(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -554,9 +412,11 @@ extern "C" int cde_rk4_backprop_linear(const void* coeffs, const void* knots, in
                                        void* grad_b, int64_t B, int64_t C, int64_t H, int dtype,
                                        const int64_t* stage_index, const void* stage_frac, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-  return rk4_backprop_linear_impl(coeffs, knots, n_intervals, degree, W, bias, act, stages, grad_out, n_out, step_dt, n_steps,
-                                  node_ptr, node_out, node_weight, grad_z0, grad_W, grad_b, nullptr, B, C, H, dtype,
-                                  stage_index, stage_frac, workspace, workspace_bytes, stream);
+  return rk4_backprop_linear_impl(Control{coeffs, knots, n_intervals, degree}, AffineField{W, bias, act},
+                                  BackpropIO{stages, grad_out, n_out, step_dt, n_steps, node_ptr, node_out, node_weight,
+                                             grad_z0, grad_W, grad_b, nullptr},
+                                  Shape{B, C, H}, dtype, StageTable{stage_index, stage_frac},
+                                  Workspace{workspace, workspace_bytes}, stream);
 }
 
 // ... and with the gradient w.r.t. the control's coefficient tensor (`grad_coeffs`: layout of `coeffs`, ZEROED by the caller,
@@ -570,45 +430,44 @@ extern "C" int cde_rk4_backprop_linear_dcontrol(const void* coeffs, const void* 
                                                 const void* stage_frac, void* workspace, size_t workspace_bytes,
                                                 void* stream) {
   if (!grad_coeffs) return CDE_ERR_NULL;
-  return rk4_backprop_linear_impl(coeffs, knots, n_intervals, degree, W, bias, act, stages, grad_out, n_out, step_dt, n_steps,
-                                  node_ptr, node_out, node_weight, grad_z0, grad_W, grad_b, grad_coeffs, B, C, H, dtype,
-                                  stage_index, stage_frac, workspace, workspace_bytes, stream);
+  return rk4_backprop_linear_impl(Control{coeffs, knots, n_intervals, degree}, AffineField{W, bias, act},
+                                  BackpropIO{stages, grad_out, n_out, step_dt, n_steps, node_ptr, node_out, node_weight,
+                                             grad_z0, grad_W, grad_b, grad_coeffs},
+                                  Shape{B, C, H}, dtype, StageTable{stage_index, stage_frac},
+                                  Workspace{workspace, workspace_bytes}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- K3m
 // workspace: [stage_index: 4*(n_sgrid-1) int64][stage_frac: 4*(n_sgrid-1) f32][weight images]
-static inline size_t mlp_ws_frac_offset(int64_t n_steps) { return cde::align256((size_t)(4 * n_steps) * sizeof(int64_t)); }
-static inline size_t mlp_ws_image_offset(int64_t n_steps) {
-  return mlp_ws_frac_offset(n_steps) + cde::align256((size_t)(4 * n_steps) * sizeof(float));
+extern "C" size_t cde_rk4_adjoint_mlp_workspace_bytes(int64_t n_sgrid) {
+  return StageWorkspace(n_sgrid, sizeof(float)).total(align256(mlp_adjoint_image_bytes()));
 }
 
-extern "C" size_t cde_rk4_adjoint_mlp_workspace_bytes(int64_t n_sgrid) {
-  const int64_t n_steps = n_sgrid > 1 ? n_sgrid - 1 : 0;
-  return mlp_ws_image_offset(n_steps) + cde::align256(cde::mlp_adjoint_image_bytes());
+// the stage table of `grid` (`negate`: the reversed grid of the continuous adjoint) and the weight images, once per solve
+static int mlp_prepare_impl(int negate, const Control& x, const void* grid, int64_t n_grid, const TwoLayerField& f,
+                            const Shape& n, Dtypes d, Workspace ws, void* stream) {
+  if (n.C < 1 || n.H < 1 || f.width < 1 || x.n_intervals < 1 || n_grid < 0) return CDE_ERR_SHAPE;
+  if (d.state != CDE_F32) return d.state == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
+  if (!mlp_shape_ok(n.C, n.H, f.width) && !mlp_shape_upper(n.C, n.H, f.width)) return CDE_ERR_UNSUPPORTED;
+  if (!x.knots || !f.W1 || !f.bias1 || !f.W2 || !f.bias2 || !ws.base || (n_grid > 1 && !grid)) return CDE_ERR_NULL;
+  if (ws.bytes < cde_rk4_adjoint_mlp_workspace_bytes(n_grid)) return CDE_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const StageWorkspace layout(n_grid, sizeof(float));
+  const int rc = with_type(d.time, [&](auto tt) {
+    return fill_stage_table<float, typename decltype(tt)::type>(x, grid, layout.n_steps, negate, CDE_METHOD_RK4,
+                                                                layout.table(ws.base), s);
+  });
+  if (rc != CDE_OK) return rc;
+  return launch_mlp_adjoint_images(f.W1, f.bias1, f.width, f.W2, f.bias2, n.C, n.H, (float*)layout.tail(ws.base), s);
 }
 
 extern "C" int cde_rk4_adjoint_mlp_prepare(const void* knots, int64_t n_intervals, const void* sgrid, int64_t n_sgrid,
                                            const void* W1, const void* bias1, int64_t width, const void* W2,
                                            const void* bias2, int64_t C, int64_t H, int dtype, int time_dtype,
                                            void* workspace, size_t workspace_bytes, void* stream) {
-  if (C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_sgrid < 0) return CDE_ERR_SHAPE;
-  if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
-  if (!cde::mlp_shape_ok(C, H, width) && !cde::mlp_shape_upper(C, H, width)) return CDE_ERR_UNSUPPORTED;
-  if (!knots || !W1 || !bias1 || !W2 || !bias2 || !workspace || (n_sgrid > 1 && !sgrid)) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_rk4_adjoint_mlp_workspace_bytes(n_sgrid)) return CDE_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t n_steps = n_sgrid > 1 ? n_sgrid - 1 : 0;
-  unsigned char* base = (unsigned char*)workspace;
-  int rc;
-  if (time_dtype == CDE_F32)
-    rc = cde::fill_stage_table<float, float>(knots, n_intervals, sgrid, n_steps, 1, (int64_t*)base,
-                                             base + mlp_ws_frac_offset(n_steps), s);
-  else if (time_dtype == CDE_F64)
-    rc = cde::fill_stage_table<float, double>(knots, n_intervals, sgrid, n_steps, 1, (int64_t*)base,
-                                              base + mlp_ws_frac_offset(n_steps), s);
-  else return CDE_ERR_DTYPE;
-  if (rc != CDE_OK) return rc;
-  return cde::launch_mlp_adjoint_images(W1, bias1, width, W2, bias2, C, H, (float*)(base + mlp_ws_image_offset(n_steps)), s);
+  return mlp_prepare_impl(1, Control{nullptr, knots, n_intervals, 0}, sgrid, n_sgrid,
+                          TwoLayerField{W1, bias1, width, W2, bias2, CDE_ACT_NONE}, Shape{0, C, H}, Dtypes{dtype, time_dtype},
+                          Workspace{workspace, workspace_bytes}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- K3m, reverse mode (adjoint=False)
@@ -623,71 +482,47 @@ extern "C" int cde_rk4_forward_mlp_stages(const void* coeffs, const void* knots,
   if (B == 0) return CDE_OK;
   if (!coeffs || !knots || !W1 || !bias1 || !W2 || !bias2 || !z0 || !grid || !t_out || !z_out) return CDE_ERR_NULL;
   if (n_grid > 1 && (!stage_index || !stage_frac || !stages)) return CDE_ERR_NULL;
+  const Control x{coeffs, knots, n_intervals, degree};
+  const TwoLayerField f{W1, bias1, width, W2, bias2, act};
+  const ForwardIO io{z0, grid, n_grid, t_out, n_out, z_out, stages};
+  const Shape n{B, C, H};
+  const StageBuffers st{stage_index, stage_frac};
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (time_dtype == CDE_F32) {
-    rc = cde::fill_stage_table<float, float>(knots, n_intervals, grid, n_grid - 1, 0, stage_index, stage_frac, s);
-    if (rc != CDE_OK) return rc;
-    return cde::launch_forward_mlp_stages<float>(coeffs, knots, n_intervals, degree, W1, bias1, width, W2, bias2, act, z0,
-                                                 grid, n_grid, t_out, n_out, z_out, stages, B, C, H, stage_index, stage_frac, s);
-  }
-  if (time_dtype == CDE_F64) {
-    rc = cde::fill_stage_table<float, double>(knots, n_intervals, grid, n_grid - 1, 0, stage_index, stage_frac, s);
-    if (rc != CDE_OK) return rc;
-    return cde::launch_forward_mlp_stages<double>(coeffs, knots, n_intervals, degree, W1, bias1, width, W2, bias2, act, z0,
-                                                  grid, n_grid, t_out, n_out, z_out, stages, B, C, H, stage_index, stage_frac, s);
-  }
-  return CDE_ERR_DTYPE;
+  return forward_solve(Dtypes{dtype, time_dtype}, x, io, CDE_METHOD_RK4, st, s, [&](auto, auto tt) {
+    return launch_forward_mlp_stages<typename decltype(tt)::type>(x, f, io, n, st, s);
+  });
 }
 
 extern "C" int cde_rk4_backprop_mlp_prepare(const void* knots, int64_t n_intervals, const void* grid, int64_t n_grid,
                                             const void* W1, const void* bias1, int64_t width, const void* W2,
                                             const void* bias2, int64_t C, int64_t H, int dtype, int time_dtype,
                                             void* workspace, size_t workspace_bytes, void* stream) {
-  if (C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_grid < 0) return CDE_ERR_SHAPE;
-  if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
-  if (!cde::mlp_shape_ok(C, H, width) && !cde::mlp_shape_upper(C, H, width)) return CDE_ERR_UNSUPPORTED;
-  if (!knots || !W1 || !bias1 || !W2 || !bias2 || !workspace || (n_grid > 1 && !grid)) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_rk4_adjoint_mlp_workspace_bytes(n_grid)) return CDE_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t n_steps = n_grid > 1 ? n_grid - 1 : 0;
-  unsigned char* base = (unsigned char*)workspace;
-  int rc;
-  if (time_dtype == CDE_F32)
-    rc = cde::fill_stage_table<float, float>(knots, n_intervals, grid, n_steps, 0, (int64_t*)base,
-                                             base + mlp_ws_frac_offset(n_steps), s);
-  else if (time_dtype == CDE_F64)
-    rc = cde::fill_stage_table<float, double>(knots, n_intervals, grid, n_steps, 0, (int64_t*)base,
-                                              base + mlp_ws_frac_offset(n_steps), s);
-  else return CDE_ERR_DTYPE;
-  if (rc != CDE_OK) return rc;
-  return cde::launch_mlp_adjoint_images(W1, bias1, width, W2, bias2, C, H, (float*)(base + mlp_ws_image_offset(n_steps)), s);
+  return mlp_prepare_impl(0, Control{nullptr, knots, n_intervals, 0}, grid, n_grid,
+                          TwoLayerField{W1, bias1, width, W2, bias2, CDE_ACT_NONE}, Shape{0, C, H}, Dtypes{dtype, time_dtype},
+                          Workspace{workspace, workspace_bytes}, stream);
 }
 
-static int rk4_backprop_mlp_sweep_impl(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
-                                          const void* stages, void* g_state, const void* grid, int64_t n_grid,
-                                          int64_t k_begin, int64_t k_end, void* U, void* G2, void* G1, void* Z,
-                                          void* grad_coeffs, int64_t B,
-                                          int64_t C, int64_t H, int dtype, int time_dtype, const void* workspace,
-                                          size_t workspace_bytes, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || n_intervals < 1 || k_begin < 0 || k_end < k_begin || k_end > n_grid - 1) return CDE_ERR_SHAPE;
-  if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
-  if (!cde::mlp_shape_ok(C, H, 1) && !cde::mlp_shape_upper(C, H, 1)) return CDE_ERR_UNSUPPORTED;
-  if (!coeffs || !knots || !stages || !g_state || !grid || !U || !G2 || !G1 || !Z || !workspace) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_rk4_adjoint_mlp_workspace_bytes(n_grid)) return CDE_ERR_WORKSPACE;
-  const int64_t n_steps = n_grid - 1;
-  const unsigned char* base = (const unsigned char*)workspace;
-  const int64_t* stage_index = (const int64_t*)base;
-  const void* stage_frac = base + mlp_ws_frac_offset(n_steps);
-  const float* img = (const float*)(base + mlp_ws_image_offset(n_steps));
-  hipStream_t s = (hipStream_t)stream;
-  if (time_dtype == CDE_F32)
-    return cde::launch_mlp_backprop_sweep<float>(coeffs, knots, n_intervals, degree, act, img, stages, n_steps, g_state, grid,
-                                                 k_begin, k_end, stage_index, stage_frac, U, G2, G1, Z, B, C, H, grad_coeffs, s);
-  if (time_dtype == CDE_F64)
-    return cde::launch_mlp_backprop_sweep<double>(coeffs, knots, n_intervals, degree, act, img, stages, n_steps, g_state, grid,
-                                                  k_begin, k_end, stage_index, stage_frac, U, G2, G1, Z, B, C, H, grad_coeffs, s);
-  return CDE_ERR_DTYPE;
+// One chunk of a two-layer sweep over the table and images its *_prepare call left in `ws`.  `io` arrives without its image;
+// `backprop`: the reverse-mode sweep over the stored stages, else the continuous adjoint.
+static int mlp_sweep_impl(bool backprop, const Control& x, SweepIO io, int64_t n_grid, const Shape& n, Dtypes d, Workspace ws,
+                          void* stream) {
+  if (n.B < 1 || n.C < 1 || n.H < 1 || x.n_intervals < 1 || io.k_begin < 0 || io.k_end < io.k_begin || io.k_end > n_grid - 1)
+    return CDE_ERR_SHAPE;
+  if (d.state != CDE_F32) return d.state == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
+  if (!mlp_shape_ok(n.C, n.H, 1) && !mlp_shape_upper(n.C, n.H, 1)) return CDE_ERR_UNSUPPORTED;
+  if (!x.coeffs || !x.knots || !(backprop ? io.stages : io.y_state) || !io.a_state || !io.grid || !io.U || !io.G2 || !io.G1 ||
+      !io.Z || !ws.base)
+    return CDE_ERR_NULL;
+  if (ws.bytes < cde_rk4_adjoint_mlp_workspace_bytes(n_grid)) return CDE_ERR_WORKSPACE;
+  const StageWorkspace layout(n_grid, sizeof(float));
+  const StageTable st = layout.table(ws.base);
+  io.image = (const float*)layout.tail(ws.base);
+  io.n_steps = n_grid - 1;
+  return with_type(d.time, [&](auto tt) {
+    using TT = typename decltype(tt)::type;
+    return backprop ? launch_mlp_backprop_sweep<TT>(x, io, n, st, (hipStream_t)stream)
+                    : launch_mlp_adjoint_sweep<TT>(x, io, n, st, (hipStream_t)stream);
+  });
 }
 
 extern "C" int cde_rk4_backprop_mlp_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
@@ -695,8 +530,9 @@ extern "C" int cde_rk4_backprop_mlp_sweep(const void* coeffs, const void* knots,
                                           int64_t k_begin, int64_t k_end, void* U, void* G2, void* G1, void* Z, int64_t B,
                                           int64_t C, int64_t H, int dtype, int time_dtype, const void* workspace,
                                           size_t workspace_bytes, void* stream) {
-  return rk4_backprop_mlp_sweep_impl(coeffs, knots, n_intervals, degree, act, stages, g_state, grid, n_grid, k_begin, k_end, U,
-                                     G2, G1, Z, nullptr, B, C, H, dtype, time_dtype, workspace, workspace_bytes, stream);
+  return mlp_sweep_impl(true, Control{coeffs, knots, n_intervals, degree},
+                        SweepIO{nullptr, act, nullptr, g_state, stages, 0, grid, k_begin, k_end, U, G2, G1, Z, nullptr}, n_grid,
+                        Shape{B, C, H}, Dtypes{dtype, time_dtype}, Workspace{(void*)workspace, workspace_bytes}, stream);
 }
 
 // ... and with the gradient w.r.t. the control's coefficient tensor (`grad_coeffs` zeroed by the caller before the first chunk,
@@ -708,8 +544,9 @@ extern "C" int cde_rk4_backprop_mlp_sweep_dcontrol(const void* coeffs, const voi
                                                    int time_dtype, const void* workspace, size_t workspace_bytes,
                                                    void* stream) {
   if (!grad_coeffs) return CDE_ERR_NULL;
-  return rk4_backprop_mlp_sweep_impl(coeffs, knots, n_intervals, degree, act, stages, g_state, grid, n_grid, k_begin, k_end, U,
-                                     G2, G1, Z, grad_coeffs, B, C, H, dtype, time_dtype, workspace, workspace_bytes, stream);
+  return mlp_sweep_impl(true, Control{coeffs, knots, n_intervals, degree},
+                        SweepIO{nullptr, act, nullptr, g_state, stages, 0, grid, k_begin, k_end, U, G2, G1, Z, grad_coeffs},
+                        n_grid, Shape{B, C, H}, Dtypes{dtype, time_dtype}, Workspace{(void*)workspace, workspace_bytes}, stream);
 }
 
 extern "C" int cde_rk4_adjoint_mlp_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
@@ -717,24 +554,7 @@ extern "C" int cde_rk4_adjoint_mlp_sweep(const void* coeffs, const void* knots, 
                                          int64_t k_begin, int64_t k_end, void* U, void* G2, void* G1, void* Z,
                                          void* grad_coeffs, int64_t B, int64_t C, int64_t H, int dtype, int time_dtype,
                                          const void* workspace, size_t workspace_bytes, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || n_intervals < 1 || k_begin < 0 || k_end < k_begin || k_end > n_sgrid - 1) return CDE_ERR_SHAPE;
-  if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
-  if (!cde::mlp_shape_ok(C, H, 1) && !cde::mlp_shape_upper(C, H, 1)) return CDE_ERR_UNSUPPORTED;
-  if (!coeffs || !knots || !y_state || !a_state || !sgrid || !U || !G2 || !G1 || !Z || !workspace) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_rk4_adjoint_mlp_workspace_bytes(n_sgrid)) return CDE_ERR_WORKSPACE;
-  const int64_t n_steps = n_sgrid - 1;
-  const unsigned char* base = (const unsigned char*)workspace;
-  const int64_t* stage_index = (const int64_t*)base;
-  const void* stage_frac = base + mlp_ws_frac_offset(n_steps);
-  const float* img = (const float*)(base + mlp_ws_image_offset(n_steps));
-  hipStream_t s = (hipStream_t)stream;
-  if (time_dtype == CDE_F32)
-    return cde::launch_mlp_adjoint_sweep<float>(coeffs, knots, n_intervals, degree, act, img, y_state, a_state, sgrid,
-                                                k_begin, k_end, stage_index, stage_frac, U, G2, G1, Z, B, C, H,
-                                                grad_coeffs, s);
-  if (time_dtype == CDE_F64)
-    return cde::launch_mlp_adjoint_sweep<double>(coeffs, knots, n_intervals, degree, act, img, y_state, a_state, sgrid,
-                                                 k_begin, k_end, stage_index, stage_frac, U, G2, G1, Z, B, C, H,
-                                                grad_coeffs, s);
-  return CDE_ERR_DTYPE;
+  return mlp_sweep_impl(false, Control{coeffs, knots, n_intervals, degree},
+                        SweepIO{nullptr, act, y_state, a_state, nullptr, 0, sgrid, k_begin, k_end, U, G2, G1, Z, grad_coeffs},
+                        n_sgrid, Shape{B, C, H}, Dtypes{dtype, time_dtype}, Workspace{(void*)workspace, workspace_bytes}, stream);
 }

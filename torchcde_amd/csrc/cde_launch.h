@@ -1,0 +1,169 @@
+// cde_launch.h -- host side of the fixed-grid solvers (rk4 / midpoint / euler): the argument structs the launchers take,
+// the prototype of every launcher and helper that crosses a translation unit, and the degree / activation dispatch.
+// Host declarations only; api.hip fills the structs where the C ABI's pointers enter, the rk4_*.hip files define the launchers.
+#pragma once
+#include <type_traits>
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/cde_mi355x.h"
+
+namespace cde {
+
+// ---------------------------------------------------------------- what always travels together
+struct Control { const void* coeffs; const void* knots; int64_t n_intervals; int degree; };
+struct AffineField { const void* W; const void* bias; int act; };
+struct TwoLayerField { const void* W1; const void* bias1; int64_t width; const void* W2; const void* bias2; int act; };
+struct Shape { int64_t B, C, H; };
+// control interval and fractional part at every stage time (api.hip: stage_table_kernel), four slots per step
+struct StageTable { const int64_t* index; const void* frac; };
+// `stages`: where the kernels of adjoint=False store their stage states (null otherwise)
+struct ForwardIO { const void* z0; const void* grid; int64_t n_grid; const void* t_out; int64_t n_out; void* z_out; void* stages; };
+// `seg_off_host`: the host copy of `seg_off` (the wide kernels' chunk loop); `grad_coeffs`: null without control gradients
+struct AdjointIO {
+  const void* z_saved; const void* grad_out; const void* sgrid; int64_t n_sgrid;
+  const int64_t* seg_off; const int64_t* seg_off_host; int64_t n_out;
+  void* grad_z0; void* grad_W; void* grad_b; void* grad_coeffs;
+};
+// reverse mode through the stored stage states of the affine field (adjoint=False)
+struct BackpropIO {
+  const void* stages; const void* grad_out; int64_t n_out;
+  const float* step_dt; int64_t n_steps; const int64_t* node_ptr; const int64_t* node_out; const float* node_weight;
+  void* grad_z0; void* grad_W; void* grad_b; void* grad_coeffs;
+};
+// steps [k_begin, k_end) of a two-layer sweep.  Continuous adjoint: `y_state`, `a_state` over `grid` = the reversed grid;
+// reverse mode: `a_state` alone (the running gradient) over the forward grid, with the `stages` of all `n_steps` steps.
+struct SweepIO {
+  const float* image; int act;
+  void* y_state; void* a_state; const void* stages; int64_t n_steps;
+  const void* grid; int64_t k_begin, k_end;
+  void* U; void* G2; void* G1; void* Z; void* grad_coeffs;
+};
+// K3p's form: the solver's stage count and whether the J rows run on the bf16 pipe (rk4 only)
+enum class PairRows { f32, bf16 };
+struct PairForm { int method; PairRows rows; };
+
+static inline const float* f32(const void* p) { return (const float*)p; }
+static inline float* f32(void* p) { return (float*)p; }
+
+// ---------------------------------------------------------------- degree / activation as compile-time constants
+// `f(std::integral_constant<int, V>{})` for the run-time value; CDE_ERR_UNSUPPORTED for any other.  `f` launches and
+// returns a code, so each launcher names its kernel's arguments once.
+template <int V> using Const = std::integral_constant<int, V>;
+template <typename F>
+int dispatch_degree(int degree, F&& f) {
+  if (degree == CDE_PATH_CUBIC) return f(Const<CDE_PATH_CUBIC>{});
+  if (degree == CDE_PATH_LINEAR) return f(Const<CDE_PATH_LINEAR>{});
+  return CDE_ERR_UNSUPPORTED;
+}
+template <typename F>
+int dispatch_act(int act, F&& f) {
+  if (act == CDE_ACT_NONE) return f(Const<CDE_ACT_NONE>{});
+  if (act == CDE_ACT_TANH) return f(Const<CDE_ACT_TANH>{});
+  return CDE_ERR_UNSUPPORTED;
+}
+template <typename F>
+int dispatch_degree_act(int degree, int act, F&& f) {
+  return dispatch_degree(degree, [&](auto D) { return dispatch_act(act, [&](auto A) { return f(D, A); }); });
+}
+// `kernel`'s dynamic LDS limit, raised to what the launch asks for
+template <typename K>
+void allow_lds(K kernel, size_t bytes) {
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+// ---------------------------------------------------------------- rk4_generic.hip (any shape, f32 / f64)
+bool generic_applicable(int64_t C, int64_t H, size_t elem, bool adjoint);
+size_t generic_adjoint_workspace_bytes(int64_t B, int64_t C, int64_t H, size_t elem);
+template <typename T, typename TT>
+int launch_forward_generic(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                           hipStream_t s);
+template <typename T, typename TT>
+int launch_adjoint_generic(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
+                           void* partial, hipStream_t s);
+
+// ---------------------------------------------------------------- rk4_mfma.hip (f32, H <= 32, C <= 8; the two-layer field)
+bool mfma_applicable(int64_t C, int64_t H, int dtype, int act);
+size_t mfma_adjoint_partial_bytes(int64_t B);
+bool mlp_shape_ok(int64_t C, int64_t H, int64_t width);        // (cde_mfma.h declares these three for the kernel files)
+bool mlp_shape_hi(int64_t C, int64_t H, int64_t width);
+bool mlp_shape_upper(int64_t C, int64_t H, int64_t width);
+// fixed-order sum of the per-tile partial parameter gradients
+int launch_reduce_partials(const float* partial, int64_t n_tiles, void* grad_W, void* grad_b, int H, int C, hipStream_t s);
+template <typename TT>
+int launch_forward_mfma(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                        hipStream_t s);
+template <typename TT>
+int launch_forward_mlp(const Control& x, const TwoLayerField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                       hipStream_t s);
+// ... storing the stage states (`io.stages`) for adjoint=False
+template <typename TT>
+int launch_forward_mfma_stages(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n,
+                               const StageTable& st, hipStream_t s);
+template <typename TT>
+int launch_forward_mlp_stages(const Control& x, const TwoLayerField& f, const ForwardIO& io, const Shape& n,
+                              const StageTable& st, hipStream_t s);
+// midpoint / euler (identity activation)
+template <typename TT>
+int launch_forward_mfma_method(int method, const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n,
+                               const StageTable& st, hipStream_t s);
+template <typename TT>
+int launch_adjoint_mfma(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
+                        float* partial, hipStream_t s);
+template <typename TT>
+int launch_adjoint_jacobian_bx(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n,
+                               const StageTable& st, float* partial, hipStream_t s);
+
+// ---------------------------------------------------------------- rk4_adjoint_pair.hip (chain wave + helper wave per tile)
+template <typename TT>
+int launch_adjoint_jacobian_pair(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n,
+                                 const StageTable& st, float* partial, hipStream_t s, PairForm form);
+int launch_backprop_jacobian_pair(const Control& x, const AffineField& f, const BackpropIO& io, const Shape& n,
+                                  const StageTable& st, float* partial, hipStream_t s);
+
+// ---------------------------------------------------------------- rk4_backprop.hip (adjoint=False of the affine field)
+size_t backprop_workspace_bytes(int64_t B);
+int launch_backprop_jacobian(const Control& x, const AffineField& f, const BackpropIO& io, const Shape& n, const StageTable& st,
+                             float* partial, hipStream_t s);
+
+// ---------------------------------------------------------------- rk4_bf16x3.hip (exact operand splits on the bf16 pipe)
+template <typename TT>
+int launch_forward_bf16x3(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                          hipStream_t s);
+template <typename TT>
+int launch_adjoint_bf16x3(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
+                          float* partial, hipStream_t s);
+
+// ---------------------------------------------------------------- rk4_split.hip (one workgroup per 16 series: small batches)
+size_t split_adjoint_partial_bytes(int64_t B);
+template <typename TT>
+int launch_forward_split(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                         hipStream_t s);
+template <typename TT>
+int launch_adjoint_split(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
+                         float* partial, hipStream_t s);
+
+// ---------------------------------------------------------------- rk4_wide.hip (H <= 64, C <= 8 or H <= 32, C <= 16)
+bool wide_applicable(int64_t C, int64_t H, int dtype, int act);
+size_t wide_adjoint_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t n_steps);
+template <typename TT>
+int launch_forward_wide(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                        hipStream_t s);
+template <typename TT>
+int launch_adjoint_wide(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
+                        void* scratch, hipStream_t s);
+// mlp_grad_reduce.hip: acc (M, N + 1) += G^T [Z | 1] over `rows` rows, G (rows, M), Z (rows, N)
+size_t wide_grad_reduce_partial_bytes(int M, int N);
+int launch_wide_grad_reduce(const float* G, const float* Z, int64_t rows, int M, int N, float* acc, float* partial,
+                            hipStream_t s);
+
+// ---------------------------------------------------------------- rk4_mlp_adjoint.hip (sweeps of the two-layer field)
+size_t mlp_adjoint_image_bytes();                              // (cde_mlp_adj.h declares these two for the kernel files)
+int launch_mlp_adjoint_images(const void* W1, const void* b1, int64_t width, const void* W2, const void* b2, int64_t C,
+                              int64_t H, float* img, hipStream_t s);
+template <typename TT>
+int launch_mlp_adjoint_sweep(const Control& x, const SweepIO& io, const Shape& n, const StageTable& st, hipStream_t s);
+template <typename TT>
+int launch_mlp_backprop_sweep(const Control& x, const SweepIO& io, const Shape& n, const StageTable& st, hipStream_t s);
+
+}  // namespace cde

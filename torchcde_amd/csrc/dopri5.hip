@@ -18,6 +18,7 @@
 // only queues launches and looks at a done flag every few dozen of them.
 #include "cde_dopri.h"
 #include "cde_split.h"
+#include "cde_launch.h"
 
 namespace cde {
 
@@ -1070,7 +1071,6 @@ static inline bool dopri_use_mfma(int64_t C, int64_t H, int dtype, int act, int 
   return variant != CDE_VARIANT_GENERIC && dtype == CDE_F32 && H <= MH && C <= MC &&
          (act == CDE_ACT_NONE || act == CDE_ACT_TANH);
 }
-bool wide_applicable(int64_t C, int64_t H, int dtype, int act);         // rk4_wide.hip
 // one-layer fields beyond the 32 x 8 tiles (H <= 64, C <= 8 or H <= 32, C <= 16): the wide attempt kernel under AUTO
 static inline bool dopri_use_wide(int64_t C, int64_t H, int dtype, int act, int variant) {
   return variant == CDE_VARIANT_AUTO && !dopri_use_mfma(C, H, dtype, act, variant) && wide_applicable(C, H, dtype, act);

@@ -16,6 +16,7 @@
 //     kernel adds the partials in slab order into the caller's accumulator -- deterministic, no atomics.
 #include "cde_mfma.h"
 #include "cde_dopri_adj.h"
+#include "cde_launch.h"
 
 namespace cde {
 

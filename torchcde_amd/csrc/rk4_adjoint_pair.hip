@@ -30,10 +30,9 @@
 // Arithmetic: K3j's, operation for operation (same rows, same consume order, same transposes, same dL/dW K order), so
 // results are bitwise K3j's; the per-wave partials keep K3j's layout and go through reduce_mfma_partials.
 #include "cde_mfma.h"
+#include "cde_launch.h"
 
 namespace cde {
-
-int launch_reduce_partials(const float* partial, int64_t n_tiles, void* grad_W, void* grad_b, int H, int C, hipStream_t s);
 
 namespace {
 
@@ -801,41 +800,29 @@ __global__ __launch_bounds__(512, 2) void rk4_backprop_jacobian_pair(
 }  // namespace
 
 // K3d's pair form (identity activation); CDE_K3D_WAVES=1 keeps the one-wave kernel of rk4_backprop.hip
-int launch_backprop_jacobian_pair(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                                  const void* stages, const void* grad_out, int64_t n_out, const float* step_dt,
-                                  int64_t n_steps, const int64_t* node_ptr, const int64_t* node_out, const float* node_weight,
-                                  void* grad_z0, void* grad_W, void* grad_b, int64_t B, int64_t C, int64_t H,
-                                  const int64_t* stage_index, const float* stage_frac, float* partial, hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 127) / 128);
+int launch_backprop_jacobian_pair(const Control& x, const AffineField& f, const BackpropIO& io, const Shape& n,
+                                  const StageTable& st, float* partial, hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 127) / 128);
   const size_t lds = (size_t)KP_LDS_FLOATS * sizeof(float);
-#define CDE_BPP(D)                                                                                                   \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)rk4_backprop_jacobian_pair<D>, hipFuncAttributeMaxDynamicSharedMemorySize,\
-                              (int)lds);                                                                             \
-    rk4_backprop_jacobian_pair<D><<<blocks, 512, lds, s>>>(                                                          \
-        (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)stages,               \
-        (const float*)grad_out, n_out, step_dt, n_steps, node_ptr, node_out, node_weight, (float*)grad_z0, partial,  \
-        B, stage_index, stage_frac, dims);                                                                           \
-  } while (0)
-  if (degree == CDE_PATH_CUBIC) CDE_BPP(CDE_PATH_CUBIC);
-  else if (degree == CDE_PATH_LINEAR) CDE_BPP(CDE_PATH_LINEAR);
-  else return CDE_ERR_UNSUPPORTED;
-#undef CDE_BPP
-  const int rc = check_launch();
+  int rc = dispatch_degree(x.degree, [&](auto D) {
+    allow_lds(rk4_backprop_jacobian_pair<D()>, lds);
+    rk4_backprop_jacobian_pair<D()><<<blocks, 512, lds, s>>>(
+        f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(io.stages), f32(io.grad_out), io.n_out, io.step_dt,
+        io.n_steps, io.node_ptr, io.node_out, io.node_weight, f32(io.grad_z0), partial, n.B, st.index, f32(st.frac), dims);
+    return CDE_OK;
+  });
+  if (rc == CDE_OK) rc = check_launch();
   if (rc != CDE_OK) return rc;
-  return launch_reduce_partials(partial, (B + 31) / 32, grad_W, grad_b, (int)H, (int)C, s);
+  return launch_reduce_partials(partial, (n.B + 31) / 32, io.grad_W, io.grad_b, (int)n.H, (int)n.C, s);
 }
 
-
 template <typename TT>
-int launch_adjoint_jacobian_pair(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                                 const void* bias, const void* z_saved, const void* grad_out, const void* sgrid,
-                                 const int64_t* seg_off, int64_t n_out, void* grad_z0, void* grad_W, void* grad_b, int64_t B,
-                                 int64_t C, int64_t H, const int64_t* stage_index, const void* stage_frac, float* partial,
-                                 hipStream_t s, int method, bool bx) {
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 127) / 128);
+int launch_adjoint_jacobian_pair(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n,
+                                 const StageTable& st, float* partial, hipStream_t s, PairForm form) {
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 127) / 128);
+  const bool bx = form.rows == PairRows::bf16;
   const size_t lds = (size_t)(bx ? KP_LDS_FLOATS_BX : KP_LDS_FLOATS) * sizeof(float);
   // bit 0: priority 3 for the chain waves, bit 1: for the helper waves (the trace build reads CDE_K3P_FLAGS once: experiments)
 #ifdef CDE_PHASE_TRACE
@@ -843,41 +830,26 @@ int launch_adjoint_jacobian_pair(const void* coeffs, const void* knots, int64_t 
 #else
   constexpr int flags = 1;
 #endif
-#define CDE_ADJ_P(D, M, X)                                                                                           \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)rk4_adjoint_jacobian_pair<TT, D, M, X>,                                   \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-    rk4_adjoint_jacobian_pair<TT, D, M, X><<<blocks, 512, lds, s>>>(                                                 \
-        (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias,                 \
-        (const float*)z_saved, (const float*)grad_out, (const TT*)sgrid, seg_off, n_out, (float*)grad_z0, partial,   \
-        B, stage_index, (const float*)stage_frac, dims, flags);                                                      \
-  } while (0)
-#define CDE_ADJ_PD(M)                                                                                                \
-  do {                                                                                                               \
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ_P(CDE_PATH_CUBIC, M, false); else CDE_ADJ_P(CDE_PATH_LINEAR, M, false);     \
-  } while (0)
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (bx && method != CDE_METHOD_RK4) return CDE_ERR_UNSUPPORTED;
-  if (bx) {
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ_P(CDE_PATH_CUBIC, CDE_METHOD_RK4, true);
-    else CDE_ADJ_P(CDE_PATH_LINEAR, CDE_METHOD_RK4, true);
-  } else if (method == CDE_METHOD_RK4) CDE_ADJ_PD(CDE_METHOD_RK4);
-  else if (method == CDE_METHOD_MIDPOINT) CDE_ADJ_PD(CDE_METHOD_MIDPOINT);
-  else if (method == CDE_METHOD_EULER) CDE_ADJ_PD(CDE_METHOD_EULER);
-  else return CDE_ERR_UNSUPPORTED;
-#undef CDE_ADJ_PD
-#undef CDE_ADJ_P
-  const int rc = check_launch();
+  if (bx && form.method != CDE_METHOD_RK4) return CDE_ERR_UNSUPPORTED;
+  int rc = dispatch_degree(x.degree, [&](auto D) -> int {
+    auto launch = [&](auto M, auto X) {
+      allow_lds(rk4_adjoint_jacobian_pair<TT, D(), M(), X()>, lds);
+      rk4_adjoint_jacobian_pair<TT, D(), M(), X()><<<blocks, 512, lds, s>>>(
+          f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(f.bias), f32(io.z_saved), f32(io.grad_out),
+          (const TT*)io.sgrid, io.seg_off, io.n_out, f32(io.grad_z0), partial, n.B, st.index, f32(st.frac), dims, flags);
+      return CDE_OK;
+    };
+    if (bx) return launch(Const<CDE_METHOD_RK4>{}, std::true_type{});           // (the bf16 rows: rk4 only)
+    if (form.method == CDE_METHOD_RK4) return launch(Const<CDE_METHOD_RK4>{}, std::false_type{});
+    if (form.method == CDE_METHOD_MIDPOINT) return launch(Const<CDE_METHOD_MIDPOINT>{}, std::false_type{});
+    if (form.method == CDE_METHOD_EULER) return launch(Const<CDE_METHOD_EULER>{}, std::false_type{});
+    return CDE_ERR_UNSUPPORTED;
+  });
+  if (rc == CDE_OK) rc = check_launch();
   if (rc != CDE_OK) return rc;
-  return launch_reduce_partials(partial, (B + 31) / 32, grad_W, grad_b, (int)H, (int)C, s);
+  return launch_reduce_partials(partial, (n.B + 31) / 32, io.grad_W, io.grad_b, (int)n.H, (int)n.C, s);
 }
-template int launch_adjoint_jacobian_pair<float>(const void*, const void*, int64_t, int, const void*, const void*, const void*,
-                                                 const void*, const void*, const int64_t*, int64_t, void*, void*, void*,
-                                                 int64_t, int64_t, int64_t, const int64_t*, const void*, float*, hipStream_t, int,
-                                                 bool);
-template int launch_adjoint_jacobian_pair<double>(const void*, const void*, int64_t, int, const void*, const void*, const void*,
-                                                  const void*, const void*, const int64_t*, int64_t, void*, void*, void*,
-                                                  int64_t, int64_t, int64_t, const int64_t*, const void*, float*, hipStream_t, int,
-                                                 bool);
+template int launch_adjoint_jacobian_pair<float>(const Control&, const AffineField&, const AdjointIO&, const Shape&, const StageTable&, float*, hipStream_t, PairForm);
+template int launch_adjoint_jacobian_pair<double>(const Control&, const AffineField&, const AdjointIO&, const Shape&, const StageTable&, float*, hipStream_t, PairForm);
 
 }  // namespace cde

@@ -31,15 +31,9 @@
 // lane's 16 values are four 16-byte loads.  Per-wave partial parameter gradients in K3j's layout, summed in tile order
 // by reduce_mfma_partials (run-to-run deterministic).
 #include "cde_mfma.h"
+#include "cde_launch.h"
 
 namespace cde {
-
-int launch_reduce_partials(const float* partial, int64_t n_tiles, void* grad_W, void* grad_b, int H, int C, hipStream_t s);
-size_t mfma_adjoint_partial_bytes(int64_t B);
-// rk4_adjoint_pair.hip: the same sweep as a chain wave + a helper wave per tile
-int launch_backprop_jacobian_pair(const void*, const void*, int64_t, int, const void*, const void*, const void*, int64_t,
-                                  const float*, int64_t, const int64_t*, const int64_t*, const float*, void*, void*, void*, int64_t,
-                                  int64_t, int64_t, const int64_t*, const float*, float*, hipStream_t);
 
 namespace {
 
@@ -593,64 +587,41 @@ __global__ __launch_bounds__(256, 1) void rk4_backprop_jacobian(
 
 size_t backprop_workspace_bytes(int64_t B) { return mfma_adjoint_partial_bytes(B); }
 
-int launch_backprop_jacobian(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                             const void* bias, int act, const void* stages, const void* grad_out, int64_t n_out,
-                             const float* step_dt, int64_t n_steps,
-                             const int64_t* node_ptr, const int64_t* node_out, const float* node_weight, void* grad_z0,
-                             void* grad_W, void* grad_b, int64_t B, int64_t C, int64_t H, const int64_t* stage_index,
-                             const float* stage_frac, float* partial, void* grad_coeffs, hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 127) / 128);
-  if (act != CDE_ACT_NONE && act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
-  if (act == CDE_ACT_TANH || grad_coeffs) {
-    const size_t lds_act = (size_t)BP_ACT_LDS_FLOATS * sizeof(float);
-#define CDE_BPA(D, A, X)                                                                                             \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)rk4_backprop_act<D, A, X>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                              (int)lds_act);                                                                         \
-    rk4_backprop_act<D, A, X><<<blocks, 256, lds_act, s>>>(                                                          \
-        (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias,                 \
-        (const float*)stages, (const float*)grad_out, n_out, step_dt, n_steps, node_ptr, node_out, node_weight,      \
-        (float*)grad_z0, partial, B, stage_index, stage_frac, dims, (float*)grad_coeffs);                            \
-  } while (0)
-#define CDE_BPA_D(D)                                                                                                 \
-  do {                                                                                                               \
-    if (grad_coeffs) { if (act == CDE_ACT_TANH) CDE_BPA(D, CDE_ACT_TANH, true); else CDE_BPA(D, CDE_ACT_NONE, true); } \
-    else CDE_BPA(D, CDE_ACT_TANH, false);                                                                            \
-  } while (0)
-    if (degree == CDE_PATH_CUBIC) CDE_BPA_D(CDE_PATH_CUBIC);
-    else if (degree == CDE_PATH_LINEAR) CDE_BPA_D(CDE_PATH_LINEAR);
-    else return CDE_ERR_UNSUPPORTED;
-#undef CDE_BPA_D
-#undef CDE_BPA
-    const int rca = check_launch();
-    if (rca != CDE_OK) return rca;
-    return launch_reduce_partials(partial, (B + 31) / 32, grad_W, grad_b, (int)H, (int)C, s);
-  }
-  {
+int launch_backprop_jacobian(const Control& x, const AffineField& f, const BackpropIO& io, const Shape& n, const StageTable& st,
+                             float* partial, hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 127) / 128);
+  if (f.act != CDE_ACT_NONE && f.act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
+  const bool pre_activation = f.act == CDE_ACT_TANH || io.grad_coeffs;
+  if (!pre_activation) {
     const int64_t e = option(CDE_OPT_K3D_WAVES);      // 1: this file's one-wave kernel, 2: the pair form (tests compare the two)
-    if (e ? e == 2 : K3D_PAIR_DEFAULT)
-      return launch_backprop_jacobian_pair(coeffs, knots, n_intervals, degree, W, stages, grad_out, n_out, step_dt, n_steps,
-                                           node_ptr, node_out, node_weight, grad_z0, grad_W, grad_b, B, C, H, stage_index,
-                                           stage_frac, partial, s);
+    if (e ? e == 2 : K3D_PAIR_DEFAULT) return launch_backprop_jacobian_pair(x, f, io, n, st, partial, s);
   }
-  const size_t lds = (size_t)(BP_WJ_FLOATS + 4 * SCR_FLOATS) * sizeof(float);
-#define CDE_BP(D)                                                                                                    \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)rk4_backprop_jacobian<D>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                              (int)lds);                                                                             \
-    rk4_backprop_jacobian<D><<<blocks, 256, lds, s>>>(                                                               \
-        (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)stages,               \
-        (const float*)grad_out, n_out, step_dt, n_steps, node_ptr, node_out, node_weight, (float*)grad_z0, partial,  \
-        B, stage_index, stage_frac, dims);                                                                           \
-  } while (0)
-  if (degree == CDE_PATH_CUBIC) CDE_BP(CDE_PATH_CUBIC);
-  else if (degree == CDE_PATH_LINEAR) CDE_BP(CDE_PATH_LINEAR);
-  else return CDE_ERR_UNSUPPORTED;
-#undef CDE_BP
-  const int rc = check_launch();
+  int rc = dispatch_degree(x.degree, [&](auto D) -> int {
+    if (!pre_activation) {
+      const size_t lds = (size_t)(BP_WJ_FLOATS + 4 * SCR_FLOATS) * sizeof(float);
+      allow_lds(rk4_backprop_jacobian<D()>, lds);
+      rk4_backprop_jacobian<D()><<<blocks, 256, lds, s>>>(
+          f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(io.stages), f32(io.grad_out), io.n_out, io.step_dt,
+          io.n_steps, io.node_ptr, io.node_out, io.node_weight, f32(io.grad_z0), partial, n.B, st.index, f32(st.frac), dims);
+      return CDE_OK;
+    }
+    auto act_kernel = [&](auto A, auto X) {
+      const size_t lds = (size_t)BP_ACT_LDS_FLOATS * sizeof(float);
+      allow_lds(rk4_backprop_act<D(), A(), X()>, lds);
+      rk4_backprop_act<D(), A(), X()><<<blocks, 256, lds, s>>>(
+          f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(f.bias), f32(io.stages), f32(io.grad_out), io.n_out,
+          io.step_dt, io.n_steps, io.node_ptr, io.node_out, io.node_weight, f32(io.grad_z0), partial, n.B, st.index,
+          f32(st.frac), dims, f32(io.grad_coeffs));
+      return CDE_OK;
+    };
+    if (!io.grad_coeffs) return act_kernel(Const<CDE_ACT_TANH>{}, std::false_type{});
+    if (f.act == CDE_ACT_TANH) return act_kernel(Const<CDE_ACT_TANH>{}, std::true_type{});
+    return act_kernel(Const<CDE_ACT_NONE>{}, std::true_type{});
+  });
+  if (rc == CDE_OK) rc = check_launch();
   if (rc != CDE_OK) return rc;
-  return launch_reduce_partials(partial, (B + 31) / 32, grad_W, grad_b, (int)H, (int)C, s);
+  return launch_reduce_partials(partial, (n.B + 31) / 32, io.grad_W, io.grad_b, (int)n.H, (int)n.C, s);
 }
 
 }  // namespace cde

@@ -25,6 +25,7 @@
 //       tile with all their channels: f_(2(2t)+half), f_(2(2t+1)+half) are two in-lane dot products with dX
 //   W_c^T tile (channel c), row rho = 8 g + 4 hf + e  <->  output unit 2 (4 g + e) + hf : D register r = output unit 2 r + half
 #include "cde_mfma.h"
+#include "cde_launch.h"
 
 namespace cde {
 
@@ -434,67 +435,43 @@ __global__ __launch_bounds__(256, 1) void rk4_adjoint_bf16x3(
 }
 
 // ------------------------------------------------------------------------------------------ host side
-int launch_reduce_partials(const float* partial, int64_t n_tiles, void* grad_W, void* grad_b, int H, int C, hipStream_t s);   // rk4_mfma.hip
-
 template <typename TT>
-int launch_forward_bf16x3(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                          const void* bias, const void* z0, const void* grid, int64_t n_grid, const void* t_out,
-                          int64_t n_out, void* z_out, int64_t B, int64_t C, int64_t H, const int64_t* stage_index,
-                          const void* stage_frac, hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 127) / 128);
-#define CDE_BX_FWD(D)                                                                                                \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)rk4_forward_bf16x3<TT, D>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                              BX_FWD_LDS_BYTES);                                                                     \
-    rk4_forward_bf16x3<TT, D><<<blocks, 256, BX_FWD_LDS_BYTES, s>>>(                                                 \
-        (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias, (const float*)z0, \
-        (const TT*)grid, n_grid, (const TT*)t_out, n_out, (float*)z_out, B, stage_index, (const float*)stage_frac, dims); \
-  } while (0)
-  if (degree == CDE_PATH_CUBIC) CDE_BX_FWD(CDE_PATH_CUBIC);
-  else if (degree == CDE_PATH_LINEAR) CDE_BX_FWD(CDE_PATH_LINEAR);
-  else return CDE_ERR_UNSUPPORTED;
-#undef CDE_BX_FWD
-  return check_launch();
-}
-
-template <typename TT>
-int launch_adjoint_bf16x3(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                          const void* bias, const void* z_saved, const void* grad_out, const void* sgrid,
-                          const int64_t* seg_off, int64_t n_out, void* grad_z0, void* grad_W, void* grad_b, int64_t B,
-                          int64_t C, int64_t H, const int64_t* stage_index, const void* stage_frac, float* partial,
+int launch_forward_bf16x3(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
                           hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 127) / 128);
-#define CDE_BX_ADJ(D)                                                                                                \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)rk4_adjoint_bf16x3<TT, D>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                              BX_ADJ_LDS_BYTES);                                                                     \
-    rk4_adjoint_bf16x3<TT, D><<<blocks, 256, BX_ADJ_LDS_BYTES, s>>>(                                                 \
-        (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias,                 \
-        (const float*)z_saved, (const float*)grad_out, (const TT*)sgrid, seg_off, n_out, (float*)grad_z0, partial, B, \
-        stage_index, (const float*)stage_frac, dims);                                                                \
-  } while (0)
-  if (degree == CDE_PATH_CUBIC) CDE_BX_ADJ(CDE_PATH_CUBIC);
-  else if (degree == CDE_PATH_LINEAR) CDE_BX_ADJ(CDE_PATH_LINEAR);
-  else return CDE_ERR_UNSUPPORTED;
-#undef CDE_BX_ADJ
-  const int rc = check_launch();
-  if (rc != CDE_OK) return rc;
-  return launch_reduce_partials(partial, (B + 31) / 32, grad_W, grad_b, (int)H, (int)C, s);
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 127) / 128);
+  const int rc = dispatch_degree(x.degree, [&](auto D) {
+    allow_lds(rk4_forward_bf16x3<TT, D()>, BX_FWD_LDS_BYTES);
+    rk4_forward_bf16x3<TT, D()><<<blocks, 256, BX_FWD_LDS_BYTES, s>>>(
+        f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(f.bias), f32(io.z0), (const TT*)io.grid, io.n_grid,
+        (const TT*)io.t_out, io.n_out, f32(io.z_out), n.B, st.index, f32(st.frac), dims);
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
 }
 
-template int launch_forward_bf16x3<float>(const void*, const void*, int64_t, int, const void*, const void*, const void*,
-                                          const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t, int64_t,
-                                          const int64_t*, const void*, hipStream_t);
-template int launch_forward_bf16x3<double>(const void*, const void*, int64_t, int, const void*, const void*, const void*,
-                                           const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t, int64_t,
-                                           const int64_t*, const void*, hipStream_t);
-template int launch_adjoint_bf16x3<float>(const void*, const void*, int64_t, int, const void*, const void*, const void*,
-                                          const void*, const void*, const int64_t*, int64_t, void*, void*, void*, int64_t,
-                                          int64_t, int64_t, const int64_t*, const void*, float*, hipStream_t);
-template int launch_adjoint_bf16x3<double>(const void*, const void*, int64_t, int, const void*, const void*, const void*,
-                                           const void*, const void*, const int64_t*, int64_t, void*, void*, void*, int64_t,
-                                           int64_t, int64_t, const int64_t*, const void*, float*, hipStream_t);
+template <typename TT>
+int launch_adjoint_bf16x3(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
+                          float* partial, hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 127) / 128);
+  int rc = dispatch_degree(x.degree, [&](auto D) {
+    allow_lds(rk4_adjoint_bf16x3<TT, D()>, BX_ADJ_LDS_BYTES);
+    rk4_adjoint_bf16x3<TT, D()><<<blocks, 256, BX_ADJ_LDS_BYTES, s>>>(
+        f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(f.bias), f32(io.z_saved), f32(io.grad_out),
+        (const TT*)io.sgrid, io.seg_off, io.n_out, f32(io.grad_z0), partial, n.B, st.index, f32(st.frac), dims);
+    return CDE_OK;
+  });
+  if (rc == CDE_OK) rc = check_launch();
+  if (rc != CDE_OK) return rc;
+  return launch_reduce_partials(partial, (n.B + 31) / 32, io.grad_W, io.grad_b, (int)n.H, (int)n.C, s);
+}
+
+#define CDE_INST(TT)                                                                                                  \
+  template int launch_forward_bf16x3<TT>(const Control&, const AffineField&, const ForwardIO&, const Shape&, const StageTable&, hipStream_t); \
+  template int launch_adjoint_bf16x3<TT>(const Control&, const AffineField&, const AdjointIO&, const Shape&, const StageTable&, float*, hipStream_t);
+CDE_INST(float)
+CDE_INST(double)
+#undef CDE_INST
 
 }  // namespace cde

@@ -10,6 +10,7 @@
 // Per stage the stage state and the control derivative are exchanged through LDS, every lane
 // forms its row of f(z) dX/dt with W streamed from L1/L2 (W is at most a few tens of KB).
 #include "cde_common.h"
+#include "cde_launch.h"
 
 namespace cde {
 
@@ -250,60 +251,50 @@ size_t generic_adjoint_workspace_bytes(int64_t B, int64_t C, int64_t H, size_t e
 }
 
 template <typename T, typename TT>
-int launch_forward_generic(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                           const void* bias, int act, const void* z0, const void* grid, int64_t n_grid,
-                           const void* t_out, int64_t n_out, void* z_out, int64_t B, int64_t C, int64_t H,
-                           const int64_t* stage_index, const void* stage_frac, hipStream_t s) {
-  const int ns = generic_ns(H, C, sizeof(T), false);
+int launch_forward_generic(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                           hipStream_t s) {
+  const int ns = generic_ns(n.H, n.C, sizeof(T), false);
   if (ns < 1) return CDE_ERR_SHAPE;
-  GenericArgs<T> g{(const T*)coeffs, (const T*)knots, n_intervals, (const T*)W, (const T*)bias, act, B, C, H, ns};
-  const int nt = ((g.NS * (int)H + 63) / 64) * 64;
-  const size_t lds = (size_t)g.NS * (H + C) * sizeof(T);
-  const unsigned blocks = (unsigned)generic_blocks(B, ns);
-  if (degree == CDE_PATH_CUBIC)
-    rk4_forward_generic<T, TT, CDE_PATH_CUBIC><<<blocks, nt, lds, s>>>(g, (const T*)z0, (const TT*)grid, n_grid, (const TT*)t_out, n_out, (T*)z_out, stage_index, (const T*)stage_frac);
-  else if (degree == CDE_PATH_LINEAR)
-    rk4_forward_generic<T, TT, CDE_PATH_LINEAR><<<blocks, nt, lds, s>>>(g, (const T*)z0, (const TT*)grid, n_grid, (const TT*)t_out, n_out, (T*)z_out, stage_index, (const T*)stage_frac);
-  else
-    return CDE_ERR_UNSUPPORTED;
-  return check_launch();
+  GenericArgs<T> g{(const T*)x.coeffs, (const T*)x.knots, x.n_intervals, (const T*)f.W, (const T*)f.bias, f.act, n.B, n.C, n.H, ns};
+  const int nt = ((g.NS * (int)n.H + 63) / 64) * 64;
+  const size_t lds = (size_t)g.NS * (n.H + n.C) * sizeof(T);
+  const unsigned blocks = (unsigned)generic_blocks(n.B, ns);
+  const int rc = dispatch_degree(x.degree, [&](auto D) {
+    rk4_forward_generic<T, TT, D()><<<blocks, nt, lds, s>>>(g, (const T*)io.z0, (const TT*)io.grid, io.n_grid, (const TT*)io.t_out,
+                                                            io.n_out, (T*)io.z_out, st.index, (const T*)st.frac);
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
 }
 
 template <typename T, typename TT>
-int launch_adjoint_generic(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                           const void* bias, int act, const void* z_saved, const void* grad_out, const void* sgrid,
-                           const int64_t* seg_off, int64_t n_out, void* grad_z0, void* grad_W, void* grad_b,
-                           int64_t B, int64_t C, int64_t H, const int64_t* stage_index, const void* stage_frac,
+int launch_adjoint_generic(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
                            void* partial_v, hipStream_t s) {
+  const int64_t H = n.H, C = n.C;
   const int ns = generic_ns(H, C, sizeof(T), true);
   if (ns < 1) return CDE_ERR_SHAPE;
-  GenericArgs<T> g{(const T*)coeffs, (const T*)knots, n_intervals, (const T*)W, (const T*)bias, act, B, C, H, ns};
+  GenericArgs<T> g{(const T*)x.coeffs, (const T*)x.knots, x.n_intervals, (const T*)f.W, (const T*)f.bias, f.act, n.B, C, H, ns};
   const int nt = ((g.NS * (int)H + 63) / 64) * 64;
   const size_t lds = (size_t)g.NS * (H + C + H * C) * sizeof(T);
-  const int64_t blocks = generic_blocks(B, ns);
+  const int64_t blocks = generic_blocks(n.B, ns);
   const int64_t P = H * C * H + H * C;
   T* partial = (T*)partial_v;
-  if (degree == CDE_PATH_CUBIC)
-    rk4_adjoint_generic<T, TT, CDE_PATH_CUBIC><<<(unsigned)blocks, nt, lds, s>>>(g, (const T*)z_saved, (const T*)grad_out, (const TT*)sgrid, seg_off, n_out, (T*)grad_z0, partial, stage_index, (const T*)stage_frac);
-  else if (degree == CDE_PATH_LINEAR)
-    rk4_adjoint_generic<T, TT, CDE_PATH_LINEAR><<<(unsigned)blocks, nt, lds, s>>>(g, (const T*)z_saved, (const T*)grad_out, (const TT*)sgrid, seg_off, n_out, (T*)grad_z0, partial, stage_index, (const T*)stage_frac);
-  else
-    return CDE_ERR_UNSUPPORTED;
-  int rc = check_launch();
+  int rc = dispatch_degree(x.degree, [&](auto D) {
+    rk4_adjoint_generic<T, TT, D()><<<(unsigned)blocks, nt, lds, s>>>(g, (const T*)io.z_saved, (const T*)io.grad_out,
+                                                                      (const TT*)io.sgrid, io.seg_off, io.n_out, (T*)io.grad_z0,
+                                                                      partial, st.index, (const T*)st.frac);
+    return CDE_OK;
+  });
+  if (rc == CDE_OK) rc = check_launch();
   if (rc != CDE_OK) return rc;
-  reduce_partials_kernel<T><<<(unsigned)((P + 255) / 256), 256, 0, s>>>(partial, blocks, P, H * C * H, (T*)grad_W, (T*)grad_b);
+  reduce_partials_kernel<T><<<(unsigned)((P + 255) / 256), 256, 0, s>>>(partial, blocks, P, H * C * H, (T*)io.grad_W, (T*)io.grad_b);
   return check_launch();
 }
 
 // explicit instantiations used by api.hip
 #define CDE_INST(T, TT)                                                                                                  \
-  template int launch_forward_generic<T, TT>(const void*, const void*, int64_t, int, const void*, const void*, int,    \
-                                             const void*, const void*, int64_t, const void*, int64_t, void*, int64_t,  \
-                                             int64_t, int64_t, const int64_t*, const void*, hipStream_t);              \
-  template int launch_adjoint_generic<T, TT>(const void*, const void*, int64_t, int, const void*, const void*, int,    \
-                                             const void*, const void*, const void*, const int64_t*, int64_t, void*,    \
-                                             void*, void*, int64_t, int64_t, int64_t, const int64_t*, const void*,     \
-                                             void*, hipStream_t);
+  template int launch_forward_generic<T, TT>(const Control&, const AffineField&, const ForwardIO&, const Shape&, const StageTable&, hipStream_t); \
+  template int launch_adjoint_generic<T, TT>(const Control&, const AffineField&, const AdjointIO&, const Shape&, const StageTable&, void*, hipStream_t);
 CDE_INST(float, float)
 CDE_INST(float, double)
 CDE_INST(double, double)

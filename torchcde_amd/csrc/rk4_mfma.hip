@@ -23,6 +23,7 @@
 // The interval index / fractional part of every stage time comes from the stage table written by
 // stage_table_kernel (api.hip) -- the same numbers CubicSpline._interpret_t would produce.
 #include "cde_mfma.h"
+#include "cde_launch.h"
 
 namespace cde {
 
@@ -1159,192 +1160,124 @@ int launch_reduce_partials(const float* partial, int64_t n_tiles, void* grad_W, 
   return check_launch();
 }
 
-bool mfma_applicable(int64_t C, int64_t H, int dtype, int act, bool adjoint) {
-  (void)adjoint;
+bool mfma_applicable(int64_t C, int64_t H, int dtype, int act) {
   const bool act_ok = act == CDE_ACT_NONE || act == CDE_ACT_TANH;
   return dtype == CDE_F32 && H >= 1 && H <= MH && C >= 1 && C <= MC && act_ok;
 }
 
 size_t mfma_adjoint_partial_bytes(int64_t B) { return (size_t)((B + 31) / 32) * PARTIAL_FLOATS * sizeof(float); }
 
+// the argument lists the forward and the adjoint kernels of this file begin with
+#define CDE_FWD_ARGS(Wp, bp)                                                                                          \
+  f32(x.coeffs), f32(x.knots), x.n_intervals, f32(Wp), f32(bp), f32(io.z0), (const TT*)io.grid, io.n_grid,            \
+      (const TT*)io.t_out, io.n_out, f32(io.z_out), n.B, st.index, f32(st.frac), dims
+#define CDE_ADJ_ARGS                                                                                                  \
+  f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(f.bias), f32(io.z_saved), f32(io.grad_out),               \
+      (const TT*)io.sgrid, io.seg_off, io.n_out, f32(io.grad_z0), partial, n.B, st.index, f32(st.frac), dims
+
 template <typename TT>
-int launch_forward_mfma(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                        const void* bias, int act, const void* z0, const void* grid, int64_t n_grid, const void* t_out,
-                        int64_t n_out, void* z_out, int64_t B, int64_t C, int64_t H, const int64_t* stage_index,
-                        const void* stage_frac, hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
+int launch_forward_mfma(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                        hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
   // product form: 8 waves x 16 series per workgroup (one per CU at B = 32768); activation form: 4 waves x 16 series
-#define CDE_FWD(D, A)                                                                                               \
-  rk4_forward_mfma<TT, D, A><<<(unsigned)((B + fwd_block_threads<A, false>() / 4 - 1) / (fwd_block_threads<A, false>() / 4)), \
-                               fwd_block_threads<A, false>(),                                                       \
-                               (A == CDE_ACT_NONE ? W16_FLOATS : ACT16_LDS_FLOATS) * sizeof(float), s>>>(           \
-      (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias, (const float*)z0, \
-      (const TT*)grid, n_grid, (const TT*)t_out, n_out, (float*)z_out, B, stage_index, (const float*)stage_frac, dims)
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_FWD(CDE_PATH_LINEAR, CDE_ACT_NONE);
-  } else if (act == CDE_ACT_TANH) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_FWD(CDE_PATH_LINEAR, CDE_ACT_TANH);
-  } else return CDE_ERR_UNSUPPORTED;
-#undef CDE_FWD
-  return check_launch();
+  const int rc = dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+    constexpr int threads = fwd_block_threads<A(), false>();
+    rk4_forward_mfma<TT, D(), A()><<<(unsigned)((n.B + threads / 4 - 1) / (threads / 4)), threads,
+                                     (A() == CDE_ACT_NONE ? W16_FLOATS : ACT16_LDS_FLOATS) * sizeof(float), s>>>(
+        CDE_FWD_ARGS(f.W, f.bias));
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
+}
+
+// the two-layer kernel <TT, D, A, true, CT, SPLIT, STAGES, rk4, HI> on its three tile shapes: 32 units x 8 channels,
+// 16 x 16, and (`upper`) 32 x 16
+struct MlpTiles { bool upper, wide; unsigned blocks; size_t lds; };
+template <typename TT, int D, int A, bool SPLIT, bool STAGES>
+static void launch_mlp_tiles(const MlpTiles& t, const Control& x, const TwoLayerField& f, const ForwardIO& io, const Shape& n,
+                             const StageTable& st, hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
+  auto launch = [&](auto CT, auto HI) {
+    auto kernel = rk4_forward_mfma<TT, D, A, true, CT(), SPLIT, STAGES, CDE_METHOD_RK4, HI()>;
+    allow_lds(kernel, t.lds);
+    kernel<<<t.blocks, 512, t.lds, s>>>(CDE_FWD_ARGS(f.W2, f.bias2), f32(f.W1), f32(f.bias1), (int)f.width, f32(io.stages));
+  };
+  if (t.upper) launch(Const<16>{}, std::true_type{});
+  else if (t.wide) launch(Const<16>{}, std::false_type{});
+  else launch(Const<MC>{}, std::false_type{});
 }
 
 template <typename TT>
-int launch_forward_mlp(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
-                       const void* bias1, int64_t width, const void* W2, const void* bias2, int act, const void* z0,
-                       const void* grid, int64_t n_grid, const void* t_out, int64_t n_out, void* z_out, int64_t B,
-                       int64_t C, int64_t H, const int64_t* stage_index, const void* stage_frac, hipStream_t s) {
+int launch_forward_mlp(const Control& x, const TwoLayerField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                       hipStream_t s) {
   // (32 units x 16 channels: the upper unit groups straight from W2 / bias2 -- 16-byte rows)
-  const bool upper = mlp_shape_hi(C, H, width) && ((uintptr_t)W2 & 15) == 0;
-  if (!mlp_shape_ok(C, H, width) && !upper) return CDE_ERR_UNSUPPORTED;
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (act != CDE_ACT_NONE && act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 127) / 128);
+  const bool upper = mlp_shape_hi(n.C, n.H, f.width) && ((uintptr_t)f.W2 & 15) == 0;
+  if (!mlp_shape_ok(n.C, n.H, f.width) && !upper) return CDE_ERR_UNSUPPORTED;
+  const unsigned blocks = (unsigned)((n.B + 127) / 128);
   const size_t lds = (size_t)MLP16_LDS_FLOATS * sizeof(float);
-  const bool wide = C > MC;                 // 16 channels x 16 (or, `upper`, 32) hidden units on the same 16 tiles
+  const bool wide = n.C > MC;               // 16 channels x 16 (or, `upper`, 32) hidden units on the same 16 tiles
   // up to 768 tiles (three rounds of one workgroup per CU still beat 8 tiles per workgroup on a quarter of the CUs): the 8
   // waves of a workgroup share a tile (K2m's split form)
-  const int64_t tiles = (B + 15) / 16;
+  const int64_t tiles = (n.B + 15) / 16;
   const bool split = tiles <= 768 && !option(CDE_OPT_K2M_NO_SPLIT);
   const size_t lds_split = lds + (8 * 64 + 8 * 64 * 4) * sizeof(float);     // f window + (8-channel tiles) the u window
-#define CDE_FWD_CT(D, A, CTV, HIV)                                                                                  \
-  do {                                                                                                              \
-    if (split) {                                                                                                    \
-      (void)hipFuncSetAttribute((const void*)rk4_forward_mfma<TT, D, A, true, CTV, true, false, CDE_METHOD_RK4, HIV>, \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_split);                        \
-      rk4_forward_mfma<TT, D, A, true, CTV, true, false, CDE_METHOD_RK4, HIV><<<(unsigned)tiles, 512, lds_split, s>>>( \
-          (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W2, (const float*)bias2,            \
-          (const float*)z0, (const TT*)grid, n_grid, (const TT*)t_out, n_out, (float*)z_out, B, stage_index,        \
-          (const float*)stage_frac, dims, (const float*)W1, (const float*)bias1, (int)width);                       \
-    } else {                                                                                                        \
-      (void)hipFuncSetAttribute((const void*)rk4_forward_mfma<TT, D, A, true, CTV, false, false, CDE_METHOD_RK4, HIV>, \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-      rk4_forward_mfma<TT, D, A, true, CTV, false, false, CDE_METHOD_RK4, HIV><<<blocks, 512, lds, s>>>(            \
-          (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W2, (const float*)bias2,            \
-          (const float*)z0, (const TT*)grid, n_grid, (const TT*)t_out, n_out, (float*)z_out, B, stage_index,        \
-          (const float*)stage_frac, dims, (const float*)W1, (const float*)bias1, (int)width);                       \
-    }                                                                                                               \
-  } while (0)
-#define CDE_FWD(D, A)                                                                                               \
-  do {                                                                                                              \
-    if (upper) CDE_FWD_CT(D, A, 16, true); else if (wide) CDE_FWD_CT(D, A, 16, false); else CDE_FWD_CT(D, A, MC, false); \
-  } while (0)
-  if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_FWD(CDE_PATH_LINEAR, CDE_ACT_NONE);
-  } else {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_FWD(CDE_PATH_LINEAR, CDE_ACT_TANH);
-  }
-#undef CDE_FWD
-#undef CDE_FWD_CT
-  return check_launch();
+  const int rc = dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+    if (split) launch_mlp_tiles<TT, D(), A(), true, false>(MlpTiles{upper, wide, (unsigned)tiles, lds_split}, x, f, io, n, st, s);
+    else launch_mlp_tiles<TT, D(), A(), false, false>(MlpTiles{upper, wide, blocks, lds}, x, f, io, n, st, s);
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
 }
 
 // K2 with the stage states stored (adjoint=False backward: rk4_backprop.hip).  Affine field, f32, H <= 32, C <= 8.
 template <typename TT>
-int launch_forward_mfma_stages(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                               const void* bias, int act, const void* z0, const void* grid, int64_t n_grid, const void* t_out,
-                               int64_t n_out, void* z_out, void* stages, int64_t B, int64_t C, int64_t H,
-                               const int64_t* stage_index, const void* stage_frac, hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
+int launch_forward_mfma_stages(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n,
+                               const StageTable& st, hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
   constexpr int threads = fwd_block_threads<CDE_ACT_NONE, false>();
-#define CDE_FWD_S(D, A)                                                                                               \
-  rk4_forward_mfma<TT, D, A, false, MC, false, true>                                                                  \
-      <<<(unsigned)((B + threads / 4 - 1) / (threads / 4)), threads,                                                  \
-         (A == CDE_ACT_NONE ? W16_FLOATS : ACT16_LDS_FLOATS) * sizeof(float), s>>>(                                   \
-          (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias,                \
-          (const float*)z0, (const TT*)grid, n_grid, (const TT*)t_out, n_out, (float*)z_out, B, stage_index,          \
-          (const float*)stage_frac, dims, nullptr, nullptr, 0, (float*)stages)
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD_S(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_FWD_S(CDE_PATH_LINEAR, CDE_ACT_NONE);
-  } else if (act == CDE_ACT_TANH) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD_S(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_FWD_S(CDE_PATH_LINEAR, CDE_ACT_TANH);
-  } else return CDE_ERR_UNSUPPORTED;
-#undef CDE_FWD_S
-  return check_launch();
+  const int rc = dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+    rk4_forward_mfma<TT, D(), A(), false, MC, false, true>
+        <<<(unsigned)((n.B + threads / 4 - 1) / (threads / 4)), threads,
+           (A() == CDE_ACT_NONE ? W16_FLOATS : ACT16_LDS_FLOATS) * sizeof(float), s>>>(
+            CDE_FWD_ARGS(f.W, f.bias), nullptr, nullptr, 0, f32(io.stages));
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
 }
-template int launch_forward_mfma_stages<float>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                               const void*, const void*, int64_t, const void*, int64_t, void*, void*, int64_t,
-                                               int64_t, int64_t, const int64_t*, const void*, hipStream_t);
-template int launch_forward_mfma_stages<double>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                                const void*, const void*, int64_t, const void*, int64_t, void*, void*, int64_t,
-                                                int64_t, int64_t, const int64_t*, const void*, hipStream_t);
 
 // K2m with the stage states stored (adjoint=False backward of the two-layer field): the one-wave-per-tile form at any batch
 template <typename TT>
-int launch_forward_mlp_stages(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
-                              const void* bias1, int64_t width, const void* W2, const void* bias2, int act, const void* z0,
-                              const void* grid, int64_t n_grid, const void* t_out, int64_t n_out, void* z_out, void* stages,
-                              int64_t B, int64_t C, int64_t H, const int64_t* stage_index, const void* stage_frac,
-                              hipStream_t s) {
-  if (!mlp_shape_ok(C, H, width) && !(mlp_shape_hi(C, H, width) && ((uintptr_t)W2 & 15) == 0)) return CDE_ERR_UNSUPPORTED;
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (act != CDE_ACT_NONE && act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 127) / 128);
+int launch_forward_mlp_stages(const Control& x, const TwoLayerField& f, const ForwardIO& io, const Shape& n,
+                              const StageTable& st, hipStream_t s) {
+  if (!mlp_shape_ok(n.C, n.H, f.width) && !(mlp_shape_hi(n.C, n.H, f.width) && ((uintptr_t)f.W2 & 15) == 0))
+    return CDE_ERR_UNSUPPORTED;
+  const unsigned blocks = (unsigned)((n.B + 127) / 128);
   const size_t lds = (size_t)MLP16_LDS_FLOATS * sizeof(float);
-#define CDE_FWD_MS(D, A, CTV, HIV)                                                                                  \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)rk4_forward_mfma<TT, D, A, true, CTV, false, true, CDE_METHOD_RK4, HIV>, \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
-    rk4_forward_mfma<TT, D, A, true, CTV, false, true, CDE_METHOD_RK4, HIV><<<blocks, 512, lds, s>>>(               \
-        (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W2, (const float*)bias2,              \
-        (const float*)z0, (const TT*)grid, n_grid, (const TT*)t_out, n_out, (float*)z_out, B, stage_index,          \
-        (const float*)stage_frac, dims, (const float*)W1, (const float*)bias1, (int)width, (float*)stages);         \
-  } while (0)
-#define CDE_FWD_MSD(D, A)                                                                                           \
-  do {                                                                                                              \
-    if (H > 16 && C > MC) CDE_FWD_MS(D, A, 16, true); else if (C > MC) CDE_FWD_MS(D, A, 16, false); else CDE_FWD_MS(D, A, MC, false); \
-  } while (0)
-  if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD_MSD(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_FWD_MSD(CDE_PATH_LINEAR, CDE_ACT_NONE);
-  } else {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD_MSD(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_FWD_MSD(CDE_PATH_LINEAR, CDE_ACT_TANH);
-  }
-#undef CDE_FWD_MSD
-#undef CDE_FWD_MS
-  return check_launch();
+  const int rc = dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+    launch_mlp_tiles<TT, D(), A(), false, true>(MlpTiles{n.H > 16 && n.C > MC, n.C > MC, blocks, lds}, x, f, io, n, st, s);
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
 }
-template int launch_forward_mlp_stages<float>(const void*, const void*, int64_t, int, const void*, const void*, int64_t,
-                                              const void*, const void*, int, const void*, const void*, int64_t, const void*,
-                                              int64_t, void*, void*, int64_t, int64_t, int64_t, const int64_t*, const void*,
-                                              hipStream_t);
-template int launch_forward_mlp_stages<double>(const void*, const void*, int64_t, int, const void*, const void*, int64_t,
-                                               const void*, const void*, int, const void*, const void*, int64_t, const void*,
-                                               int64_t, void*, void*, int64_t, int64_t, int64_t, const int64_t*, const void*,
-                                               hipStream_t);
 
 // midpoint / euler through the same kernel (affine field, f32, H <= 32, C <= 8)
 template <typename TT>
-int launch_forward_mfma_method(int method, const void* coeffs, const void* knots, int64_t n_intervals, int degree,
-                               const void* W, const void* bias, const void* z0, const void* grid, int64_t n_grid,
-                               const void* t_out, int64_t n_out, void* z_out, int64_t B, int64_t C, int64_t H,
-                               const int64_t* stage_index, const void* stage_frac, hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
+int launch_forward_mfma_method(int method, const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n,
+                               const StageTable& st, hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
   constexpr int threads = fwd_block_threads<CDE_ACT_NONE, false>();
-#define CDE_FWD_M(D, M)                                                                                               \
-  rk4_forward_mfma<TT, D, CDE_ACT_NONE, false, MC, false, false, M>                                                   \
-      <<<(unsigned)((B + threads / 4 - 1) / (threads / 4)), threads, W16_FLOATS * sizeof(float), s>>>(                \
-          (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias,                \
-          (const float*)z0, (const TT*)grid, n_grid, (const TT*)t_out, n_out, (float*)z_out, B, stage_index,          \
-          (const float*)stage_frac, dims)
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (method == CDE_METHOD_MIDPOINT) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD_M(CDE_PATH_CUBIC, CDE_METHOD_MIDPOINT); else CDE_FWD_M(CDE_PATH_LINEAR, CDE_METHOD_MIDPOINT);
-  } else if (method == CDE_METHOD_EULER) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD_M(CDE_PATH_CUBIC, CDE_METHOD_EULER); else CDE_FWD_M(CDE_PATH_LINEAR, CDE_METHOD_EULER);
-  } else return CDE_ERR_UNSUPPORTED;
-#undef CDE_FWD_M
-  return check_launch();
+  if (method != CDE_METHOD_MIDPOINT && method != CDE_METHOD_EULER) return CDE_ERR_UNSUPPORTED;
+  const int rc = dispatch_degree(x.degree, [&](auto D) {
+    auto launch = [&](auto M) {
+      rk4_forward_mfma<TT, D(), CDE_ACT_NONE, false, MC, false, false, M()>
+          <<<(unsigned)((n.B + threads / 4 - 1) / (threads / 4)), threads, W16_FLOATS * sizeof(float), s>>>(
+              CDE_FWD_ARGS(f.W, f.bias));
+    };
+    if (method == CDE_METHOD_MIDPOINT) launch(Const<CDE_METHOD_MIDPOINT>{}); else launch(Const<CDE_METHOD_EULER>{});
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
 }
-template int launch_forward_mfma_method<float>(int, const void*, const void*, int64_t, int, const void*, const void*, const void*,
-                                               const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t, int64_t,
-                                               const int64_t*, const void*, hipStream_t);
-template int launch_forward_mfma_method<double>(int, const void*, const void*, int64_t, int, const void*, const void*, const void*,
-                                                const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t, int64_t,
-                                                const int64_t*, const void*, hipStream_t);
 
 // which of the two adjoint kernels of the affine field runs: K3j (shared Jacobian) unless CDE_OPT_K3_FORM = 1 asks for K3
 // (the tests run both against the oracle; scripts compare their timings)
@@ -1353,10 +1286,6 @@ static bool k3_form_jacobian() {
 }
 
 // K3p (rk4_adjoint_pair.hip): K3j as a chain wave + a helper wave per tile, two waves per SIMD.  CDE_OPT_K3_WAVES = 1 / 2 picks the form (tests run both; bitwise the same results)
-template <typename TT>
-int launch_adjoint_jacobian_pair(const void*, const void*, int64_t, int, const void*, const void*, const void*, const void*,
-                                 const void*, const int64_t*, int64_t, void*, void*, void*, int64_t, int64_t, int64_t,
-                                 const int64_t*, const void*, float*, hipStream_t, int method, bool bx = false);
 constexpr bool K3_PAIR_DEFAULT = true;       // 5.26 -> 5.01 ms on the headline workload (profiles/r05_k3_pair_b.log)
 static bool k3_form_pair() {
   const int64_t e = option(CDE_OPT_K3_WAVES);
@@ -1364,116 +1293,69 @@ static bool k3_form_pair() {
 }
 
 template <typename TT>
-int launch_adjoint_mfma(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                        const void* bias, int act, const void* z_saved, const void* grad_out, const void* sgrid,
-                        const int64_t* seg_off, int64_t n_out, void* grad_z0, void* grad_W, void* grad_b, int64_t B,
-                        int64_t C, int64_t H, const int64_t* stage_index, const void* stage_frac, float* partial,
-                        void* grad_coeffs, hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 127) / 128);
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-#define CDE_ADJ(KERNEL, LDS_FLOATS)                                                                                  \
-  do {                                                                                                               \
-    const size_t lds = (size_t)(LDS_FLOATS) * sizeof(float);                                                         \
-    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
-    KERNEL<<<blocks, 256, lds, s>>>((const float*)coeffs, (const float*)knots, n_intervals, (const float*)W,         \
-                                    (const float*)bias, (const float*)z_saved, (const float*)grad_out,               \
-                                    (const TT*)sgrid, seg_off, n_out, (float*)grad_z0, partial, B, stage_index,      \
-                                    (const float*)stage_frac, dims);                                                 \
-  } while (0)
-#define CDE_ADJ_DX(KERNEL)                                                                                           \
-  do {                                                                                                               \
-    const size_t lds = (size_t)(ACT_ADJ_LDS_FLOATS) * sizeof(float);                                                 \
-    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
-    KERNEL<<<blocks, 256, lds, s>>>((const float*)coeffs, (const float*)knots, n_intervals, (const float*)W,         \
-                                    (const float*)bias, (const float*)z_saved, (const float*)grad_out,               \
-                                    (const TT*)sgrid, seg_off, n_out, (float*)grad_z0, partial, B, stage_index,      \
-                                    (const float*)stage_frac, dims, (float*)grad_coeffs);                            \
-  } while (0)
-  if (grad_coeffs) {                       // control gradients: the pre-activation kernel (it holds act(Y) in-lane)
-    if (act == CDE_ACT_NONE) {
-      if (degree == CDE_PATH_CUBIC) CDE_ADJ_DX((rk4_adjoint_act_mfma<TT, CDE_PATH_CUBIC, CDE_ACT_NONE, true>));
-      else CDE_ADJ_DX((rk4_adjoint_act_mfma<TT, CDE_PATH_LINEAR, CDE_ACT_NONE, true>));
-    } else if (act == CDE_ACT_TANH) {
-      if (degree == CDE_PATH_CUBIC) CDE_ADJ_DX((rk4_adjoint_act_mfma<TT, CDE_PATH_CUBIC, CDE_ACT_TANH, true>));
-      else CDE_ADJ_DX((rk4_adjoint_act_mfma<TT, CDE_PATH_LINEAR, CDE_ACT_TANH, true>));
-    } else return CDE_ERR_UNSUPPORTED;
-  } else if (act == CDE_ACT_NONE && k3_form_jacobian() && k3_form_pair()) {
-    return launch_adjoint_jacobian_pair<TT>(coeffs, knots, n_intervals, degree, W, bias, z_saved, grad_out, sgrid, seg_off,
-                                            n_out, grad_z0, grad_W, grad_b, B, C, H, stage_index, stage_frac, partial, s,
-                                            CDE_METHOD_RK4);
-  } else if (act == CDE_ACT_NONE && k3_form_jacobian()) {
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ((rk4_adjoint_jacobian<TT, CDE_PATH_CUBIC>), WJ_FLOATS + 4 * SCR_FLOATS);
-    else CDE_ADJ((rk4_adjoint_jacobian<TT, CDE_PATH_LINEAR>), WJ_FLOATS + 4 * SCR_FLOATS);
-  } else if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ((rk4_adjoint_mfma<TT, CDE_PATH_CUBIC>), W1_FLOATS + W2_FLOATS + 4 * SCR_FLOATS);
-    else CDE_ADJ((rk4_adjoint_mfma<TT, CDE_PATH_LINEAR>), W1_FLOATS + W2_FLOATS + 4 * SCR_FLOATS);
-  } else if (act == CDE_ACT_TANH) {
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ((rk4_adjoint_act_mfma<TT, CDE_PATH_CUBIC, CDE_ACT_TANH>), ACT_ADJ_LDS_FLOATS);
-    else CDE_ADJ((rk4_adjoint_act_mfma<TT, CDE_PATH_LINEAR, CDE_ACT_TANH>), ACT_ADJ_LDS_FLOATS);
-  } else return CDE_ERR_UNSUPPORTED;
-#undef CDE_ADJ
-#undef CDE_ADJ_DX
-  int rc = check_launch();
+int launch_adjoint_mfma(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
+                        float* partial, hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 127) / 128);
+  if (x.degree != CDE_PATH_CUBIC && x.degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
+  if (!io.grad_coeffs && f.act == CDE_ACT_NONE && k3_form_jacobian() && k3_form_pair())
+    return launch_adjoint_jacobian_pair<TT>(x, f, io, n, st, partial, s, PairForm{CDE_METHOD_RK4, PairRows::f32});
+  auto launch = [&](auto kernel, int64_t lds_floats, auto... tail) {
+    const size_t lds = (size_t)lds_floats * sizeof(float);
+    allow_lds(kernel, lds);
+    kernel<<<blocks, 256, lds, s>>>(CDE_ADJ_ARGS, tail...);
+    return CDE_OK;
+  };
+  int rc;
+  if (io.grad_coeffs)                      // control gradients: the pre-activation kernel (it holds act(Y) in-lane)
+    rc = dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+      return launch(rk4_adjoint_act_mfma<TT, D(), A(), true>, ACT_ADJ_LDS_FLOATS, f32(io.grad_coeffs));
+    });
+  else if (f.act == CDE_ACT_NONE && k3_form_jacobian())
+    rc = dispatch_degree(x.degree, [&](auto D) { return launch(rk4_adjoint_jacobian<TT, D()>, WJ_FLOATS + 4 * SCR_FLOATS); });
+  else if (f.act == CDE_ACT_NONE)
+    rc = dispatch_degree(x.degree, [&](auto D) {
+      return launch(rk4_adjoint_mfma<TT, D()>, W1_FLOATS + W2_FLOATS + 4 * SCR_FLOATS);
+    });
+  else if (f.act == CDE_ACT_TANH)
+    rc = dispatch_degree(x.degree, [&](auto D) {
+      return launch(rk4_adjoint_act_mfma<TT, D(), CDE_ACT_TANH>, ACT_ADJ_LDS_FLOATS, (float*)nullptr);
+    });
+  else return CDE_ERR_UNSUPPORTED;
+  if (rc == CDE_OK) rc = check_launch();
   if (rc != CDE_OK) return rc;
-  return launch_reduce_partials(partial, (B + 31) / 32, grad_W, grad_b, (int)H, (int)C, s);
+  return launch_reduce_partials(partial, (n.B + 31) / 32, io.grad_W, io.grad_b, (int)n.H, (int)n.C, s);
 }
 
 // variant "bf16x3": K3j with its J rows on the bf16 pipe (three-piece operands)
 template <typename TT>
-int launch_adjoint_jacobian_bx(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                               const void* bias, const void* z_saved, const void* grad_out, const void* sgrid,
-                               const int64_t* seg_off, int64_t n_out, void* grad_z0, void* grad_W, void* grad_b, int64_t B,
-                               int64_t C, int64_t H, const int64_t* stage_index, const void* stage_frac, float* partial,
-                               hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 127) / 128);
+int launch_adjoint_jacobian_bx(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n,
+                               const StageTable& st, float* partial, hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 127) / 128);
   const size_t lds = (size_t)(WJB_FLOATS + 4 * SCR_FLOATS) * sizeof(float);
-#define CDE_ADJ_BX(D)                                                                                                \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)rk4_adjoint_jacobian<TT, D, true>,                                        \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-    rk4_adjoint_jacobian<TT, D, true><<<blocks, 256, lds, s>>>(                                                      \
-        (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias,                 \
-        (const float*)z_saved, (const float*)grad_out, (const TT*)sgrid, seg_off, n_out, (float*)grad_z0, partial,   \
-        B, stage_index, (const float*)stage_frac, dims);                                                             \
-  } while (0)
-  if (degree == CDE_PATH_CUBIC) CDE_ADJ_BX(CDE_PATH_CUBIC);
-  else if (degree == CDE_PATH_LINEAR) CDE_ADJ_BX(CDE_PATH_LINEAR);
-  else return CDE_ERR_UNSUPPORTED;
-#undef CDE_ADJ_BX
-  const int rc = check_launch();
+  int rc = dispatch_degree(x.degree, [&](auto D) {
+    allow_lds(rk4_adjoint_jacobian<TT, D(), true>, lds);
+    rk4_adjoint_jacobian<TT, D(), true><<<blocks, 256, lds, s>>>(CDE_ADJ_ARGS);
+    return CDE_OK;
+  });
+  if (rc == CDE_OK) rc = check_launch();
   if (rc != CDE_OK) return rc;
-  return launch_reduce_partials(partial, (B + 31) / 32, grad_W, grad_b, (int)H, (int)C, s);
+  return launch_reduce_partials(partial, (n.B + 31) / 32, io.grad_W, io.grad_b, (int)n.H, (int)n.C, s);
 }
-template int launch_adjoint_jacobian_bx<float>(const void*, const void*, int64_t, int, const void*, const void*, const void*,
-                                               const void*, const void*, const int64_t*, int64_t, void*, void*, void*,
-                                               int64_t, int64_t, int64_t, const int64_t*, const void*, float*, hipStream_t);
-template int launch_adjoint_jacobian_bx<double>(const void*, const void*, int64_t, int, const void*, const void*, const void*,
-                                                const void*, const void*, const int64_t*, int64_t, void*, void*, void*,
-                                                int64_t, int64_t, int64_t, const int64_t*, const void*, float*, hipStream_t);
+#undef CDE_ADJ_ARGS
+#undef CDE_FWD_ARGS
 
-template int launch_forward_mfma<float>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                        const void*, const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t,
-                                        int64_t, const int64_t*, const void*, hipStream_t);
-template int launch_forward_mfma<double>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                         const void*, const void*, int64_t, const void*, int64_t, void*, int64_t,
-                                         int64_t, int64_t, const int64_t*, const void*, hipStream_t);
-template int launch_forward_mlp<float>(const void*, const void*, int64_t, int, const void*, const void*, int64_t,
-                                       const void*, const void*, int, const void*, const void*, int64_t, const void*,
-                                       int64_t, void*, int64_t, int64_t, int64_t, const int64_t*, const void*,
-                                       hipStream_t);
-template int launch_forward_mlp<double>(const void*, const void*, int64_t, int, const void*, const void*, int64_t,
-                                        const void*, const void*, int, const void*, const void*, int64_t, const void*,
-                                        int64_t, void*, int64_t, int64_t, int64_t, const int64_t*, const void*,
-                                        hipStream_t);
-template int launch_adjoint_mfma<float>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                        const void*, const void*, const void*, const int64_t*, int64_t, void*, void*,
-                                        void*, int64_t, int64_t, int64_t, const int64_t*, const void*, float*, void*,
-                                        hipStream_t);
-template int launch_adjoint_mfma<double>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                         const void*, const void*, const void*, const int64_t*, int64_t, void*, void*,
-                                         void*, int64_t, int64_t, int64_t, const int64_t*, const void*, float*, void*,
-                                         hipStream_t);
+#define CDE_INST(TT)                                                                                                  \
+  template int launch_forward_mfma<TT>(const Control&, const AffineField&, const ForwardIO&, const Shape&, const StageTable&, hipStream_t); \
+  template int launch_forward_mlp<TT>(const Control&, const TwoLayerField&, const ForwardIO&, const Shape&, const StageTable&, hipStream_t); \
+  template int launch_forward_mfma_stages<TT>(const Control&, const AffineField&, const ForwardIO&, const Shape&, const StageTable&, hipStream_t); \
+  template int launch_forward_mlp_stages<TT>(const Control&, const TwoLayerField&, const ForwardIO&, const Shape&, const StageTable&, hipStream_t); \
+  template int launch_forward_mfma_method<TT>(int, const Control&, const AffineField&, const ForwardIO&, const Shape&, const StageTable&, hipStream_t); \
+  template int launch_adjoint_mfma<TT>(const Control&, const AffineField&, const AdjointIO&, const Shape&, const StageTable&, float*, hipStream_t); \
+  template int launch_adjoint_jacobian_bx<TT>(const Control&, const AffineField&, const AdjointIO&, const Shape&, const StageTable&, float*, hipStream_t);
+CDE_INST(float)
+CDE_INST(double)
+#undef CDE_INST
 
 }  // namespace cde

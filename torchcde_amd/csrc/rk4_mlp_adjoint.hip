@@ -28,6 +28,7 @@
 // with every (P, tb, T1) offset an instruction immediate.
 // 1152 MFMAs per stage = 76.3 MFLOP per series per solve for the sweep itself.
 #include "cde_mlp_adj.h"
+#include "cde_launch.h"
 
 namespace cde {
 
@@ -581,131 +582,84 @@ int launch_mlp_adjoint_images(const void* W1, const void* b1, int64_t width, con
 
 constexpr int64_t K3M_S8_MAX_TILES = 1536;    // 24576 series (measured: 12288: 34.4 -> 20.9 ms, 24576: 44.1 -> 41.9, 32768: 47.6 vs 52.2)
 
+// the arguments both sweep kernels begin with
+#define CDE_SWEEP_ARGS(y_state)                                                                                     \
+  f32(x.coeffs), f32(x.knots), x.n_intervals, io.image, y_state, f32(io.a_state), (const TT*)io.grid, io.k_begin,   \
+      io.k_end, st.index, f32(st.frac), f32(io.U), f32(io.G2), f32(io.G1), f32(io.Z), n.B, dims
+
 template <typename TT>
-int launch_mlp_adjoint_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
-                             const float* img, void* y_state, void* a_state, const void* sgrid, int64_t k_begin,
-                             int64_t k_end, const int64_t* stage_index, const void* stage_frac, void* U, void* G2,
-                             void* G1, void* Z, int64_t B, int64_t C, int64_t H, void* grad_coeffs, hipStream_t s) {
-  if (k_end <= k_begin) return CDE_OK;
-  const Dims dims{(int)H, (int)C};
+int launch_mlp_adjoint_sweep(const Control& x, const SweepIO& io, const Shape& n, const StageTable& st, hipStream_t s) {
+  if (io.k_end <= io.k_begin) return CDE_OK;
+  const Dims dims{(int)n.H, (int)n.C};
   // up to 512 tiles (two rounds of one workgroup per CU; the 8-wave form would use a quarter of the CUs there): four
   // waves per tile (the split form)
-  const int64_t tiles = (B + 15) / 16;
+  const int64_t tiles = (n.B + 15) / 16;
   // (the eight-wave form of 8-channel tiles runs ~7 ms per round of 256 tiles: it beats the one-wave-per-tile form up to
   //  CDE_OPT_K3M_S8_TILES tiles; measured crossover in profiles/NOTES.md)
   const int64_t s8_req = option(CDE_OPT_K3M_S8_TILES);                    // (-1: the default; an override can only LOWER the measured limit)
   const int64_t s8_tiles = s8_req < 0 || s8_req > K3M_S8_MAX_TILES ? K3M_S8_MAX_TILES : s8_req;
-  const bool s8_shape = C <= MC && !grad_coeffs && !option(CDE_OPT_K3M_SPLIT4);
+  const bool s8_shape = n.C <= MC && !io.grad_coeffs && !option(CDE_OPT_K3M_SPLIT4);
   // (control gradients of the 16-channel layout: the one-wave-per-tile form at every batch size)
   const bool split = tiles <= (s8_shape ? (s8_tiles > 512 ? s8_tiles : 512) : 512) && !option(CDE_OPT_K3M_NO_SPLIT) &&
-                     !(grad_coeffs && C > MC);
-  const unsigned blocks = split ? (unsigned)tiles : (unsigned)((B + 127) / 128);
+                     !(io.grad_coeffs && n.C > MC);
+  const unsigned blocks = split ? (unsigned)tiles : (unsigned)((n.B + 127) / 128);
   const unsigned threads = split ? 256 : 512;
   const size_t lds = (size_t)ADJ_LDS_FLOATS * sizeof(float) + (split ? (size_t)4 * 64 * 9 * sizeof(float) : 0);
   // ... eight waves per tile (everything split eight ways) for 8-channel tiles without control gradients
-  if (split && s8_shape && tiles <= (s8_tiles > 512 ? s8_tiles : 512)) {
-#define CDE_SWEEP8(D, A)                                                                                           \
-  do {                                                                                                             \
-    (void)hipFuncSetAttribute((const void*)rk4_adjoint_mlp_sweep_s8<TT, D, A>,                                     \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-    rk4_adjoint_mlp_sweep_s8<TT, D, A><<<blocks, 512, lds, s>>>(                                                   \
-        (const float*)coeffs, (const float*)knots, n_intervals, img, (float*)y_state, (float*)a_state,             \
-        (const TT*)sgrid, k_begin, k_end, stage_index, (const float*)stage_frac, (float*)U, (float*)G2, (float*)G1, \
-        (float*)Z, B, dims);                                                                                       \
-  } while (0)
-    if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-    if (act == CDE_ACT_NONE) {
-      if (degree == CDE_PATH_CUBIC) CDE_SWEEP8(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_SWEEP8(CDE_PATH_LINEAR, CDE_ACT_NONE);
-    } else if (act == CDE_ACT_TANH) {
-      if (degree == CDE_PATH_CUBIC) CDE_SWEEP8(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_SWEEP8(CDE_PATH_LINEAR, CDE_ACT_TANH);
-    } else return CDE_ERR_UNSUPPORTED;
-#undef CDE_SWEEP8
-    return check_launch();
-  }
-#define CDE_SWEEP_L(D, A, X, CTV, SPL, GC)                                                                         \
-  do {                                                                                                             \
-    (void)hipFuncSetAttribute((const void*)rk4_adjoint_mlp_sweep<TT, D, A, X, CTV, SPL>,                           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-    rk4_adjoint_mlp_sweep<TT, D, A, X, CTV, SPL><<<blocks, threads, lds, s>>>(                                     \
-        (const float*)coeffs, (const float*)knots, n_intervals, img, (float*)y_state, (float*)a_state,             \
-        (const TT*)sgrid, k_begin, k_end, stage_index, (const float*)stage_frac, (float*)U, (float*)G2, (float*)G1, \
-        (float*)Z, B, dims, GC);                                                                                   \
-  } while (0)
-#define CDE_SWEEP_X(D, A, X)                                                                                       \
-  do {                                                                                                             \
-    if (C > MC) {                              /* 16 channels x 16 units */                                        \
-      if (X) CDE_SWEEP_L(D, A, X, 16, false, (float*)grad_coeffs);                                                 \
-      else if (split) CDE_SWEEP_L(D, A, false, 16, true, nullptr);                                                 \
-      else CDE_SWEEP_L(D, A, false, 16, false, nullptr);                                                           \
-      break;                                                                                                       \
-    }                                                                                                              \
-    if (split) CDE_SWEEP_L(D, A, X, MC, true, (float*)grad_coeffs);                                                \
-    else CDE_SWEEP_L(D, A, X, MC, false, (float*)grad_coeffs);                                                     \
-  } while (0)
-#define CDE_SWEEP(D, A)                                                                                            \
-  do {                                                                                                             \
-    if (grad_coeffs) CDE_SWEEP_X(D, A, true); else CDE_SWEEP_X(D, A, false);                                       \
-  } while (0)
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_SWEEP(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_SWEEP(CDE_PATH_LINEAR, CDE_ACT_NONE);
-  } else if (act == CDE_ACT_TANH) {
-    if (degree == CDE_PATH_CUBIC) CDE_SWEEP(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_SWEEP(CDE_PATH_LINEAR, CDE_ACT_TANH);
-  } else return CDE_ERR_UNSUPPORTED;
-#undef CDE_SWEEP
-#undef CDE_SWEEP_X
-#undef CDE_SWEEP_L
-  return check_launch();
+  const bool eight = split && s8_shape && tiles <= (s8_tiles > 512 ? s8_tiles : 512);
+  using Yes = std::true_type;
+  using No = std::false_type;
+  const int rc = dispatch_degree_act(x.degree, io.act, [&](auto D, auto A) {
+    auto launch = [&](auto X, auto CT, auto SPL) {
+      allow_lds(rk4_adjoint_mlp_sweep<TT, D(), A(), X(), CT(), SPL()>, lds);
+      rk4_adjoint_mlp_sweep<TT, D(), A(), X(), CT(), SPL()><<<blocks, threads, lds, s>>>(CDE_SWEEP_ARGS(f32(io.y_state)),
+                                                                                         f32(io.grad_coeffs));
+    };
+    if (eight) {
+      allow_lds(rk4_adjoint_mlp_sweep_s8<TT, D(), A()>, lds);
+      rk4_adjoint_mlp_sweep_s8<TT, D(), A()><<<blocks, 512, lds, s>>>(CDE_SWEEP_ARGS(f32(io.y_state)));
+    } else if (n.C > MC) {                       // 16 channels x 16 units
+      if (io.grad_coeffs) launch(Yes{}, Const<16>{}, No{});
+      else if (split) launch(No{}, Const<16>{}, Yes{});
+      else launch(No{}, Const<16>{}, No{});
+    } else if (io.grad_coeffs) {
+      if (split) launch(Yes{}, Const<MC>{}, Yes{}); else launch(Yes{}, Const<MC>{}, No{});
+    } else {
+      if (split) launch(No{}, Const<MC>{}, Yes{}); else launch(No{}, Const<MC>{}, No{});
+    }
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
 }
 
 // the reverse-mode form (adjoint=False): one wave per tile, steps k_end-1 .. k_begin of the forward grid
 template <typename TT>
-int launch_mlp_backprop_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
-                              const float* img, const void* stages, int64_t n_steps_total, void* g_state, const void* grid,
-                              int64_t k_begin, int64_t k_end, const int64_t* stage_index, const void* stage_frac, void* U,
-                              void* G2, void* G1, void* Z, int64_t B, int64_t C, int64_t H, void* grad_coeffs,
-                              hipStream_t s) {
-  if (k_end <= k_begin) return CDE_OK;
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 127) / 128);
+int launch_mlp_backprop_sweep(const Control& x, const SweepIO& io, const Shape& n, const StageTable& st, hipStream_t s) {
+  if (io.k_end <= io.k_begin) return CDE_OK;
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 127) / 128);
   const size_t lds = (size_t)ADJ_LDS_FLOATS * sizeof(float);
-#define CDE_BP_L(D, A, X, CTV)                                                                                     \
-  do {                                                                                                             \
-    (void)hipFuncSetAttribute((const void*)rk4_adjoint_mlp_sweep<TT, D, A, X, CTV, false, true>,                   \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-    rk4_adjoint_mlp_sweep<TT, D, A, X, CTV, false, true><<<blocks, 512, lds, s>>>(                                 \
-        (const float*)coeffs, (const float*)knots, n_intervals, img, nullptr, (float*)g_state, (const TT*)grid,    \
-        k_begin, k_end, stage_index, (const float*)stage_frac, (float*)U, (float*)G2, (float*)G1, (float*)Z, B,    \
-        dims, (float*)grad_coeffs, (const float*)stages, n_steps_total);                                           \
-  } while (0)
-#define CDE_BP(D, A)                                                                                               \
-  do {                                                                                                             \
-    if (C > MC) { if (grad_coeffs) CDE_BP_L(D, A, true, 16); else CDE_BP_L(D, A, false, 16); }                     \
-    else if (grad_coeffs) CDE_BP_L(D, A, true, MC);                                                                \
-    else CDE_BP_L(D, A, false, MC);                                                                                \
-  } while (0)
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_BP(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_BP(CDE_PATH_LINEAR, CDE_ACT_NONE);
-  } else if (act == CDE_ACT_TANH) {
-    if (degree == CDE_PATH_CUBIC) CDE_BP(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_BP(CDE_PATH_LINEAR, CDE_ACT_TANH);
-  } else return CDE_ERR_UNSUPPORTED;
-#undef CDE_BP
-#undef CDE_BP_L
-  return check_launch();
+  const int rc = dispatch_degree_act(x.degree, io.act, [&](auto D, auto A) {
+    auto launch = [&](auto X, auto CT) {
+      allow_lds(rk4_adjoint_mlp_sweep<TT, D(), A(), X(), CT(), false, true>, lds);
+      rk4_adjoint_mlp_sweep<TT, D(), A(), X(), CT(), false, true><<<blocks, 512, lds, s>>>(
+          CDE_SWEEP_ARGS(nullptr), f32(io.grad_coeffs), f32(io.stages), io.n_steps);
+    };
+    auto tiles = [&](auto CT) {
+      if (io.grad_coeffs) launch(std::true_type{}, CT); else launch(std::false_type{}, CT);
+    };
+    if (n.C > MC) tiles(Const<16>{}); else tiles(Const<MC>{});
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
 }
-template int launch_mlp_backprop_sweep<float>(const void*, const void*, int64_t, int, int, const float*, const void*, int64_t,
-                                              void*, const void*, int64_t, int64_t, const int64_t*, const void*, void*, void*,
-                                              void*, void*, int64_t, int64_t, int64_t, void*, hipStream_t);
-template int launch_mlp_backprop_sweep<double>(const void*, const void*, int64_t, int, int, const float*, const void*, int64_t,
-                                               void*, const void*, int64_t, int64_t, const int64_t*, const void*, void*, void*,
-                                               void*, void*, int64_t, int64_t, int64_t, void*, hipStream_t);
+#undef CDE_SWEEP_ARGS
 
-template int launch_mlp_adjoint_sweep<float>(const void*, const void*, int64_t, int, int, const float*, void*, void*,
-                                             const void*, int64_t, int64_t, const int64_t*, const void*, void*, void*,
-                                             void*, void*, int64_t, int64_t, int64_t, void*, hipStream_t);
-template int launch_mlp_adjoint_sweep<double>(const void*, const void*, int64_t, int, int, const float*, void*, void*,
-                                              const void*, int64_t, int64_t, const int64_t*, const void*, void*, void*,
-                                              void*, void*, int64_t, int64_t, int64_t, void*, hipStream_t);
+#define CDE_INST(TT)                                                                                                  \
+  template int launch_mlp_adjoint_sweep<TT>(const Control&, const SweepIO&, const Shape&, const StageTable&, hipStream_t); \
+  template int launch_mlp_backprop_sweep<TT>(const Control&, const SweepIO&, const Shape&, const StageTable&, hipStream_t);
+CDE_INST(float)
+CDE_INST(double)
+#undef CDE_INST
 
 }  // namespace cde

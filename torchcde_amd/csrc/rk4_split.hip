@@ -28,6 +28,7 @@
 // is time, hence packed VALU, VGPR-form MFMA (no v_accvgpr moves; -mllvm -amdgpu-mfma-vgpr-form for this file) and
 // the control derivative computed once per tile and stage.
 #include "cde_split.h"
+#include "cde_launch.h"
 
 namespace cde {
 
@@ -536,79 +537,53 @@ __global__ __launch_bounds__(512, 1) void rk4_adjoint_split8(
   }
 }
 
-// defined in rk4_mfma.hip: fixed-order sum of the per-tile partials
-int launch_reduce_partials(const float* partial, int64_t n_tiles, void* grad_W, void* grad_b, int H, int C, hipStream_t s);
-
 // ------------------------------------------------------------------------------------------ host side
 size_t split_adjoint_partial_bytes(int64_t B) { return (size_t)((B + 15) / 16) * SPL_PARTIAL_FLOATS * sizeof(float); }
 
 template <typename TT>
-int launch_forward_split(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                         const void* bias, int act, const void* z0, const void* grid, int64_t n_grid, const void* t_out,
-                         int64_t n_out, void* z_out, int64_t B, int64_t C, int64_t H, const int64_t* stage_index,
-                         const void* stage_frac, hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 15) / 16);
-#define CDE_FWD(D, A)                                                                                                \
-  rk4_forward_split<TT, D, A><<<blocks, 256, 0, s>>>(                                                                \
-      (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias, (const float*)z0, \
-      (const TT*)grid, n_grid, (const TT*)t_out, n_out, (float*)z_out, B, stage_index, (const float*)stage_frac, dims)
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_FWD(CDE_PATH_LINEAR, CDE_ACT_NONE);
-  } else if (act == CDE_ACT_TANH) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_FWD(CDE_PATH_LINEAR, CDE_ACT_TANH);
-  } else return CDE_ERR_UNSUPPORTED;
-#undef CDE_FWD
-  return check_launch();
+int launch_forward_split(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                         hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 15) / 16);
+  const int rc = dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+    rk4_forward_split<TT, D(), A()><<<blocks, 256, 0, s>>>(
+        f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(f.bias), f32(io.z0), (const TT*)io.grid, io.n_grid,
+        (const TT*)io.t_out, io.n_out, f32(io.z_out), n.B, st.index, f32(st.frac), dims);
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
 }
 
 template <typename TT>
-int launch_adjoint_split(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                         const void* bias, int act, const void* z_saved, const void* grad_out, const void* sgrid,
-                         const int64_t* seg_off, int64_t n_out, void* grad_z0, void* grad_W, void* grad_b, int64_t B,
-                         int64_t C, int64_t H, const int64_t* stage_index, const void* stage_frac, float* partial,
-                         hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 15) / 16);
+int launch_adjoint_split(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
+                         float* partial, hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 15) / 16);
   const size_t lds = (size_t)SPL8_LDS_FLOATS * sizeof(float);
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-#define CDE_ADJ(D, A, J)                                                                                             \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)rk4_adjoint_split8<TT, D, A, J>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)lds);                                                                             \
-    rk4_adjoint_split8<TT, D, A, J><<<blocks, 512, lds, s>>>(                                                        \
-        (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias,                 \
-        (const float*)z_saved, (const float*)grad_out, (const TT*)sgrid, seg_off, n_out, (float*)grad_z0, partial,   \
-        B, stage_index, (const float*)stage_frac, dims);                                                             \
-  } while (0)
   const bool jacobian = option(CDE_OPT_K3_FORM) != 1;                // 1: the two-GEMM chain waves (tests, comparisons)
-  if (act == CDE_ACT_NONE && jacobian) {
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ(CDE_PATH_CUBIC, CDE_ACT_NONE, true); else CDE_ADJ(CDE_PATH_LINEAR, CDE_ACT_NONE, true);
-  } else if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ(CDE_PATH_CUBIC, CDE_ACT_NONE, false); else CDE_ADJ(CDE_PATH_LINEAR, CDE_ACT_NONE, false);
-  } else if (act == CDE_ACT_TANH) {
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ(CDE_PATH_CUBIC, CDE_ACT_TANH, false); else CDE_ADJ(CDE_PATH_LINEAR, CDE_ACT_TANH, false);
-  } else return CDE_ERR_UNSUPPORTED;
-#undef CDE_ADJ
-  int rc = check_launch();
+  int rc = dispatch_degree(x.degree, [&](auto D) -> int {
+    auto launch = [&](auto A, auto J) {
+      allow_lds(rk4_adjoint_split8<TT, D(), A(), J()>, lds);
+      rk4_adjoint_split8<TT, D(), A(), J()><<<blocks, 512, lds, s>>>(
+          f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(f.bias), f32(io.z_saved), f32(io.grad_out),
+          (const TT*)io.sgrid, io.seg_off, io.n_out, f32(io.grad_z0), partial, n.B, st.index, f32(st.frac), dims);
+      return CDE_OK;
+    };
+    if (f.act == CDE_ACT_NONE && jacobian) return launch(Const<CDE_ACT_NONE>{}, std::true_type{});
+    if (f.act == CDE_ACT_NONE) return launch(Const<CDE_ACT_NONE>{}, std::false_type{});
+    if (f.act == CDE_ACT_TANH) return launch(Const<CDE_ACT_TANH>{}, std::false_type{});
+    return CDE_ERR_UNSUPPORTED;
+  });
+  if (rc == CDE_OK) rc = check_launch();
   if (rc != CDE_OK) return rc;
-  return launch_reduce_partials(partial, (B + 15) / 16, grad_W, grad_b, (int)H, (int)C, s);
+  return launch_reduce_partials(partial, (n.B + 15) / 16, io.grad_W, io.grad_b, (int)n.H, (int)n.C, s);
 }
 
-template int launch_forward_split<float>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                         const void*, const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t,
-                                         int64_t, const int64_t*, const void*, hipStream_t);
-template int launch_forward_split<double>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                          const void*, const void*, int64_t, const void*, int64_t, void*, int64_t,
-                                          int64_t, int64_t, const int64_t*, const void*, hipStream_t);
-template int launch_adjoint_split<float>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                         const void*, const void*, const void*, const int64_t*, int64_t, void*, void*,
-                                         void*, int64_t, int64_t, int64_t, const int64_t*, const void*, float*,
-                                         hipStream_t);
-template int launch_adjoint_split<double>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                          const void*, const void*, const void*, const int64_t*, int64_t, void*, void*,
-                                          void*, int64_t, int64_t, int64_t, const int64_t*, const void*, float*,
-                                          hipStream_t);
+#define CDE_INST(TT)                                                                                                  \
+  template int launch_forward_split<TT>(const Control&, const AffineField&, const ForwardIO&, const Shape&, const StageTable&, hipStream_t); \
+  template int launch_adjoint_split<TT>(const Control&, const AffineField&, const AdjointIO&, const Shape&, const StageTable&, float*, hipStream_t);
+CDE_INST(float)
+CDE_INST(double)
+#undef CDE_INST
 
 }  // namespace cde

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "cde_split.h"
+#include "cde_launch.h"
 
 namespace cde {
 
@@ -425,11 +426,6 @@ __global__ void wide_unpack_kernel(const float* __restrict__ acc, float* __restr
 }
 
 // ------------------------------------------------------------------------------------------ host side
-// defined in mlp_grad_reduce.hip: acc (M, N + 1) += G^T [Z | 1] over `rows` rows, G (rows, M), Z (rows, N)
-int launch_wide_grad_reduce(const float* G, const float* Z, int64_t rows, int M, int N, float* acc, float* partial,
-                            hipStream_t s);
-size_t wide_grad_reduce_partial_bytes(int M, int N);
-
 bool wide_applicable(int64_t C, int64_t H, int dtype, int act) {
   const bool act_ok = act == CDE_ACT_NONE || act == CDE_ACT_TANH;
   return dtype == CDE_F32 && act_ok && H >= 1 && C >= 1 && ((H <= 64 && C <= 8) || (H <= 32 && C <= 16));
@@ -443,30 +439,20 @@ static size_t wide_sweep_lds() {
 }
 
 template <typename TT>
-int launch_forward_wide(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                        const void* bias, int act, const void* z0, const void* grid, int64_t n_grid, const void* t_out,
-                        int64_t n_out, void* z_out, int64_t B, int64_t C, int64_t H, const int64_t* stage_index,
-                        const void* stage_frac, hipStream_t s) {
-  const Dims dims{(int)H, (int)C};
-  const unsigned blocks = (unsigned)((B + 15) / 16);
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (act != CDE_ACT_NONE && act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
-#define CDE_FWD(D, A, NWV, NBV)                                                                                      \
-  rk4_forward_wide<TT, D, A, NWV, NBV><<<blocks, 64 * NWV, 0, s>>>(                                                  \
-      (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias, (const float*)z0, \
-      (const TT*)grid, n_grid, (const TT*)t_out, n_out, (float*)z_out, B, stage_index, (const float*)stage_frac, dims)
-#define CDE_FWD_SHAPE(D, A)                                                                                          \
-  do {                                                                                                               \
-    if (wide_tall(C)) CDE_FWD(D, A, 8, 2); else CDE_FWD(D, A, 4, 4);                                                 \
-  } while (0)
-  if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD_SHAPE(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_FWD_SHAPE(CDE_PATH_LINEAR, CDE_ACT_NONE);
-  } else {
-    if (degree == CDE_PATH_CUBIC) CDE_FWD_SHAPE(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_FWD_SHAPE(CDE_PATH_LINEAR, CDE_ACT_TANH);
-  }
-#undef CDE_FWD_SHAPE
-#undef CDE_FWD
-  return check_launch();
+int launch_forward_wide(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                        hipStream_t s) {
+  const Dims dims{(int)n.H, (int)n.C};
+  const unsigned blocks = (unsigned)((n.B + 15) / 16);
+  const int rc = dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+    auto launch = [&](auto NW, auto NB) {
+      rk4_forward_wide<TT, D(), A(), NW(), NB()><<<blocks, 64 * NW(), 0, s>>>(
+          f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(f.bias), f32(io.z0), (const TT*)io.grid, io.n_grid,
+          (const TT*)io.t_out, io.n_out, f32(io.z_out), n.B, st.index, f32(st.frac), dims);
+    };
+    if (wide_tall(n.C)) launch(Const<8>{}, Const<2>{}); else launch(Const<4>{}, Const<4>{});
+    return CDE_OK;
+  });
+  return rc != CDE_OK ? rc : check_launch();
 }
 
 // workspace of the backward pass behind the stage tables: [y | a | acc | reduction partials | G chunk | Z chunk]
@@ -505,18 +491,16 @@ WideLayout wide_layout(int64_t B, int64_t C, int64_t H, int64_t n_steps) {
 size_t wide_adjoint_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t n_steps) { return wide_layout(B, C, H, n_steps).total; }
 
 template <typename TT>
-int launch_adjoint_wide(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                        const void* bias, int act, const void* z_saved, const void* grad_out, const void* sgrid,
-                        int64_t n_sgrid, const int64_t* seg_off_host, int64_t n_out, void* grad_z0, void* grad_W,
-                        void* grad_b, int64_t B, int64_t C, int64_t H, const int64_t* stage_index,
-                        const void* stage_frac, void* scratch, hipStream_t s) {
+int launch_adjoint_wide(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
+                        void* scratch, hipStream_t s) {
+  const int64_t B = n.B, H = n.H, C = n.C;
   const Dims dims{(int)H, (int)C};
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (act != CDE_ACT_NONE && act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
+  if (x.degree != CDE_PATH_CUBIC && x.degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
+  if (f.act != CDE_ACT_NONE && f.act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
   // the chunk loop runs on the host and reads the segment offsets from the caller's HOST copy (`seg_off_host` of the C
   // ABI): no device-to-host copy, no stream synchronisation -- the call only queues work and is graph-capturable
-  if (n_out > 1 && !seg_off_host) return CDE_ERR_NULL;
-  const WideLayout L = wide_layout(B, C, H, n_sgrid - 1);
+  if (io.n_out > 1 && !io.seg_off_host) return CDE_ERR_NULL;
+  const WideLayout L = wide_layout(B, C, H, io.n_sgrid - 1);
   unsigned char* base = (unsigned char*)scratch;
   float* y_state = (float*)(base + L.off_y);
   float* a_state = (float*)(base + L.off_a);
@@ -527,62 +511,48 @@ int launch_adjoint_wide(const void* coeffs, const void* knots, int64_t n_interva
   const unsigned blocks = (unsigned)((B + 15) / 16);
   const unsigned seed_blocks = (unsigned)((B * H + 255) / 256);
   zero_async(acc, (size_t)L.HP * L.CT * (L.HP + 1) * sizeof(float), s);
-  wide_seed_kernel<<<seed_blocks, 256, 0, s>>>(y_state, a_state, (const float*)z_saved, (const float*)grad_out,
-                                               n_out - 1, n_out, B, (int)H, 1);
-#define CDE_SWEEP(D, A, NWV, NBV)                                                                                    \
-  do {                                                                                                               \
-    const size_t lds = wide_sweep_lds<NWV, NBV>();                                                                   \
-    (void)hipFuncSetAttribute((const void*)rk4_adjoint_wide_sweep<TT, D, A, NWV, NBV>,                               \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-    rk4_adjoint_wide_sweep<TT, D, A, NWV, NBV><<<blocks, 64 * NWV, lds, s>>>(                                        \
-        (const float*)coeffs, (const float*)knots, n_intervals, (const float*)W, (const float*)bias, y_state,        \
-        a_state, (const TT*)sgrid, k, ke, stage_index, (const float*)stage_frac, Gbuf, Zbuf, B, dims);               \
-  } while (0)
-#define CDE_SWEEP_SHAPE(D, A)                                                                                        \
-  do {                                                                                                               \
-    if (wide_tall(C)) CDE_SWEEP(D, A, 8, 2); else CDE_SWEEP(D, A, 4, 4);                                             \
-  } while (0)
-  for (int64_t p = 0; p + 1 < n_out; ++p) {
-    int64_t k = seg_off_host[p];
-    const int64_t k_end = seg_off_host[p + 1] - 1;
+  wide_seed_kernel<<<seed_blocks, 256, 0, s>>>(y_state, a_state, f32(io.z_saved), f32(io.grad_out), io.n_out - 1, io.n_out,
+                                               B, (int)H, 1);
+  auto sweep = [&](int64_t k, int64_t ke) {              // steps [k, ke) of the reversed grid
+    return dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+      auto launch = [&](auto NW, auto NB) {
+        const size_t lds = wide_sweep_lds<NW(), NB()>();
+        allow_lds(rk4_adjoint_wide_sweep<TT, D(), A(), NW(), NB()>, lds);
+        rk4_adjoint_wide_sweep<TT, D(), A(), NW(), NB()><<<blocks, 64 * NW(), lds, s>>>(
+            f32(x.coeffs), f32(x.knots), x.n_intervals, f32(f.W), f32(f.bias), y_state, a_state, (const TT*)io.sgrid, k, ke,
+            st.index, f32(st.frac), Gbuf, Zbuf, B, dims);
+      };
+      if (wide_tall(C)) launch(Const<8>{}, Const<2>{}); else launch(Const<4>{}, Const<4>{});
+      return CDE_OK;
+    });
+  };
+  for (int64_t p = 0; p + 1 < io.n_out; ++p) {
+    int64_t k = io.seg_off_host[p];
+    const int64_t k_end = io.seg_off_host[p + 1] - 1;
     while (k < k_end) {
       const int64_t ke = k + L.chunk_steps < k_end ? k + L.chunk_steps : k_end;
-      if (act == CDE_ACT_NONE) {
-        if (degree == CDE_PATH_CUBIC) CDE_SWEEP_SHAPE(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_SWEEP_SHAPE(CDE_PATH_LINEAR, CDE_ACT_NONE);
-      } else {
-        if (degree == CDE_PATH_CUBIC) CDE_SWEEP_SHAPE(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_SWEEP_SHAPE(CDE_PATH_LINEAR, CDE_ACT_TANH);
-      }
+      sweep(k, ke);
       int rc = check_launch();
       if (rc != CDE_OK) return rc;
       rc = launch_wide_grad_reduce(Gbuf, Zbuf, 4 * (ke - k) * ((B + 15) / 16 * 16), L.HP * L.CT, L.HP, acc, partial, s);
       if (rc != CDE_OK) return rc;
       k = ke;
     }
-    wide_seed_kernel<<<seed_blocks, 256, 0, s>>>(y_state, a_state, (const float*)z_saved, (const float*)grad_out,
-                                                 n_out - 2 - p, n_out, B, (int)H, 0);
+    wide_seed_kernel<<<seed_blocks, 256, 0, s>>>(y_state, a_state, f32(io.z_saved), f32(io.grad_out), io.n_out - 2 - p,
+                                                 io.n_out, B, (int)H, 0);
   }
-#undef CDE_SWEEP_SHAPE
-#undef CDE_SWEEP
-  if (hipMemcpyAsync(grad_z0, a_state, (size_t)B * H * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+  if (hipMemcpyAsync(io.grad_z0, a_state, (size_t)B * H * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
     return CDE_ERR_LAUNCH;
-  wide_unpack_kernel<<<(unsigned)((H * C * (H + 1) + 255) / 256), 256, 0, s>>>(acc, (float*)grad_W, (float*)grad_b, (int)H,
+  wide_unpack_kernel<<<(unsigned)((H * C * (H + 1) + 255) / 256), 256, 0, s>>>(acc, f32(io.grad_W), f32(io.grad_b), (int)H,
                                                                                (int)C, L.HP, L.CT);
   return check_launch();
 }
 
-template int launch_forward_wide<float>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                        const void*, const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t,
-                                        int64_t, const int64_t*, const void*, hipStream_t);
-template int launch_forward_wide<double>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                         const void*, const void*, int64_t, const void*, int64_t, void*, int64_t, int64_t,
-                                         int64_t, const int64_t*, const void*, hipStream_t);
-template int launch_adjoint_wide<float>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                        const void*, const void*, const void*, int64_t, const int64_t*, int64_t, void*,
-                                        void*, void*, int64_t, int64_t, int64_t, const int64_t*, const void*, void*,
-                                        hipStream_t);
-template int launch_adjoint_wide<double>(const void*, const void*, int64_t, int, const void*, const void*, int,
-                                         const void*, const void*, const void*, int64_t, const int64_t*, int64_t, void*,
-                                         void*, void*, int64_t, int64_t, int64_t, const int64_t*, const void*, void*,
-                                         hipStream_t);
+#define CDE_INST(TT)                                                                                                  \
+  template int launch_forward_wide<TT>(const Control&, const AffineField&, const ForwardIO&, const Shape&, const StageTable&, hipStream_t); \
+  template int launch_adjoint_wide<TT>(const Control&, const AffineField&, const AdjointIO&, const Shape&, const StageTable&, void*, hipStream_t);
+CDE_INST(float)
+CDE_INST(double)
+#undef CDE_INST
 
 }  // namespace cde
