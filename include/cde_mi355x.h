@@ -53,6 +53,16 @@ enum { CDE_EVAL_VALUE = 0, CDE_EVAL_DERIVATIVE = 1 };
  * example/irregular_data.py:36-46.                                                       */
 enum { CDE_ACT_NONE = 0, CDE_ACT_TANH = 1 };
 
+/* The two-layer fields f(z) = act( W2 hidden(W1 z + b1) + b2 ) carry their hidden activation in the same `int act`:
+ * the final activation (CDE_ACT_*) in bits 0-3 as ever, the hidden one in bits 4-7, so act = 0 / 1 keeps meaning
+ * relu inside.  CDE_HIDDEN_SOFTPLUS is softplus with beta 1 and threshold 20 (torch.nn.functional.softplus's defaults).
+ * Every two-layer entry point answers a hidden code it does not know (or any higher bit) with CDE_ERR_UNSUPPORTED
+ * from its argument checks; the one-layer entry points accept CDE_ACT_NONE / CDE_ACT_TANH alone.                  */
+enum { CDE_HIDDEN_RELU = 0, CDE_HIDDEN_SOFTPLUS = 1 };
+#define CDE_FIELD_ACT(final_act, hidden_act) ((final_act) | ((hidden_act) << 4))
+#define CDE_FIELD_FINAL(act) ((act) & 15)
+#define CDE_FIELD_HIDDEN(act) (((act) >> 4) & 15)
+
 /* kernel selection for the fused solvers */
 enum {
   CDE_VARIANT_AUTO = 0,    /* f32: the MFMA kernels for H <= 32, C <= 8 (identity or tanh), the wide tile kernels for
@@ -302,6 +312,8 @@ int cde_rk4_forward_linear(const void* coeffs, const void* knots, int64_t n_inte
  * (example/time_series_classification.py:20-51: Linear(H,128) -> relu -> Linear(128,H*C) -> tanh);
  * replaces the same reference code as K2 plus the user module's two nn.Linear calls per stage.
  *   W1 (width, H), bias1 (width), W2 (H*C, width), bias2 (H*C);  act applies after the second layer.
+ * `act` = CDE_FIELD_ACT(final, hidden) here and in every other two-layer entry point (K3m, K4 with W1, K4am):
+ * hidden = CDE_HIDDEN_SOFTPLUS puts softplus in place of the relu.
  * f32 only, width <= 128, and (H <= 32, C <= 8) or (H <= 16, C <= 16) -- the sixteen 16-row MFMA tiles of the
  * second layer hold 32 hidden units x 8 channels or 16 x 16, zero padded; otherwise CDE_ERR_UNSUPPORTED.
  * (The 16 x 16 tiling takes the 14-channel depth-3 logsignature control of example/logsignature_example.py:22.)
@@ -333,7 +345,8 @@ int cde_mlp_grad_reduce(const void* G, const void* X, int64_t rows, int layer, v
  *     [dL/dW2 | dL/db2] = G2^T U        [dL/dW1 | dL/db1] = G1^T Z
  *   scratch rows: row = (local_stage * B + series), local_stage = 4*(k - k_begin) + rk_stage
  *     U  (rows, 132) f32: relu(W1 z + b1) in columns 0..127 (zero beyond `width`); the CALLER sets column 128 to 1
- *                         and 129..131 to 0 once (the kernel never writes them)
+ *                         and 129..131 to 0 once (the kernel never writes them).  With CDE_HIDDEN_SOFTPLUS the columns
+ *                         beyond `width` hold softplus(0) = ln 2: the caller takes columns 0..width-1 of G2^T U
  *     G2 (rows, 256) f32: quadrature-weighted dL/dY2, column h*8 + c (zero beyond the real H, C)
  *     G1 (rows, 128) f32: quadrature-weighted dL/dY1
  *     Z  (rows, 36)  f32: z in columns 0..H-1; the CALLER zeroes the buffer and sets column 32 to 1 once

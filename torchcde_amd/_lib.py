@@ -38,6 +38,14 @@ F32, F64 = 0, 1
 PATH_LINEAR, PATH_CUBIC = 1, 3
 EVAL_VALUE, EVAL_DERIVATIVE = 0, 1
 ACT_NONE, ACT_TANH = 0, 1
+HIDDEN_RELU, HIDDEN_SOFTPLUS = 0, 1      # CDE_HIDDEN_*: the two-layer fields' hidden activation, bits 4-7 of their `act`
+
+
+def field_act(final_act, hidden_act=HIDDEN_RELU):
+    """CDE_FIELD_ACT of include/cde_mi355x.h: the `int act` of a two-layer entry point."""
+    return final_act | (hidden_act << 4)
+
+
 VARIANT_AUTO, VARIANT_GENERIC, VARIANT_MFMA, VARIANT_SPLIT, VARIANT_BF16X3 = 0, 1, 2, 3, 4
 METHOD_RK4, METHOD_MIDPOINT, METHOD_EULER = 0, 1, 2
 FIXED_METHODS = {"rk4": METHOD_RK4, "midpoint": METHOD_MIDPOINT, "euler": METHOD_EULER}

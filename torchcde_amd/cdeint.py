@@ -209,12 +209,20 @@ def _grids_for(t_host, step_size, adjoint_step_size, device):
 
 
 def _field_values(act, weights, z):
-    """F(z) of a fused field, (..., H * C): Linear(H, H * C) -- weights (W, b) -- or the two-layer Linear -> relu -> Linear --
-    weights (W1, b1, W2, b2) -- followed by the field's activation."""
+    """F(z) of a fused field, (..., H * C): Linear(H, H * C) -- weights (W, b) -- or the two-layer Linear -> relu | softplus ->
+    Linear -- weights (W1, b1, W2, b2) -- followed by the field's activation.  `act`: the field's `code` (final activation in
+    bits 0-3, the two-layer field's hidden one in bits 4-7)."""
     if len(weights) == 4:
-        z = torch.nn.functional.linear(z, weights[0], weights[1]).relu()
+        z = torch.nn.functional.linear(z, weights[0], weights[1])
+        z = torch.nn.functional.softplus(z) if (act >> 4) == _lib.HIDDEN_SOFTPLUS else z.relu()
     y = torch.nn.functional.linear(z, weights[-2], weights[-1])
-    return y.tanh() if act == _lib.ACT_TANH else y
+    return y.tanh() if (act & 15) == _lib.ACT_TANH else y
+
+
+def _abi_act(field):
+    """The `int act` of the C ABI for a recognised field: its final activation, and in bits 4-7 the hidden activation of a
+    two-layer field (include/cde_mi355x.h: CDE_FIELD_ACT; an affine field has none)."""
+    return _lib.field_act(field.act, getattr(field, "hidden_act", _lib.HIDDEN_RELU))
 
 
 def _weight_args(weights):
@@ -424,7 +432,7 @@ class _MlpPlan:
         coeffs, knots, _ = path._native_inputs()
         self.coeffs, self.knots = coeffs, knots
         self.n_intervals, self.degree = path._n_intervals(), path._degree
-        self.field, self.act, self.batch, self.B, self.H, self.C = field, field.act, batch, coeffs.size(0), H, C
+        self.field, self.act, self.batch, self.B, self.H, self.C = field, _abi_act(field), batch, coeffs.size(0), H, C
         self.path = path
         self.device = coeffs.device
         self.grids = _grids_for(_to_host(t), step_size, step_size if adjoint_step_size is None else adjoint_step_size,
@@ -842,7 +850,7 @@ class _Dopri5Plan:
         coeffs, knots, _ = path._native_inputs()
         self.coeffs, self.knots = coeffs, knots
         self.path = path
-        self.n_intervals, self.degree, self.act = path._n_intervals(), path._degree, field.act
+        self.n_intervals, self.degree, self.act = path._n_intervals(), path._degree, _abi_act(field)
         self.hidden = field.hidden if field.kind == "mlp2" else None      # two-layer field: its first Linear
         self.batch, self.B, self.H, self.C = batch, coeffs.size(0), H, C
         self.dtype, self.device = coeffs.dtype, coeffs.device

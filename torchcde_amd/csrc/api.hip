@@ -226,6 +226,7 @@ extern "C" int cde_rk4_forward_mlp(const void* coeffs, const void* knots, int64_
                                    int time_dtype, int64_t* stage_index, void* stage_frac, void* stream) {
   if (B < 0 || C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_grid < 1 || n_out < 1) return CDE_ERR_SHAPE;
   if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
+  if (!field_act_known(act)) return CDE_ERR_UNSUPPORTED;
   if (B == 0) return CDE_OK;
   if (!coeffs || !knots || !W1 || !bias1 || !W2 || !bias2 || !z0 || !grid || !t_out || !z_out) return CDE_ERR_NULL;
   if (n_grid > 1 && (!stage_index || !stage_frac)) return CDE_ERR_NULL;
@@ -479,6 +480,7 @@ extern "C" int cde_rk4_forward_mlp_stages(const void* coeffs, const void* knots,
                                           void* stream) {
   if (B < 0 || C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_grid < 1 || n_out < 1) return CDE_ERR_SHAPE;
   if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
+  if (!field_act_known(act)) return CDE_ERR_UNSUPPORTED;
   if (B == 0) return CDE_OK;
   if (!coeffs || !knots || !W1 || !bias1 || !W2 || !bias2 || !z0 || !grid || !t_out || !z_out) return CDE_ERR_NULL;
   if (n_grid > 1 && (!stage_index || !stage_frac || !stages)) return CDE_ERR_NULL;
@@ -510,6 +512,7 @@ static int mlp_sweep_impl(bool backprop, const Control& x, SweepIO io, int64_t n
     return CDE_ERR_SHAPE;
   if (d.state != CDE_F32) return d.state == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
   if (!mlp_shape_ok(n.C, n.H, 1) && !mlp_shape_upper(n.C, n.H, 1)) return CDE_ERR_UNSUPPORTED;
+  if (!field_act_known(io.act)) return CDE_ERR_UNSUPPORTED;
   if (!x.coeffs || !x.knots || !(backprop ? io.stages : io.y_state) || !io.a_state || !io.grid || !io.U || !io.G2 || !io.G1 ||
       !io.Z || !ws.base)
     return CDE_ERR_NULL;

@@ -66,6 +66,22 @@ template <typename F>
 int dispatch_degree_act(int degree, int act, F&& f) {
   return dispatch_degree(degree, [&](auto D) { return dispatch_act(act, [&](auto A) { return f(D, A); }); });
 }
+// the two-layer fields: `act` = CDE_FIELD_ACT(final, hidden), handed to the kernels whole (cde_mfma.h: final_tanh, hidden_softplus)
+constexpr int FIELD_SOFTPLUS_NONE = CDE_FIELD_ACT(CDE_ACT_NONE, CDE_HIDDEN_SOFTPLUS);
+constexpr int FIELD_SOFTPLUS_TANH = CDE_FIELD_ACT(CDE_ACT_TANH, CDE_HIDDEN_SOFTPLUS);
+static inline bool field_act_known(int act) {
+  return (act & ~0xff) == 0 && (CDE_FIELD_FINAL(act) == CDE_ACT_NONE || CDE_FIELD_FINAL(act) == CDE_ACT_TANH) &&
+         (CDE_FIELD_HIDDEN(act) == CDE_HIDDEN_RELU || CDE_FIELD_HIDDEN(act) == CDE_HIDDEN_SOFTPLUS);
+}
+template <typename F>
+int dispatch_degree_field(int degree, int act, F&& f) {
+  if (!field_act_known(act)) return CDE_ERR_UNSUPPORTED;
+  return dispatch_degree(degree, [&](auto D) -> int {
+    if (CDE_FIELD_HIDDEN(act) == CDE_HIDDEN_RELU) return dispatch_act(act, [&](auto A) { return f(D, A); });
+    if (act == FIELD_SOFTPLUS_NONE) return f(D, Const<FIELD_SOFTPLUS_NONE>{});
+    return f(D, Const<FIELD_SOFTPLUS_TANH>{});
+  });
+}
 // `kernel`'s dynamic LDS limit, raised to what the launch asks for
 template <typename K>
 void allow_lds(K kernel, size_t bytes) {
@@ -160,7 +176,7 @@ int launch_wide_grad_reduce(const float* G, const float* Z, int64_t rows, int M,
 // ---------------------------------------------------------------- rk4_mlp_adjoint.hip (sweeps of the two-layer field)
 size_t mlp_adjoint_image_bytes();                              // (cde_mlp_adj.h declares these two for the kernel files)
 int launch_mlp_adjoint_images(const void* W1, const void* b1, int64_t width, const void* W2, const void* b2, int64_t C,
-                              int64_t H, float* img, hipStream_t s);
+                              int64_t H, float* img, hipStream_t s, float b1_pad = 0.f);
 template <typename TT>
 int launch_mlp_adjoint_sweep(const Control& x, const SweepIO& io, const Shape& n, const StageTable& st, hipStream_t s);
 template <typename TT>

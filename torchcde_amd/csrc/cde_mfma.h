@@ -316,8 +316,12 @@ __device__ __forceinline__ float tanh_fast(float x) {
   const float small = __builtin_fmaf(ax * x2, p, ax);
   return __builtin_copysignf(ax < 0.25f ? small : big, x);
 }
+// ACT of a two-layer kernel is the entry point's whole code, CDE_FIELD_ACT(final, hidden); the one-layer kernels pass the
+// final activation alone (hidden bits zero), so both kinds share these helpers.
+constexpr bool final_tanh(int act) { return CDE_FIELD_FINAL(act) == CDE_ACT_TANH; }
+constexpr bool hidden_softplus(int act) { return CDE_FIELD_HIDDEN(act) == CDE_HIDDEN_SOFTPLUS; }
 template <int ACT>
-__device__ __forceinline__ float activate(float y) { return ACT == CDE_ACT_TANH ? tanh_fast(y) : y; }
+__device__ __forceinline__ float activate(float y) { return final_tanh(ACT) ? tanh_fast(y) : y; }
 
 // two at a time: the polynomial / affine parts become v_pk_mul / v_pk_add / v_pk_fma (9 packed + 12 scalar
 // instructions per pair instead of 2 x 14); same operations, same results as tanh_fast
@@ -338,7 +342,43 @@ __device__ __forceinline__ f32x2 tanh_fast2(f32x2 x) {
 }
 template <int ACT>
 __device__ __forceinline__ f32x2 activate2(float y0, float y1) {
-  return ACT == CDE_ACT_TANH ? tanh_fast2(f32x2{y0, y1}) : f32x2{y0, y1};
+  return final_tanh(ACT) ? tanh_fast2(f32x2{y0, y1}) : f32x2{y0, y1};
+}
+
+// softplus(x) = log(1 + exp(x)) (beta 1) as max(x, 0) + log1p(exp(-|x|)): nothing overflows, and above torch's
+// threshold of 20 the second term (< 2.1e-9) is below half an ulp of x, so the sum IS x -- torch's linear branch
+// without a select.  t = exp(-|x|) on v_exp_f32; log1p(t) on v_log_f32 for t >= 2^-10 and as t - t^2/2 + t^3/3 below
+// (where 1 + t would round away the low bits of t; truncation < t^4/4 < 2.3e-13), so the negative tail keeps its
+// relative accuracy (softplus(x) -> exp(x), to ~2e-6 relative: the rounding of |x| log2(e)).  Absolute error: the rounding
+// of 1 + t (<= 6e-8), 1 ulp each of v_exp_f32 / v_log_f32 and the final sum's half ulp.  The same operations in float32 with
+// correctly rounded exp2 / log2, against float64 over [-30, 30]: 1.7e-7 for |x| <= 1, elsewhere within 1e-7 of half an ulp
+// of the result (4.8e-7 at x = 8.7); the hardware's two 1-ulp instructions add at most ~1e-7 to that.  A dozen VALU
+// instructions, two of them transcendental.
+__device__ __forceinline__ float softplus_fast(float x) {
+  const float ax = __builtin_fabsf(x);
+  const float t = __builtin_amdgcn_exp2f(ax * -1.4426950408889634f);           // exp(-|x|) in (0, 1]
+  const float lg = __builtin_amdgcn_logf(1.f + t) * 0.6931471805599453f;       // v_log_f32 is log2
+  float p = __builtin_fmaf(t, 1.f / 3.f, -0.5f);
+  p = __builtin_fmaf(t, p, 1.f);
+  return __builtin_fmaxf(x, 0.f) + (t < 0.0009765625f ? t * p : lg);
+}
+// its slope sigmoid(x), from the VALUE u = softplus(x): 1 - exp(-u) (one v_exp_f32 and a subtraction; 1.2e-7
+// absolute against sigmoid(x) in the same emulation: u's own error and 1 ulp of exp(-u) in (0, 1)).  The backward passes re-derive the slope from the u they hold as
+// layer 2's B operands instead of carrying 32 more floats per lane across layer 2 (profiles/NOTES.md).
+__device__ __forceinline__ float softplus_slope_from_value(float u) {
+  return 1.f - __builtin_amdgcn_exp2f(u * -1.4426950408889634f);
+}
+// hidden activation of the two-layer fields and dL/dpre = g * hidden'(pre) from what the relu path carries (`positive`: its
+// mask bit) or the softplus path (`u`: the value)
+template <int ACT>
+__device__ __forceinline__ float hidden_activate(float pre) {
+  if constexpr (hidden_softplus(ACT)) return softplus_fast(pre);
+  else return fmaxf(pre, 0.f);
+}
+template <int ACT>
+__device__ __forceinline__ float hidden_backward(float g, bool positive, float u) {
+  if constexpr (hidden_softplus(ACT)) return g * softplus_slope_from_value(u);
+  else return positive ? g : 0.f;
 }
 
 // stage the weight and bias images in LDS (they stay there: [WY_FLOATS weight][BY_FLOATS bias])
@@ -421,7 +461,7 @@ __device__ __forceinline__ void field_act16_split(const float4* wy, const float4
 }
 
 // ============================================================================ two-layer fields
-// f(z) = reshape_{HxC}(act(W2 relu(W1 z + b1) + b2)) dX   (reference example/time_series_classification.py:20-51:
+// f(z) = reshape_{HxC}(act(W2 hidden(W1 z + b1) + b2)) dX, hidden = relu | softplus   (reference example/time_series_classification.py:20-51:
 // Linear(H, width) -> relu -> Linear(width, H*C) -> tanh, width = 128).  Same tiling as field_act16 with a hidden
 // layer in front: layer 1 is 8 tiles (width padded to 128) x 8 K steps whose C/D fragment -- lane (n, q) holds
 // hidden-layer units 16*T1 + 4q + r -- is exactly the B operand of layer 2's K step (T1, r), so the hidden layer
@@ -431,7 +471,7 @@ constexpr int W1M_FLOATS = 8 * 2 * 64 * 4;           // layer 1: 8 tiles x 2 gro
 constexpr int B1M_FLOATS = 8 * 4 * 4;                // [tile][q][r]
 constexpr int W2M_FLOATS = 16 * 8 * 64 * 4;          // layer 2: 16 tiles x 8 groups of 4 K steps
 constexpr int MLP16_LDS_FLOATS = W1M_FLOATS + B1M_FLOATS + W2M_FLOATS + BY_FLOATS;
-struct MlpDims { int H, C, width; };
+struct MlpDims { int H, C, width; float b1_pad = 0.f; };     // b1_pad: bias of the hidden-layer units beyond `width` (cde_mlp_adj.h)
 bool mlp_shape_ok(int64_t C, int64_t H, int64_t width);     // rk4_mfma.hip
 // 32 hidden units x 16 channels (round 6; config 5 at hidden size 32: 14 logsignature channels): twice the 16 tiles.  The LDS
 // images hold unit groups 0..3 as before; groups 4..7 (hidden units 16..31) are read straight from the caller's output-layer
@@ -455,7 +495,7 @@ __device__ __forceinline__ float mlp16_image(const float* __restrict__ W1, const
   e -= W1M_FLOATS;
   if (e < B1M_FLOATS) {
     const int unit = 16 * (e >> 4) + 4 * ((e >> 2) & 3) + (e & 3);
-    return unit < d.width ? b1[unit] : 0.f;
+    return unit < d.width ? b1[unit] : d.b1_pad;
   }
   e -= B1M_FLOATS;
   if (e < W2M_FLOATS) {
@@ -509,7 +549,7 @@ __device__ __forceinline__ void field_mlp16(const float* img, int lane, int q, c
 #pragma unroll
       for (int s = 0; s < 8; ++s) y0 = mfma16(a0[s], zs[s], y0);      // one chain, bias first: the bits of the unsplit form
       *reinterpret_cast<float4*>(xu + (pw * 64 + lane) * 4) =
-          make_float4(fmaxf(y0[0], 0.f), fmaxf(y0[1], 0.f), fmaxf(y0[2], 0.f), fmaxf(y0[3], 0.f));
+          make_float4(hidden_activate<ACT>(y0[0]), hidden_activate<ACT>(y0[1]), hidden_activate<ACT>(y0[2]), hidden_activate<ACT>(y0[3]));
     }
     __syncthreads();
     f32x4 y[2];
@@ -565,7 +605,7 @@ __device__ __forceinline__ void field_mlp16(const float* img, int lane, int q, c
 #pragma unroll
     for (int s = 0; s < 8; ++s) { y0 = mfma16(a0[s], zs[s], y0); y1 = mfma16(a1[s], zs[s], y1); }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { u[8 * TP + r] = fmaxf(y0[r], 0.f); u[8 * TP + 4 + r] = fmaxf(y1[r], 0.f); }
+    for (int r = 0; r < 4; ++r) { u[8 * TP + r] = hidden_activate<ACT>(y0[r]); u[8 * TP + 4 + r] = hidden_activate<ACT>(y1[r]); }
   }
   // ---- layer 2 + activation + contraction, one unit group (4 hidden units x CT channels = NB tiles) at a time
   fa = f32x4{0.f, 0.f, 0.f, 0.f};

@@ -44,7 +44,7 @@ __device__ __forceinline__ void plain_store4(float* p, float a, float b, float c
 // One evaluation of the augmented dynamics of the two-layer field for the 16 series of a wave (lane (n, q) owns hidden
 // units q, 4+q, .., 28+q of z and a): f = F(z) dX, va = a^T dF/dz dX, and -- when `stream` -- the UNWEIGHTED factors of
 // the parameter gradients of this evaluation, one row per series:
-//     U  [132]  relu(W1 z + b1) | 1 | 0 0 0        G2 [256]  dL/dY2 = a_h dX_c act'(Y2)   (padded (h, c) layout)
+//     U  [132]  hidden(W1 z + b1) | 1 | 0 0 0       G2 [256]  dL/dY2 = a_h dX_c act'(Y2)   (padded (h, c) layout)
 //     Z  [36]   z | 1 | 0 0 0                      G1 [128]  dL/dY1
 // (the "1" columns are written once by the host; dW2 | db2 = G2^T U, dW1 | db1 = G1^T Z).  The body is K3m's (same
 // MFMA order, same LDS reads); TGRAD adds kt = a . (F(z) d2X/dt2), the slope of vjp_t (cde_dopri_adj.h).
@@ -115,6 +115,7 @@ __device__ __forceinline__ void mlp_adjoint_eval(const float* lds_base, const fl
   //  registers for the launch -- `w1t_regs`, indexed by compile-time constants only -- instead of 16 L2 loads per call)
 
   // ---- layer 1: u = relu(W1 z + b1); `mask` bit s2 = (pre-activation of the lane's s2-th hidden unit > 0)
+  // (softplus: u alone -- its slope is re-derived from u below, the mask is dead code)
   float u[32];
   unsigned mask = 0;
 #pragma unroll
@@ -128,8 +129,8 @@ __device__ __forceinline__ void mlp_adjoint_eval(const float* lds_base, const fl
     for (int s = 0; s < 8; ++s) { y0 = mfma16(a0[s], zs[s], y0); y1 = mfma16(a1[s], zs[s], y1); }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      u[8 * TP + r] = fmaxf(y0[r], 0.f);
-      u[8 * TP + 4 + r] = fmaxf(y1[r], 0.f);
+      u[8 * TP + r] = hidden_activate<ACT>(y0[r]);
+      u[8 * TP + 4 + r] = hidden_activate<ACT>(y1[r]);
       mask |= (y0[r] > 0.f ? 1u : 0u) << (8 * TP + r);
       mask |= (y1[r] > 0.f ? 1u : 0u) << (8 * TP + 4 + r);
     }
@@ -201,7 +202,7 @@ __device__ __forceinline__ void mlp_adjoint_eval(const float* lds_base, const fl
         f = c == 0 ? t * dX[0] : __builtin_fmaf(t, dX[c], f);
         if (TGRAD) h2 = __builtin_fmaf(t, d2X[c], h2);
         if constexpr (DCTRL) gxl[c] = __builtin_fmaf(as_P, t, gxl[c]);
-        const float slope = ACT == CDE_ACT_TANH ? __builtin_fmaf(-t, t, 1.f) : 1.f;
+        const float slope = final_tanh(ACT) ? __builtin_fmaf(-t, t, 1.f) : 1.f;
         g2[c] = as_P * (dX[c] * slope);
       }
     }
@@ -283,10 +284,10 @@ __device__ __forceinline__ void mlp_adjoint_eval(const float* lds_base, const fl
     }
   }
   CDE_EVAL_STAMP(2, "+v"(gu[0]), "+v"(gu[7]));
-  // ---- dL/dY1 = gu * relu'(pre1);  va = W1^T dL/dY1
+  // ---- dL/dY1 = gu * hidden'(pre1);  va = W1^T dL/dY1
   float g1[32];
 #pragma unroll
-  for (int s2 = 0; s2 < 32; ++s2) g1[s2] = (mask >> s2) & 1u ? gu[s2 >> 2][s2 & 3] : 0.f;
+  for (int s2 = 0; s2 < 32; ++s2) g1[s2] = hidden_backward<ACT>(gu[s2 >> 2][s2 & 3], (mask >> s2) & 1u, u[s2]);
   if (stream && writer) {
 #pragma unroll
     for (int T1 = 0; T1 < 8; ++T1)
@@ -355,7 +356,7 @@ __device__ __forceinline__ void mlp_adjoint_eval_split8(const float* lds_base, f
   float uo[4];
   unsigned mask = 0;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) { uo[r] = fmaxf(y1[r], 0.f); mask |= (y1[r] > 0.f ? 1u : 0u) << r; }
+  for (int r = 0; r < 4; ++r) { uo[r] = hidden_activate<ACT>(y1[r]); mask |= (y1[r] > 0.f ? 1u : 0u) << r; }
   *reinterpret_cast<float4*>(xb + (w * 64 + lane) * 4) = make_float4(uo[0], uo[1], uo[2], uo[3]);
   if (stream) {
     store4(urow + 16 * w, uo[0], uo[1], uo[2], uo[3]);
@@ -397,7 +398,7 @@ __device__ __forceinline__ void mlp_adjoint_eval_split8(const float* lds_base, f
       const float t = tv[r];
       f = c == 0 ? t * dX[0] : __builtin_fmaf(t, dX[c], f);
       if (TGRAD) h2 = __builtin_fmaf(t, d2X[c], h2);
-      const float slope = ACT == CDE_ACT_TANH ? __builtin_fmaf(-t, t, 1.f) : 1.f;
+      const float slope = final_tanh(ACT) ? __builtin_fmaf(-t, t, 1.f) : 1.f;
       g2[c] = as_w * (dX[c] * slope);
     }
   }
@@ -427,10 +428,10 @@ __device__ __forceinline__ void mlp_adjoint_eval_split8(const float* lds_base, f
     }
   }
   const f32x4 gu = gua + gub;
-  // ---- dL/dY1 = gu * relu'(pre1) for its units; its share of va = W1^T dL/dY1
+  // ---- dL/dY1 = gu * hidden'(pre1) for its units; its share of va = W1^T dL/dY1
   float g1[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) g1[r] = (mask >> r) & 1u ? gu[r] : 0.f;
+  for (int r = 0; r < 4; ++r) g1[r] = hidden_backward<ACT>(gu[r], (mask >> r) & 1u, uo[r]);
   if (stream) store4(g1row + 16 * w, g1[0] * wq, g1[1] * wq, g1[2] * wq, g1[3] * wq);
   f32x4 pa = {0.f, 0.f, 0.f, 0.f}, pb = pa;
   pa = mfma16(w1tr[0].x, g1[0], pa); pb = mfma16(w1tr[1].x, g1[0], pb);
@@ -462,9 +463,13 @@ __device__ __forceinline__ void mlp_adjoint_eval_split8(const float* lds_base, f
 #undef CDE_EVAL_STAMP
 }
 
-// host side of the images (rk4_mlp_adjoint.hip)
+// host side of the images (rk4_mlp_adjoint.hip).  `b1_pad`: the bias of the hidden-layer units beyond `width` -- relu(0) = 0
+// keeps them out of every product, softplus(0) = ln 2 would put them into the U rows (harmless for the weights, whose columns
+// beyond `width` are zero, but K4am's error norm runs over the whole gradient image): K4am pads with SOFTPLUS_PAD_BIAS there,
+// at which softplus_fast and its slope are exactly 0.
+constexpr float SOFTPLUS_PAD_BIAS = -1e30f;
 size_t mlp_adjoint_image_bytes();
 int launch_mlp_adjoint_images(const void* W1, const void* b1, int64_t width, const void* W2, const void* b2, int64_t C,
-                              int64_t H, float* img, hipStream_t s);
+                              int64_t H, float* img, hipStream_t s, float b1_pad);
 
 }  // namespace cde

@@ -1122,7 +1122,8 @@ static int dopri5_advance_impl(const void* coeffs, const void* knots, int64_t n_
   const bool mlp_upper = mlp && cde::mlp_shape_hi(C, H, width) && ((uintptr_t)W & 15) == 0;     // 32 units x 16 channels (cde_mfma.h: MlpHi)
   if (mlp && (dtype != CDE_F32 || !(cde::mlp_shape_ok(C, H, width) || mlp_upper) || variant == CDE_VARIANT_GENERIC))
     return CDE_ERR_UNSUPPORTED;
-  if (act != CDE_ACT_NONE && act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
+  // (the two-layer field's `act` carries its hidden activation: CDE_FIELD_ACT)
+  if (mlp ? !cde::field_act_known(act) : (act != CDE_ACT_NONE && act != CDE_ACT_TANH)) return CDE_ERR_UNSUPPORTED;
   if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
   if (!coeffs || !knots || !W || !bias || !z0 || !t_out || !z_out || !workspace) return CDE_ERR_NULL;
   if (n_jump > 0 && !jump_t) return CDE_ERR_NULL;
@@ -1223,11 +1224,15 @@ static int dopri5_advance_impl(const void* coeffs, const void* knots, int64_t n_
   do {                                                                                                             \
     if (mlp_upper) CDE_MLP_CT(D, A, 16, true); else if (C > cde::MC) CDE_MLP_CT(D, A, 16, false); else CDE_MLP_CT(D, A, cde::MC, false); \
   } while (0)
-      if (act == CDE_ACT_NONE) {
-        if (degree == CDE_PATH_CUBIC) CDE_MLP(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_MLP(CDE_PATH_LINEAR, CDE_ACT_NONE);
-      } else {
-        if (degree == CDE_PATH_CUBIC) CDE_MLP(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_MLP(CDE_PATH_LINEAR, CDE_ACT_TANH);
-      }
+#define CDE_MLP_D(A)                                                                                               \
+  do {                                                                                                             \
+    if (degree == CDE_PATH_CUBIC) CDE_MLP(CDE_PATH_CUBIC, A); else CDE_MLP(CDE_PATH_LINEAR, A);                    \
+  } while (0)
+      if (act == CDE_ACT_NONE) CDE_MLP_D(CDE_ACT_NONE);
+      else if (act == CDE_ACT_TANH) CDE_MLP_D(CDE_ACT_TANH);
+      else if (act == cde::FIELD_SOFTPLUS_NONE) CDE_MLP_D(cde::FIELD_SOFTPLUS_NONE);
+      else CDE_MLP_D(cde::FIELD_SOFTPLUS_TANH);
+#undef CDE_MLP_D
 #undef CDE_MLP
 #undef CDE_MLP_CT
       return cde::check_launch();

@@ -1,5 +1,5 @@
 // dopri5_mlp_adjoint.hip -- K4am: the continuous-adjoint backward of an ADAPTIVE (dopri5) solve for the two-layer field
-//   f(z) = reshape_{HxC}( act( W2 relu(W1 z + b1) + b2 ) ) dX          (example/time_series_classification.py:20-51)
+//   f(z) = reshape_{HxC}( act( W2 hidden(W1 z + b1) + b2 ) ) dX, hidden = relu | softplus          (example/time_series_classification.py:20-51)
 //
 // This is the call every example of the reference makes to train its model: cdeint(X, func, z0, X.interval) with no
 // method -- dopri5, adjoint=True (example/time_series_classification.py:83-86, example/irregular_data.py:59,
@@ -31,6 +31,7 @@
 #include "cde_dopri_adj.h"
 #include "cde_dopri_ctl.h"
 #include "cde_mlp_adj.h"
+#include "cde_launch.h"
 
 namespace cde {
 
@@ -1321,7 +1322,7 @@ static int dopri5_adjoint_mlp_advance_impl(const void* coeffs, const void* knots
   if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
   if (!mlp_shape_ok(C, H, width) && !mlp_shape_upper(C, H, width)) return CDE_ERR_UNSUPPORTED;
   if (mlp_shape_upper(C, H, width) && sharded) return CDE_ERR_UNSUPPORTED;       // (one GPU's batch: no image exchange for the upper half)
-  if (act != CDE_ACT_NONE && act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
+  if (!field_act_known(act)) return CDE_ERR_UNSUPPORTED;
   if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
   if (norm_kind != 0 && norm_kind != 1) return CDE_ERR_UNSUPPORTED;
   if (!coeffs || !knots || !W1 || !bias1 || !W2 || !bias2 || !y_init || !a_init || !a_out || !workspace) return CDE_ERR_NULL;
@@ -1375,7 +1376,8 @@ static int dopri5_adjoint_mlp_advance_impl(const void* coeffs, const void* knots
       zero_async(base + L.U, L.trace - L.U, s);
       const int64_t rows = (int64_t)MADJ_FSLOTS * L.rows_per_stage;
       madj_ones_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, s>>>(g.U, g.Z, rows);
-      const int rc = launch_mlp_adjoint_images(W1, bias1, width, W2, bias2, C, H, (float*)(base + L.image), s);
+      const int rc = launch_mlp_adjoint_images(W1, bias1, width, W2, bias2, C, H, (float*)(base + L.image), s,
+                                               CDE_FIELD_HIDDEN(act) == CDE_HIDDEN_SOFTPLUS ? SOFTPLUS_PAD_BIAS : 0.f);
       if (rc != CDE_OK) return rc;
     }
     if (dctrl) zero_async(base + L.rec, L.gx - L.rec, s);                         // stage records, control norm sums, time terms
@@ -1471,11 +1473,15 @@ static int dopri5_adjoint_mlp_advance_impl(const void* coeffs, const void* knots
     else if (L.split8 && !dctrl) CDE_MADJ_LAUNCH_S8(D, A);       /* (control gradients: the four-wave form) */          \
     else CDE_MADJ_W(D, A, 8, false);                                                                                 \
   } while (0)
-  if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_MADJ(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_MADJ(CDE_PATH_LINEAR, CDE_ACT_NONE);
-  } else {
-    if (degree == CDE_PATH_CUBIC) CDE_MADJ(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_MADJ(CDE_PATH_LINEAR, CDE_ACT_TANH);
-  }
+#define CDE_MADJ_D(A)                                                                                                \
+  do {                                                                                                               \
+    if (degree == CDE_PATH_CUBIC) CDE_MADJ(CDE_PATH_CUBIC, A); else CDE_MADJ(CDE_PATH_LINEAR, A);                    \
+  } while (0)
+  if (act == CDE_ACT_NONE) CDE_MADJ_D(CDE_ACT_NONE);
+  else if (act == CDE_ACT_TANH) CDE_MADJ_D(CDE_ACT_TANH);
+  else if (act == FIELD_SOFTPLUS_NONE) CDE_MADJ_D(FIELD_SOFTPLUS_NONE);
+  else CDE_MADJ_D(FIELD_SOFTPLUS_TANH);
+#undef CDE_MADJ_D
 #undef CDE_MADJ
 #undef CDE_MADJ_W
 #undef CDE_MADJ_LAUNCH

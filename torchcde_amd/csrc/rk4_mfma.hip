@@ -1221,7 +1221,7 @@ int launch_forward_mlp(const Control& x, const TwoLayerField& f, const ForwardIO
   const int64_t tiles = (n.B + 15) / 16;
   const bool split = tiles <= 768 && !option(CDE_OPT_K2M_NO_SPLIT);
   const size_t lds_split = lds + (8 * 64 + 8 * 64 * 4) * sizeof(float);     // f window + (8-channel tiles) the u window
-  const int rc = dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+  const int rc = dispatch_degree_field(x.degree, f.act, [&](auto D, auto A) {
     if (split) launch_mlp_tiles<TT, D(), A(), true, false>(MlpTiles{upper, wide, (unsigned)tiles, lds_split}, x, f, io, n, st, s);
     else launch_mlp_tiles<TT, D(), A(), false, false>(MlpTiles{upper, wide, blocks, lds}, x, f, io, n, st, s);
     return CDE_OK;
@@ -1253,7 +1253,7 @@ int launch_forward_mlp_stages(const Control& x, const TwoLayerField& f, const Fo
     return CDE_ERR_UNSUPPORTED;
   const unsigned blocks = (unsigned)((n.B + 127) / 128);
   const size_t lds = (size_t)MLP16_LDS_FLOATS * sizeof(float);
-  const int rc = dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+  const int rc = dispatch_degree_field(x.degree, f.act, [&](auto D, auto A) {
     launch_mlp_tiles<TT, D(), A(), false, true>(MlpTiles{n.H > 16 && n.C > MC, n.C > MC, blocks, lds}, x, f, io, n, st, s);
     return CDE_OK;
   });

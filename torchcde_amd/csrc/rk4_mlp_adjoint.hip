@@ -232,8 +232,8 @@ __global__ __launch_bounds__(SPLIT ? 256 : 512, SPLIT ? 1 : 2) void rk4_adjoint_
         for (int s = 0; s < 8; ++s) { y0 = mfma16(a0[s], zs[s], y0); y1 = mfma16(a1[s], zs[s], y1); }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          u[8 * TP + r] = fmaxf(y0[r], 0.f);
-          u[8 * TP + 4 + r] = fmaxf(y1[r], 0.f);
+          u[8 * TP + r] = hidden_activate<ACT>(y0[r]);
+          u[8 * TP + 4 + r] = hidden_activate<ACT>(y1[r]);
           mask |= (y0[r] > 0.f ? 1u : 0u) << (8 * TP + r);
           mask |= (y1[r] > 0.f ? 1u : 0u) << (8 * TP + 4 + r);
         }
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(SPLIT ? 256 : 512, SPLIT ? 1 : 2) void rk4_adjoint_
             const int c = 4 * tb + r;
             const float t = tv[r];
             f = c == 0 ? t * dX[0] : __builtin_fmaf(t, dX[c], f);
-            const float slope = ACT == CDE_ACT_TANH ? __builtin_fmaf(-t, t, 1.f) : 1.f;
+            const float slope = final_tanh(ACT) ? __builtin_fmaf(-t, t, 1.f) : 1.f;
             g2[c] = as_P * (dX[c] * slope);
             if constexpr (DCOEFF) gdx[c] = __builtin_fmaf(as_P, t, gdx[c]);
           }
@@ -384,10 +384,10 @@ __global__ __launch_bounds__(SPLIT ? 256 : 512, SPLIT ? 1 : 2) void rk4_adjoint_
         if (nidx != idx) flush_control_grad(idx);
       }
       row = load_row<DEGREE, CT>(coeffs, sc, n_intervals, nidx, Cr);     // for the next stage; lands during the va phase
-      // ---- dL/dY1 = gu * relu'(pre1);  va = W1^T dL/dY1
+      // ---- dL/dY1 = gu * hidden'(pre1) (softplus: the slope from u, cde_mfma.h);  va = W1^T dL/dY1
       float g1[32];
 #pragma unroll
-      for (int s2 = 0; s2 < 32; ++s2) g1[s2] = (mask >> s2) & 1u ? gu[s2 >> 2][s2 & 3] : 0.f;
+      for (int s2 = 0; s2 < 32; ++s2) g1[s2] = hidden_backward<ACT>(gu[s2 >> 2][s2 & 3], (mask >> s2) & 1u, u[s2]);
       if (valid) {
         float* grow = G1 + out_row * G1_COLS + 4 * q;
 #pragma unroll
@@ -573,9 +573,9 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_mlp_sweep_s8(
 size_t mlp_adjoint_image_bytes() { return (size_t)MLP_ADJ_IMAGE_HI_FLOATS * sizeof(float); }
 
 int launch_mlp_adjoint_images(const void* W1, const void* b1, int64_t width, const void* W2, const void* b2, int64_t C,
-                              int64_t H, float* img, hipStream_t s) {
+                              int64_t H, float* img, hipStream_t s, float b1_pad) {
   mlp_adj_image_kernel<<<(MLP_ADJ_IMAGE_HI_FLOATS + 255) / 256, 256, 0, s>>>(
-      (const float*)W1, (const float*)b1, (const float*)W2, (const float*)b2, img, MlpDims{(int)H, (int)C, (int)width},
+      (const float*)W1, (const float*)b1, (const float*)W2, (const float*)b2, img, MlpDims{(int)H, (int)C, (int)width, b1_pad},
       C > MC ? 4 : 2);                          // channel blocks per unit group: 32 units x 8 channels or 16 x 16
   return check_launch();
 }
@@ -609,7 +609,7 @@ int launch_mlp_adjoint_sweep(const Control& x, const SweepIO& io, const Shape& n
   const bool eight = split && s8_shape && tiles <= (s8_tiles > 512 ? s8_tiles : 512);
   using Yes = std::true_type;
   using No = std::false_type;
-  const int rc = dispatch_degree_act(x.degree, io.act, [&](auto D, auto A) {
+  const int rc = dispatch_degree_field(x.degree, io.act, [&](auto D, auto A) {
     auto launch = [&](auto X, auto CT, auto SPL) {
       allow_lds(rk4_adjoint_mlp_sweep<TT, D(), A(), X(), CT(), SPL()>, lds);
       rk4_adjoint_mlp_sweep<TT, D(), A(), X(), CT(), SPL()><<<blocks, threads, lds, s>>>(CDE_SWEEP_ARGS(f32(io.y_state)),
@@ -639,7 +639,7 @@ int launch_mlp_backprop_sweep(const Control& x, const SweepIO& io, const Shape& 
   const Dims dims{(int)n.H, (int)n.C};
   const unsigned blocks = (unsigned)((n.B + 127) / 128);
   const size_t lds = (size_t)ADJ_LDS_FLOATS * sizeof(float);
-  const int rc = dispatch_degree_act(x.degree, io.act, [&](auto D, auto A) {
+  const int rc = dispatch_degree_field(x.degree, io.act, [&](auto D, auto A) {
     auto launch = [&](auto X, auto CT) {
       allow_lds(rk4_adjoint_mlp_sweep<TT, D(), A(), X(), CT(), false, true>, lds);
       rk4_adjoint_mlp_sweep<TT, D(), A(), X(), CT(), false, true><<<blocks, 512, lds, s>>>(

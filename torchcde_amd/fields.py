@@ -4,8 +4,9 @@
 The fused kernels implement two families:
         f(t, z) = act( Linear(H, H*C)(z) ) viewed as (..., H, C),      act in {identity, tanh}
 i.e. the README field (reference README.md:42-49) and ``example/irregular_data.py:36-46``, and
-        f(t, z) = act( Linear(W, H*C)( relu( Linear(H, W)(z) ) ) ) viewed as (..., H, C)
-i.e. ``example/time_series_classification.py:20-51`` (forward solves only).  A module is recognised by
+        f(t, z) = act( Linear(W, H*C)( hidden( Linear(H, W)(z) ) ) ) viewed as (..., H, C),   hidden in {relu, softplus}
+i.e. ``example/time_series_classification.py:20-51`` and its smooth variant with ``torch.nn.functional.softplus`` (torch's
+defaults only: beta 1, threshold 20; any other beta / threshold is refused) in place of the relu.  A module is recognised by
 *probing*, not by tracing source: it must own exactly one (two) nn.Linear and no other parameter; during
 the compatibility evaluation ``func(t[0], z0)`` that the reference performs anyway, forward hooks record
 the Linears' inputs and outputs, and the module's result must be BITWISE equal to the family's formula
@@ -16,7 +17,7 @@ solved step by step) rather than mis-solved.
 Value-dependent look-alikes (relu6 == relu while every pre-activation is below 6, hardtanh / clamp == identity
 inside [-1, 1], dropout in eval mode ...) are excluded STRUCTURALLY, not by luck of the probed values: the
 verification runs under a dispatch-mode recorder and refuses the module if it executes any operator outside
-{matrix products, bias add, relu, tanh, pure layout ops}; it is repeated on an input scaled far outside the
+{matrix products, bias add, relu, softplus, tanh, pure layout ops}; it is repeated on an input scaled far outside the
 data range and at a second time value.  The verdict is cached per module and re-used only while the module's
 *fingerprint* -- class and ``forward`` function of every submodule (monkey-patching on the class or the
 instance), train/eval flags and every plain Python attribute (e.g. a ``use_tanh`` switch) -- is unchanged.
@@ -53,14 +54,19 @@ class AffineField:
 
 
 class MLPField:
-    """(hidden Linear, output Linear, final activation enum): Linear -> relu -> Linear -> act."""
+    """(hidden Linear, output Linear, final activation enum, hidden activation enum): Linear -> relu | softplus -> Linear -> act."""
     kind = "mlp2"
 
-    def __init__(self, hidden, output, act):
+    def __init__(self, hidden, output, act, hidden_act=_lib.HIDDEN_RELU):
         self.hidden, self.output = hidden, output
         self.linears = (hidden, output)
         self.act = act
+        self.hidden_act = hidden_act
         self.shapes = {}
+
+    @property
+    def code(self):              # the `int act` of the C ABI's two-layer entry points (include/cde_mi355x.h: CDE_FIELD_ACT)
+        return _lib.field_act(self.act, self.hidden_act)
 
     @property
     def weight(self):            # the layer that produces the (H, C) matrix
@@ -92,7 +98,7 @@ _verified = weakref.WeakKeyDictionary()   # func -> AffineField, after the two-t
 
 # operators a member of the fused families may execute (aten names at dispatch level); anything else -> step-wise
 _ALLOWED_OPS = {
-    "addmm", "mm", "bmm", "matmul", "linear", "add", "relu", "tanh",                      # arithmetic of the families
+    "addmm", "mm", "bmm", "matmul", "linear", "add", "relu", "softplus", "tanh",          # arithmetic of the families
     "t", "transpose", "permute", "view", "_unsafe_view", "reshape", "_reshape_alias", "expand", "unsqueeze", "squeeze",
     "alias", "detach", "clone", "contiguous", "as_strided", "unflatten", "flatten", "select", "slice",   # layout only
 }
@@ -107,6 +113,14 @@ class _OpRecorder(torch.utils._python_dispatch.TorchDispatchMode):
         name = op.overloadpacket.__name__ if hasattr(op, "overloadpacket") else str(op)
         if name not in _ALLOWED_OPS:
             self.foreign.append(name)
+        elif name == "softplus":
+            # the fused field is torch's DEFAULT softplus.  The arguments are looked at here, not left to the comparison of
+            # values: in float32 another threshold changes no value unless a pre-activation falls between about 16.6 and it
+            operands = list(args[1:3]) + [None] * (3 - len(args))
+            beta = (kwargs or {}).get("beta", 1 if operands[0] is None else operands[0])
+            threshold = (kwargs or {}).get("threshold", 20 if operands[1] is None else operands[1])
+            if beta != 1 or threshold != 20:
+                self.foreign.append("softplus(beta=%r, threshold=%r)" % (beta, threshold))
         return op(*args, **(kwargs or {}))
 
 
@@ -162,8 +176,21 @@ def _final_activation(system, last_out):
     return None
 
 
+def _hidden_activation(hidden_in, first_out):
+    """Which hidden activation turns the first layer's output into the second layer's input, bitwise -- or None.  Softplus
+    is compared against torch's DEFAULT beta and threshold: another beta differs everywhere, another threshold wherever a
+    pre-activation lies between the two thresholds (the probe's far input, z * 37 + 11, is there to produce such values)."""
+    if hidden_in.shape != first_out.shape:
+        return None
+    if torch.equal(hidden_in, first_out.relu()):
+        return _lib.HIDDEN_RELU
+    if torch.equal(hidden_in, torch.nn.functional.softplus(first_out)):
+        return _lib.HIDDEN_SOFTPLUS
+    return None
+
+
 def _classify(system, calls, z):
-    """(kind, act, ordered layers) if ``system`` is exactly one of the fused formulas applied to the recorded layer
+    """(kind, act, ordered layers) -- act = (final, hidden) for the two-layer family -- if ``system`` is exactly one of the fused formulas applied to the recorded layer
     inputs/outputs, else None (bitwise comparison: view/reshape never change values, so any other arithmetic in
     ``func`` is detected)."""
     if not isinstance(system, torch.Tensor) or len(calls) not in (1, 2):
@@ -175,10 +202,11 @@ def _classify(system, calls, z):
         act = _final_activation(system, first_out)
         return None if act is None else ("affine", act, (first,))
     second, hidden_in, second_out = calls[1]
-    if second is first or hidden_in.shape != first_out.shape or not torch.equal(hidden_in, first_out.relu()):
+    hidden = None if second is first else _hidden_activation(hidden_in, first_out)
+    if hidden is None:
         return None
     act = _final_activation(system, second_out)
-    return None if act is None else ("mlp2", act, (first, second))
+    return None if act is None else ("mlp2", (act, hidden), (first, second))
 
 
 def probe(func, t0, z0):
@@ -216,8 +244,13 @@ def probe(func, t0, z0):
     system3, calls3, foreign3 = _evaluate_recording(func, linears, t0, far)
     if foreign3 or _classify(system3, calls3, far) != found:
         return None, system
-    if known is None or known.kind != kind or known.act != act or known.linears != ordered:
-        known = AffineField(ordered[0], act) if kind == "affine" else MLPField(ordered[0], ordered[1], act)
+    if kind == "mlp2":
+        act, hidden = act
+    else:
+        hidden = None
+    if (known is None or known.kind != kind or known.act != act or getattr(known, "hidden_act", None) != hidden
+            or known.linears != ordered):
+        known = AffineField(ordered[0], act) if kind == "affine" else MLPField(ordered[0], ordered[1], act, hidden)
         try:
             _verified[func] = known
         except TypeError:

@@ -92,7 +92,7 @@ class ForeignControlField(ControlledField):
 
 def _explicit_dynamics(field, params):
     """The augmented dynamics of the continuous adjoint in closed form for a RECOGNISED vector field (fields.py: the
-    probe established bitwise that func is act(Linear(z)) or act(Linear(relu(Linear(z)))) viewed (..., H, C)):
+    probe established bitwise that func is act(Linear(z)) or act(Linear(relu | softplus (Linear(z)))) viewed (..., H, C)):
     (t, y, a) -> (f, -a^T df/dy, [-a^T df/dp for p in params]) with a dozen matrix / elementwise launches instead of an
     autograd graph of about forty per evaluation -- the step-wise adaptive backward of the reference's example models
     (two-layer field, default dopri5 + adjoint call) is bound by launches, not by arithmetic.  Returns None when a
@@ -112,6 +112,7 @@ def _explicit_dynamics(field, params):
         slots.append(where[0])
     tanh = rec.act == _lib.ACT_TANH
     two = len(layers) == 2
+    softplus = two and rec.hidden_act == _lib.HIDDEN_SOFTPLUS
     out_layer = layers[-1]
 
     def run(tt, yy, aa):
@@ -123,7 +124,7 @@ def _explicit_dynamics(field, params):
         if two:
             w1, b1 = layers[0].weight, layers[0].bias
             h1 = z @ w1.t() if b1 is None else torch.addmm(b1, z, w1.t())
-            r = h1.relu()
+            r = torch.nn.functional.softplus(h1) if softplus else h1.relu()
         else:
             r = z
         w, b = out_layer.weight, out_layer.bias
@@ -140,7 +141,7 @@ def _explicit_dynamics(field, params):
         if (len(layers) - 1, "bias") in need:
             grads[(len(layers) - 1, "bias")] = gu.sum(0)
         if two:
-            gh1 = (gu @ w) * (h1 > 0)
+            gh1 = (gu @ w) * (torch.sigmoid(h1).masked_fill(h1 > 20, 1.0) if softplus else (h1 > 0))   # softplus' = sigmoid; torch: 1 above its threshold
             if (0, "weight") in need:
                 grads[(0, "weight")] = gh1.t() @ z
             if (0, "bias") in need:
