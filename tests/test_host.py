@@ -107,7 +107,7 @@ def test_argument_errors_come_back_as_codes_without_a_gpu():
     assert lib.cde_hermite_bdiff_coeffs(null, null, null, 0, 5, 3, 0, null) == 0       # empty batch is a no-op
     assert lib.cde_path_eval(null, null, null, 3, null, 2, 0, 3, 3, 1, 0, null) == -3
     assert lib.cde_rk4_adjoint_workspace_bytes(32768, 8, 32, 128, 0, 2) > 1024 * 8448 * 4
-    # the fixed-grid solvers: every call of the table is turned away before the first HIP call, with the recorded code
+    # the fused solvers: every call of the table is turned away before the first HIP call, with the recorded code
     from rejected_calls import CALLS, REJECTED, build_args
     assert set(REJECTED) == set(CALLS)
     wrong = []
@@ -117,6 +117,22 @@ def test_argument_errors_come_back_as_codes_without_a_gpu():
                 got = getattr(lib, name)(*build_args(CALLS[name], overrides))
                 if got != code:
                     wrong.append("%s(%s): %d, expected %d" % (name, overrides, got, code))
+    assert not wrong, "\n".join(wrong)
+
+
+def test_adaptive_workspace_layouts_keep_their_recorded_sizes_and_offsets():
+    """Every size / offset query of the adaptive solvers (K4, K4a, K4am) at default options against the values recorded
+    in tests/rejected_calls.py: the batch sizes straddle every form switch of the layouts.  Pure host functions."""
+    from rejected_calls import LAYOUT, LAYOUT_B, LAYOUT_CH
+    lib = torchcde_amd.load()
+    wrong = []
+    for query, want in LAYOUT.items():
+        name, _, extra = query.partition(" ")
+        tail = [int(extra.partition("=")[2])] if extra else []
+        call = getattr(lib, name)
+        got = call() if isinstance(want, int) else [[call(B, C, H, *tail) for C, H in LAYOUT_CH] for B in LAYOUT_B]
+        if got != want:
+            wrong.append("%s: %r, expected %r" % (query, got, want))
     assert not wrong, "\n".join(wrong)
 
 

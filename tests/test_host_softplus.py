@@ -76,43 +76,15 @@ def test_probes_far_input_separates_softplus_thresholds_by_value_too():
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-# the adaptive two-layer entry points in the notation of tests/rejected_calls.py ("name=1.5": a double)
-_ADAPTIVE = {
-    "cde_dopri5_advance_mlp": "coeffs knots n_intervals=4 degree=3 W1 bias1 width=32 W2 bias2 act=1 z0 t_out n_out=2 jump_t "
-                              "n_jump=0 rtol=1e-4 atol=1e-6 safety=0.9 ifactor=10.0 dfactor=0.2 z_out B=64 C=8 H=32 dtype=0 "
-                              "workspace workspace_bytes=1073741824 first_launch=0 n_launches=1 stream=0",
-    "cde_dopri5_advance_mlp_sharded": "coeffs knots n_intervals=4 degree=3 W1 bias1 width=32 W2 bias2 act=1 z0 t_out n_out=2 "
-                                      "jump_t n_jump=0 rtol=1e-4 atol=1e-6 safety=0.9 ifactor=10.0 dfactor=0.2 z_out B=64 C=8 "
-                                      "H=32 dtype=0 workspace workspace_bytes=1073741824 first_launch=0 reduced_sums "
-                                      "B_global=128 stream=0",
-    "cde_dopri5_adjoint_mlp_advance": "coeffs knots n_intervals=4 degree=3 W1 bias1 width=32 W2 bias2 act=1 y_init a_init s0=-1.0 "
-                                      "s1=0.0 jump_s n_jump=0 rtol=1e-4 atol=1e-6 safety=0.9 ifactor=10.0 dfactor=0.2 "
-                                      "norm_kind=0 a_out B=64 C=8 H=32 dtype=0 first_interval=1 workspace "
-                                      "workspace_bytes=1073741824 first_launch=0 n_launches=1 stream=0",
-    "cde_dopri5_adjoint_mlp_advance_dcontrol": "coeffs knots n_intervals=4 degree=3 W1 bias1 width=32 W2 bias2 act=1 y_init a_init "
-                                               "s0=-1.0 s1=0.0 jump_s n_jump=0 rtol=1e-4 atol=1e-6 safety=0.9 ifactor=10.0 "
-                                               "dfactor=0.2 norm_kind=0 a_out B=64 C=8 H=32 dtype=0 first_interval=1 workspace "
-                                               "workspace_bytes=1073741824 first_launch=0 n_launches=1 grad_coeffs "
-                                               "control_numel=8192 grad_knots stream=0",
-    "cde_dopri5_adjoint_mlp_advance_sharded": "coeffs knots n_intervals=4 degree=3 W1 bias1 width=32 W2 bias2 act=1 y_init a_init "
-                                              "s0=-1.0 s1=0.0 jump_s n_jump=0 rtol=1e-4 atol=1e-6 safety=0.9 ifactor=10.0 "
-                                              "dfactor=0.2 norm_kind=0 a_out B=64 C=8 H=32 dtype=0 first_interval=1 workspace "
-                                              "workspace_bytes=1073741824 first_launch=0 reduced_sums B_global=128 stream=0",
-}
+# the adaptive two-layer entry points (their valid calls: tests/rejected_calls.py)
+_ADAPTIVE = ["cde_dopri5_advance_mlp", "cde_dopri5_advance_mlp_sharded", "cde_dopri5_adjoint_mlp_advance",
+             "cde_dopri5_adjoint_mlp_advance_dcontrol", "cde_dopri5_adjoint_mlp_advance_sharded"]
 _FIXED = ["cde_rk4_forward_mlp", "cde_rk4_forward_mlp_stages", "cde_rk4_adjoint_mlp_sweep", "cde_rk4_backprop_mlp_sweep",
           "cde_rk4_backprop_mlp_sweep_dcontrol"]
 
 
 def _args(name, overrides):
-    if name in CALLS:
-        return build_args(CALLS[name], overrides)
-    over = dict(tok.split("=") for tok in overrides.split())
-    out = []
-    for tok in _ADAPTIVE[name].split():
-        key, _, value = tok.partition("=")
-        value = over.get(key, value or str(0x1000))
-        out.append(float(value) if ("." in value or "e-" in value) else int(value))
-    return out
+    return build_args(CALLS[name], overrides)
 
 
 def test_abi_keeps_its_version_and_the_python_mirror_of_the_codes():

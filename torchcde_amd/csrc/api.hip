@@ -42,7 +42,6 @@ __global__ void stage_table_kernel(const T* __restrict__ knots, int64_t n_interv
 
 // A solve's stage table and what follows it in one allocation: [index: 4 n_steps int64 | frac: 4 n_steps elem | tail],
 // every part 256-byte aligned.  `n_grid` grid points are n_grid - 1 steps (none for an empty grid).
-static inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 struct StageBuffers {
   int64_t* index; void* frac;
   operator StageTable() const { return StageTable{index, frac}; }
@@ -57,7 +56,6 @@ struct StageWorkspace {
   void* tail(const void* ws) const { return (unsigned char*)ws + tail_offset(); }
 };
 struct Dtypes { int state, time; };
-struct Workspace { void* base; size_t bytes; };
 
 template <typename T, typename TT>
 static int fill_stage_table(const Control& x, const void* grid, int64_t n_steps, int negate, int method, StageBuffers to,

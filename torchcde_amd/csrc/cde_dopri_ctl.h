@@ -3,6 +3,7 @@
 // coefficient / knot-time blocks of torchdiffeq's adjoint state.
 #pragma once
 #include "cde_dopri_adj.h"
+#include "cde_launch.h"
 
 namespace cde {
 
@@ -246,5 +247,72 @@ __global__ __launch_bounds__(256) void adjoint_control_kernel(AdjControlArgs r, 
   }
 }
 
+// ------------------------------------------------------------------------------------------ host side of K4a and K4am
+// What the two adjoint families share: both protocols' checks on the launch window, the controller's arguments, the control
+// kernel's, the first launch's zero fills and the opening of the sharded "sums" entry points.  `Layout` = AdjLayout /
+// MadjLayout, which name these parts alike: partial, carry, trace, trace_all, rec, cq, ktp, gx.
+static inline int adj_window_check(const Sharding& sh, const ControlGrads& cg, LaunchWindow w, int64_t B) {
+  if (cg.coeffs && (sh.on() || cg.numel < 1)) return CDE_ERR_UNSUPPORTED;       // control gradients: one controller per solve
+  if (cg.knots && !cg.coeffs) return CDE_ERR_UNSUPPORTED;
+  if (sh.on() && (w.n != 1 || sh.B_global < B)) return CDE_ERR_SHAPE;           // sharded: one launch per all-reduce
+  if (w.first > 0 && sh.on() && !sh.reduced_sums) return CDE_ERR_NULL;
+  return CDE_OK;
+}
+// `own`: the element counts of the family's parameter tensors; the coefficient tensor and the knot times follow them
+template <typename Layout>
+AdjCommon adj_common(const AdjInterval& iv, const Jumps& jumps, const StepControl& tol, const Shape& n, int64_t n_intervals,
+                     const Sharding& sh, const ControlGrads& cg, std::initializer_list<int64_t> own, unsigned char* base,
+                     const Layout& L) {
+  AdjCommon c{};
+  c.s0 = iv.s0; c.s1 = iv.s1; c.jump_s = jumps.t; c.n_jump = jumps.n;
+  c.rtol = tol.rtol; c.atol = tol.atol; c.safety = tol.safety; c.ifactor = tol.ifactor; c.dfactor = tol.dfactor;
+  c.n_state = (sh.B_global > 0 ? sh.B_global : n.B) * n.H;
+  int p = 0;
+  for (int64_t count : own) c.n_param[p++] = count;
+  c.n_param[p] = cg.coeffs ? cg.numel : 1; c.n_param[p + 1] = cg.knots ? n_intervals + 1 : 1;
+  c.n_pt = p + (cg.coeffs ? (cg.knots ? 2 : 1) : 0);
+  c.norm_kind = iv.norm_kind;
+  c.trace = (double*)(base + L.trace); c.trace_all = (double*)(base + L.trace_all); c.carry = (double*)(base + L.carry);
+  return c;
+}
+// `n_wg` workgroups of the attempt kernel leave time-term sums, `kt_stride` apart per parity
+template <typename Layout>
+AdjControlArgs adj_control_args(const Control& x, const AdjInterval& iv, const StepControl& tol, const Shape& n,
+                                const ControlGrads& cg, unsigned char* base, const Layout& L, int n_wg, int kt_stride) {
+  AdjControlArgs cr;
+  cr.ctrl = base; cr.rec = base + L.rec; cr.gx = (const float*)(base + L.gx); cr.G = (float*)cg.coeffs;
+  cr.knots = (const float*)x.knots; cr.cq = (double*)(base + L.cq); cr.B = n.B; cr.n_intervals = x.n_intervals;
+  cr.C = (int)n.C; cr.degree = x.degree; cr.norm_kind = iv.norm_kind; cr.rtol = (float)tol.rtol; cr.atol = (float)tol.atol;
+  cr.G_knots = (float*)cg.knots; cr.ktp = (const double*)(base + L.ktp); cr.n_wg = n_wg; cr.kt_stride = kt_stride;
+  return cr;
+}
+// The first launch of an interval's solve zeroes the controller blocks (phase 0); on the first interval of a backward pass
+// also vjp_t -- unless the caller has set it (first_interval bit 1: output times that require a gradient, torchdiffeq starts
+// every interval at vjp_t - f(t_i, y_i) . dL/dy_i; cde_dopri5_adjoint*_carry_offset) -- and, in `totals()`, the family's
+// running totals; with control gradients the stage records and the control norm sums.
+template <typename Layout, typename Totals>
+int adj_first_launch(unsigned char* base, const Layout& L, const AdjInterval& iv, bool dctrl, hipStream_t s, Totals&& totals) {
+  zero_async(base, 2 * ADJ_CTRL_STRIDE, s);
+  if (iv.first_interval & 1) {
+    if (!(iv.first_interval & 2)) zero_async(base + L.carry, 256, s);
+    const int rc = totals();
+    if (rc != CDE_OK) return rc;
+  }
+  if (dctrl) zero_async(base + L.rec, L.gx - L.rec, s);
+  return CDE_OK;
+}
+// How the entry points of the sharded protocols open (after the single attempt launch `total_launches - 1`): shape, NULL,
+// workspace; then `parity` of the launch whose sums are pending -- they sit in the slots of the next launch, parity ^ 1.
+struct SumsCall {
+  int rc; int parity; unsigned char* base;
+  const double* pending(size_t partial, int64_t stride) const { return (const double*)(base + partial) + (int64_t)(parity ^ 1) * stride * ADJ_NS; }
+};
+static inline SumsCall sums_call(const Workspace& ws, const Shape& n, int64_t total_launches, const void* sums,
+                                 size_t (*workspace_bytes)(int64_t, int64_t, int64_t)) {
+  if (n.B < 1 || n.C < 1 || n.H < 1 || total_launches < 1) return SumsCall{CDE_ERR_SHAPE, 0, nullptr};
+  if (!ws.base || !sums) return SumsCall{CDE_ERR_NULL, 0, nullptr};
+  if (ws.bytes < workspace_bytes(n.B, n.C, n.H)) return SumsCall{CDE_ERR_WORKSPACE, 0, nullptr};
+  return SumsCall{CDE_OK, (int)((total_launches - 1) & 1), (unsigned char*)ws.base};
+}
 
 }  // namespace cde

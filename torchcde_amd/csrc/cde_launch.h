@@ -1,6 +1,8 @@
-// cde_launch.h -- host side of the fixed-grid solvers (rk4 / midpoint / euler): the argument structs the launchers take,
-// the prototype of every launcher and helper that crosses a translation unit, and the degree / activation dispatch.
-// Host declarations only; api.hip fills the structs where the C ABI's pointers enter, the rk4_*.hip files define the launchers.
+// cde_launch.h -- host side of the fused solvers: the argument structs the launchers take, the prototype of every launcher
+// and helper that crosses a translation unit, the degree / activation dispatch and the adaptive families' launch loop.
+// Host code only: declarations, and the two templates that touch the runtime for the kernel they are handed (allow_lds,
+// launch_attempts -- the latter holds a <<<>>> launch, so only .hip files include this header).  Fixed grid (rk4 / midpoint / euler): api.hip fills the structs where the C ABI's pointers enter,
+// the rk4_*.hip files define the launchers.  Adaptive (dopri5): the entry points of the dopri5*.hip files fill them.
 #pragma once
 #include <type_traits>
 #include <hip/hip_runtime.h>
@@ -39,12 +41,30 @@ struct SweepIO {
   const void* grid; int64_t k_begin, k_end;
   void* U; void* G2; void* G1; void* Z; void* grad_coeffs;
 };
+struct Workspace { void* base; size_t bytes; };
+static inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }        // every part of a workspace starts on one
 // K3p's form: the solver's stage count and whether the J rows run on the bf16 pipe (rk4 only)
 enum class PairRows { f32, bf16 };
 struct PairForm { int method; PairRows rows; };
 
 static inline const float* f32(const void* p) { return (const float*)p; }
 static inline float* f32(void* p) { return (float*)p; }
+
+// ---------------------------------------------------------------- the adaptive protocol (dopri5*.hip)
+struct StepControl { double rtol, atol, safety, ifactor, dfactor; };
+struct Jumps { const double* t; int64_t n; };                  // ascending; the adjoint solves: in reversed time
+struct DopriIO { const void* z0; const double* t_out; int64_t n_out; void* z_out; };
+// one output interval [s0, s1] of a backward pass, in reversed time
+struct AdjInterval { const void* y_init; const void* a_init; double s0, s1; void* a_out; int first_interval, norm_kind; };
+// a call queues launches [first, first + n) of its solve; launch i works on controller block i & 1 (`parity`)
+struct LaunchWindow { int64_t first, n; };
+// one step controller for a batch sharded over GPUs: the pending sums added up over all shards, the global batch size
+struct Sharding {
+  const double* reduced_sums; int64_t B_global;
+  bool on() const { return reduced_sums != nullptr || B_global > 0; }
+};
+// adjoint_params naming the control: `coeffs` null without control gradients, `knots` null without the knot-time block
+struct ControlGrads { void* coeffs; int64_t numel; void* knots; };
 
 // ---------------------------------------------------------------- degree / activation as compile-time constants
 // `f(std::integral_constant<int, V>{})` for the run-time value; CDE_ERR_UNSUPPORTED for any other.  `f` launches and
@@ -86,6 +106,19 @@ int dispatch_degree_field(int degree, int act, F&& f) {
 template <typename K>
 void allow_lds(K kernel, size_t bytes) {
   (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+// the launch loop of every adaptive family: per launch of the window the attempt kernel on its parity, then `after(parity)`
+// (the kernels that digest what the attempt left); a code other than CDE_OK from `after` ends the loop
+template <typename K, typename Args, typename After>
+int launch_attempts(K kernel, unsigned grid, unsigned block, size_t lds, hipStream_t s, const Args& g, LaunchWindow w,
+                    After&& after) {
+  for (int64_t i = 0; i < w.n; ++i) {
+    const int parity = (int)((w.first + i) & 1);
+    kernel<<<grid, block, lds, s>>>(g, parity);
+    const int rc = after(parity);
+    if (rc != CDE_OK) return rc;
+  }
+  return CDE_OK;
 }
 
 // ---------------------------------------------------------------- rk4_generic.hip (any shape, f32 / f64)
@@ -181,5 +214,11 @@ template <typename TT>
 int launch_mlp_adjoint_sweep(const Control& x, const SweepIO& io, const Shape& n, const StageTable& st, hipStream_t s);
 template <typename TT>
 int launch_mlp_backprop_sweep(const Control& x, const SweepIO& io, const Shape& n, const StageTable& st, hipStream_t s);
+
+// ---------------------------------------------------------------- dopri5_adjoint.hip (for K4a and K4am alike)
+// the ADJ_NS pending state sums of `n_wg` workgroups -> sums; and, under "seminorm", vjp_t at the end of an interval redone
+// from the reduced sums (neither asks for the launch status)
+void launch_adjoint_state_sums(const double* partial, int n_wg, double* sums, hipStream_t s);
+void launch_adjoint_carry(const unsigned char* ctrl, int p2, const double* reduced, double* carry, hipStream_t s);
 
 }  // namespace cde

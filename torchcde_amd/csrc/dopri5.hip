@@ -1037,7 +1037,6 @@ static inline int64_t dopri_blocks(int64_t B, int64_t H) {
   int64_t tiles = (B + ns - 1) / ns;
   return tiles < 1 ? 1 : (tiles > 2048 ? 2048 : tiles);
 }
-static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 // sharded batches: this shard's pending partial sums, added up in block order (what the next launch would do itself)
 __global__ __launch_bounds__(64) void dopri_pending_sums_kernel(const double* __restrict__ partial, int64_t n_blocks,
@@ -1084,6 +1083,34 @@ static inline int64_t dopri_blocks_any(int64_t B, int64_t H) {          // parti
   const int64_t m = a > b ? a : b;
   return m > 512 ? m : 512;
 }
+// which attempt kernel a one-layer solve takes (the two-layer fields: always the MFMA kernels) ...
+enum class DopriForm { generic, wide, mfma };
+static inline DopriForm dopri_form(const Shape& n, int dtype, int act, int variant) {
+  if (dopri_use_mfma(n.C, n.H, dtype, act, variant)) return DopriForm::mfma;
+  return dopri_use_wide(n.C, n.H, dtype, act, variant) ? DopriForm::wide : DopriForm::generic;
+}
+// ... and that kernel's grid, the small batches' split forms aside (never taken by a sharded batch): the workgroups that
+// leave partial sums
+static inline int64_t dopri_grid(DopriForm form, const Shape& n) {
+  return form == DopriForm::mfma ? (n.B + 127) / 128 : form == DopriForm::wide ? dopri_wide_grid(n.B, n.C) : dopri_blocks(n.B, n.H);
+}
+
+// workspace: [ctrl x2 | partial sums 2 x blocks x 2 | weight image | state 2 x 5 x B x H | trace], every part 256-byte aligned
+struct DopriLayout {
+  size_t ctrl, partial, image, state, trace, total;
+  int64_t blocks;                                                       // allocation stride of the partial sums
+};
+static DopriLayout dopri_layout(int64_t B, int64_t H, int dtype) {
+  DopriLayout L;
+  L.blocks = dopri_blocks_any(B, H);
+  L.ctrl = 0;
+  L.partial = align256(2 * sizeof(DopriCtrl));
+  L.image = L.partial + align256((size_t)2 * L.blocks * 2 * sizeof(double));
+  L.state = L.image + align256(DOPRI_IMAGE_BYTES);
+  L.trace = align256(L.state + (size_t)2 * 5 * B * H * (dtype == CDE_F64 ? 8 : 4));
+  L.total = L.trace + align256((size_t)CDE_DOPRI5_TRACE_STEPS * 3 * sizeof(double));
+  return L;
+}
 
 }  // namespace cde
 
@@ -1098,190 +1125,135 @@ extern "C" int cde_debug_k4_phase_trace(void* host_out, size_t bytes) {
 // ================================================================================================ C ABI
 extern "C" size_t cde_dopri5_trace_offset(int64_t B, int64_t C, int64_t H, int dtype) {
   (void)C;
-  const size_t elem = dtype == CDE_F64 ? 8 : 4;
-  return cde::al256(cde::al256(2 * sizeof(cde::DopriCtrl)) +
-                    cde::al256((size_t)2 * cde::dopri_blocks_any(B, H) * 2 * sizeof(double)) +
-                    (size_t)2 * 5 * B * H * elem + cde::al256(cde::DOPRI_IMAGE_BYTES));
+  return cde::dopri_layout(B, H, dtype).trace;
 }
 
 extern "C" size_t cde_dopri5_workspace_bytes(int64_t B, int64_t C, int64_t H, int dtype) {
-  return cde_dopri5_trace_offset(B, C, H, dtype) + cde::al256((size_t)CDE_DOPRI5_TRACE_STEPS * 3 * sizeof(double));
+  (void)C;
+  return cde::dopri_layout(B, H, dtype).total;
 }
 
-// W1 == nullptr: one-layer field (W, bias); otherwise W1/bias1/width is the hidden layer and W/bias the output layer
-static int dopri5_advance_impl(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
-                               const void* bias1, int64_t width, const void* W, const void* bias, int act,
-                               const void* z0, const double* t_out, int64_t n_out, const double* jump_t, int64_t n_jump,
-                               double rtol, double atol, double safety, double ifactor, double dfactor, void* z_out,
-                               int64_t B, int64_t C, int64_t H, int dtype, int variant, void* workspace,
-                               size_t workspace_bytes, int64_t first_launch, int64_t n_launches, void* stream,
-                               const double* ext_sums = nullptr, int64_t B_global = 0) {
-  const bool mlp = W1 != nullptr;
-  if (B < 1 || C < 1 || H < 1 || H > 256 || n_intervals < 1 || n_out < 1 || n_launches < 0 || n_jump < 0) return CDE_ERR_SHAPE;
-  if (mlp && (width < 1 || !bias1)) return width < 1 ? CDE_ERR_SHAPE : CDE_ERR_NULL;
-  const bool mlp_upper = mlp && cde::mlp_shape_hi(C, H, width) && ((uintptr_t)W & 15) == 0;     // 32 units x 16 channels (cde_mfma.h: MlpHi)
-  if (mlp && (dtype != CDE_F32 || !(cde::mlp_shape_ok(C, H, width) || mlp_upper) || variant == CDE_VARIANT_GENERIC))
+namespace cde {
+
+// A one-layer field travels as a TwoLayerField without a hidden layer: W1 == nullptr, and (W2, bias2) are its (W, bias).
+static TwoLayerField one_layer(const void* W, const void* bias, int act) { return TwoLayerField{nullptr, nullptr, 0, W, bias, act}; }
+
+static int dopri5_advance(const Control& x, const TwoLayerField& f, const DopriIO& io, const Jumps& jumps,
+                          const StepControl& tol, const Shape& n, int dtype, int variant, const Workspace& ws, LaunchWindow w,
+                          const Sharding& sh, hipStream_t s) {
+  const int64_t B = n.B, C = n.C, H = n.H;
+  const bool mlp = f.W1 != nullptr;
+  if (B < 1 || C < 1 || H < 1 || H > 256 || x.n_intervals < 1 || io.n_out < 1 || w.n < 0 || jumps.n < 0) return CDE_ERR_SHAPE;
+  if (mlp && (f.width < 1 || !f.bias1)) return f.width < 1 ? CDE_ERR_SHAPE : CDE_ERR_NULL;
+  const bool mlp_upper = mlp && mlp_shape_hi(C, H, f.width) && ((uintptr_t)f.W2 & 15) == 0;   // 32 units x 16 channels (cde_mfma.h: MlpHi)
+  if (mlp && (dtype != CDE_F32 || !(mlp_shape_ok(C, H, f.width) || mlp_upper) || variant == CDE_VARIANT_GENERIC))
     return CDE_ERR_UNSUPPORTED;
   // (the two-layer field's `act` carries its hidden activation: CDE_FIELD_ACT)
-  if (mlp ? !cde::field_act_known(act) : (act != CDE_ACT_NONE && act != CDE_ACT_TANH)) return CDE_ERR_UNSUPPORTED;
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (!coeffs || !knots || !W || !bias || !z0 || !t_out || !z_out || !workspace) return CDE_ERR_NULL;
-  if (n_jump > 0 && !jump_t) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_workspace_bytes(B, C, H, dtype)) return CDE_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const bool use_mfma = mlp || cde::dopri_use_mfma(C, H, dtype, act, variant);
-  if (variant == CDE_VARIANT_MFMA && !use_mfma) return CDE_ERR_UNSUPPORTED;
-  const int64_t blocks = cde::dopri_blocks_any(B, H);          // allocation stride of the partial sums
-  unsigned char* base = (unsigned char*)workspace;
-  cde::DopriCtrl* ctrl = (cde::DopriCtrl*)base;
-  double* partial = (double*)(base + cde::al256(2 * sizeof(cde::DopriCtrl)));
-  float* w16 = (float*)(base + cde::al256(2 * sizeof(cde::DopriCtrl)) + cde::al256((size_t)2 * blocks * 2 * sizeof(double)));
-  void* state = (unsigned char*)w16 + cde::al256(cde::DOPRI_IMAGE_BYTES);
-  double* trace = (double*)(base + cde_dopri5_trace_offset(B, C, H, dtype));
-  if (first_launch == 0) {
-    cde::zero_async(ctrl, 2 * sizeof(cde::DopriCtrl), s);                                                // phase 0
+  if (mlp ? !field_act_known(f.act) : (f.act != CDE_ACT_NONE && f.act != CDE_ACT_TANH)) return CDE_ERR_UNSUPPORTED;
+  if (x.degree != CDE_PATH_CUBIC && x.degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
+  if (!x.coeffs || !x.knots || !f.W2 || !f.bias2 || !io.z0 || !io.t_out || !io.z_out || !ws.base) return CDE_ERR_NULL;
+  if (jumps.n > 0 && !jumps.t) return CDE_ERR_NULL;
+  const DopriLayout L = dopri_layout(B, H, dtype);
+  if (ws.bytes < L.total) return CDE_ERR_WORKSPACE;
+  const DopriForm form = mlp ? DopriForm::mfma : dopri_form(n, dtype, f.act, variant);
+  if (variant == CDE_VARIANT_MFMA && form != DopriForm::mfma) return CDE_ERR_UNSUPPORTED;
+  unsigned char* base = (unsigned char*)ws.base;
+  float* image = (float*)(base + L.image);
+  if (w.first == 0) zero_async(base + L.ctrl, 2 * sizeof(DopriCtrl), s);                                  // phase 0
+  // the kernels' arguments for element type T; `ns`: series per tile, `img`: the MFMA kernels' weight image
+  auto args = [&](auto type, int ns, const float* img) {
+    using T = decltype(type);
+    return DopriArgs<T>{(const T*)x.coeffs, (const T*)x.knots, x.n_intervals, x.degree, (const T*)f.W2, (const T*)f.bias2,
+                        f.act, (const T*)io.z0, io.t_out, io.n_out, jumps.t, jumps.n, tol.rtol, tol.atol, tol.safety,
+                        tol.ifactor, tol.dfactor, (T*)io.z_out, B, C, H, ns, (DopriCtrl*)(base + L.ctrl),
+                        (T*)(base + L.state), img, (double*)(base + L.partial), L.blocks, (const T*)f.W1,
+                        (const T*)f.bias1, (int)f.width, (double*)(base + L.trace), sh.reduced_sums, sh.B_global};
+  };
+  // every launch of the window; every form may ask for more than the 64 KB of LDS a kernel gets by default (knot buffer up
+  // to 32 KB + the 33.8 KB tanh image + the split forms' 18 KB exchange window): the limit is raised per instantiation
+  auto attempts = [&](auto kernel, int64_t grid, unsigned block, size_t lds, const auto& g, bool raise_lds = true) {
+    if (raise_lds) allow_lds(kernel, lds);
+    launch_attempts(kernel, (unsigned)grid, block, lds, s, g, w, [](int) { return CDE_OK; });
+    return check_launch();
+  };
+  const int64_t n_knots = x.n_intervals + 1, tiles = (B + 15) / 16;
+  if (form == DopriForm::generic) {
+    const int ns = dopri_ns(H), nt = ((ns * (int)H + 63) / 64) * 64;
+    auto run = [&](auto type) {
+      using T = decltype(type);
+      const size_t lds = (((size_t)ns * (H + C) * sizeof(T) + 15) / 16) * 16 + 2 * nt * sizeof(double);
+      return attempts(dopri5_attempt_kernel<T>, dopri_grid(form, n), nt, lds, args(type, ns, nullptr), false);
+    };
+    return dtype == CDE_F32 ? run(float{}) : dtype == CDE_F64 ? run(double{}) : CDE_ERR_DTYPE;
   }
-  const int ns = cde::dopri_ns(H);
-  const int nt = ((ns * (int)H + 63) / 64) * 64;
-#define CDE_DOPRI(T)                                                                                              \
-  do {                                                                                                            \
-    cde::DopriArgs<T> g{(const T*)coeffs, (const T*)knots, n_intervals, degree, (const T*)W, (const T*)bias, act, \
-                        (const T*)z0, t_out, n_out, jump_t, n_jump, rtol, atol, safety, ifactor, dfactor,         \
-                        (T*)z_out, B, C, H, ns, ctrl, (T*)state, nullptr, partial, blocks};                        \
-    g.trace = trace; g.ext_sums = ext_sums; g.B_global = B_global;                                                \
-    const size_t lds = (((size_t)ns * (H + C) * sizeof(T) + 15) / 16) * 16 + 2 * nt * sizeof(double);                                 \
-    for (int64_t i = 0; i < n_launches; ++i)                                                                      \
-      cde::dopri5_attempt_kernel<T><<<(unsigned)cde::dopri_blocks(B, H), nt, lds, s>>>(g, (int)((first_launch + i) & 1)); \
-  } while (0)
-  if (!mlp && cde::dopri_use_wide(C, H, dtype, act, variant)) {
-    cde::DopriArgs<float> g{(const float*)coeffs, (const float*)knots, n_intervals, degree, (const float*)W,
-                            (const float*)bias, act, (const float*)z0, t_out, n_out, jump_t, n_jump, rtol, atol, safety,
-                            ifactor, dfactor, (float*)z_out, B, C, H, 16, ctrl, (float*)state, w16, partial, blocks,
-                            nullptr, nullptr, 0, trace, ext_sums, B_global};
-    const unsigned grid = (unsigned)cde::dopri_wide_grid(B, C);
-    const int64_t n_knots = n_intervals + 1;
-#define CDE_WIDE(D, A, NWV, NBV)                                                                                   \
-  do {                                                                                                             \
-    const size_t lds = cde::dopri_wide_lds_bytes<NWV, NBV>(n_knots);                                               \
-    (void)hipFuncSetAttribute((const void*)cde::dopri5_attempt_wide<D, A, NWV, NBV>,                               \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-    for (int64_t i = 0; i < n_launches; ++i)                                                                       \
-      cde::dopri5_attempt_wide<D, A, NWV, NBV><<<grid, 64 * NWV, lds, s>>>(g, (int)((first_launch + i) & 1));      \
-  } while (0)
-#define CDE_WIDE_SHAPE(D, A)                                                                                       \
-  do {                                                                                                             \
-    if (C <= cde::MC) CDE_WIDE(D, A, 8, 2); else CDE_WIDE(D, A, 4, 4);                                             \
-  } while (0)
-    if (act == CDE_ACT_NONE) {
-      if (degree == CDE_PATH_CUBIC) CDE_WIDE_SHAPE(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_WIDE_SHAPE(CDE_PATH_LINEAR, CDE_ACT_NONE);
-    } else {
-      if (degree == CDE_PATH_CUBIC) CDE_WIDE_SHAPE(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_WIDE_SHAPE(CDE_PATH_LINEAR, CDE_ACT_TANH);
-    }
-#undef CDE_WIDE_SHAPE
-#undef CDE_WIDE
-    return cde::check_launch();
+  const DopriArgs<float> g = args(float{}, 16, image);
+  if (form == DopriForm::wide) {
+    // one-layer fields beyond the 32 x 8 tiles: NW waves over NB blocks of hidden units
+    return dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+      auto run = [&](auto NW, auto NB) {
+        return attempts(dopri5_attempt_wide<D(), A(), NW(), NB()>, dopri_wide_grid(B, C), 64 * NW(),
+                        dopri_wide_lds_bytes<NW(), NB()>(n_knots), g);
+      };
+      return C <= MC ? run(Const<8>{}, Const<2>{}) : run(Const<4>{}, Const<4>{});
+    });
   }
-  if (use_mfma) {
-    cde::DopriArgs<float> g{(const float*)coeffs, (const float*)knots, n_intervals, degree, (const float*)W,
-                            (const float*)bias, act, (const float*)z0, t_out, n_out, jump_t, n_jump, rtol, atol, safety,
-                            ifactor, dfactor, (float*)z_out, B, C, H, 16, ctrl, (float*)state, w16, partial, blocks,
-                            (const float*)W1, (const float*)bias1, (int)width, trace, ext_sums, B_global};
-    const cde::Dims dims{(int)H, (int)C};
-    const unsigned grid = (unsigned)((B + 127) / 128);
-    const int64_t n_knots = n_intervals + 1;
-    if (mlp) {
-      if (first_launch == 0)
-        cde::mlp16_image_kernel<<<(cde::MLP16_LDS_FLOATS + 255) / 256, 256, 0, s>>>(
-            (const float*)W1, (const float*)bias1, (const float*)W, (const float*)bias, w16,
-            cde::MlpDims{(int)H, (int)C, (int)width}, C > cde::MC ? 4 : 2);
-      const size_t lds = 2 * 512 * sizeof(double) +
-                         (n_knots <= cde::DOPRI_MAX_LDS_KNOTS_MLP ? (size_t)((n_knots + 3) / 4 * 4) * sizeof(float) : 0) +
-                         cde::DOPRI_IMAGE_BYTES;
-      // up to 256 tiles (one workgroup per CU): the 8 waves of a workgroup share a tile
-      const int64_t tiles = (B + 15) / 16;
-      const int64_t split_req = cde::option(CDE_OPT_K4M_SPLIT_TILES);           // (measurements; -1: the default)
-      // (an override can only LOWER the threshold: the split form was measured and tested up to these tile counts)
-      const int64_t split_max = C > cde::MC ? 256 : cde::DOPRI_MLP_SPLIT_TILES;
-      const int64_t split_tiles = split_req >= 0 && split_req < split_max ? split_req : split_max;
-      const bool split = tiles <= split_tiles && !ext_sums && B_global == 0 && !cde::option(CDE_OPT_K4M_NO_SPLIT);
-      const size_t lds_split = lds + (size_t)cde::DOPRI_XWIN_FLOATS * sizeof(float);
-#define CDE_MLP_CT(D, A, CTV, HIV)                                                                                 \
-  do {                                                                                                             \
-    if (split) {                                                                                                   \
-      (void)hipFuncSetAttribute((const void*)cde::dopri5_attempt_mfma<D, A, true, CTV, true, HIV>,                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_split);                       \
-      for (int64_t i = 0; i < n_launches; ++i)                                                                     \
-        cde::dopri5_attempt_mfma<D, A, true, CTV, true, HIV><<<(unsigned)tiles, 512, lds_split, s>>>(              \
-            g, (int)((first_launch + i) & 1));                                                                     \
-    } else {                                                                                                       \
-      (void)hipFuncSetAttribute((const void*)cde::dopri5_attempt_mfma<D, A, true, CTV, false, HIV>,                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                             \
-      for (int64_t i = 0; i < n_launches; ++i)                                                                     \
-        cde::dopri5_attempt_mfma<D, A, true, CTV, false, HIV><<<grid, 512, lds, s>>>(g, (int)((first_launch + i) & 1)); \
-    }                                                                                                              \
-  } while (0)
-#define CDE_MLP(D, A)                                                                                              \
-  do {                                                                                                             \
-    if (mlp_upper) CDE_MLP_CT(D, A, 16, true); else if (C > cde::MC) CDE_MLP_CT(D, A, 16, false); else CDE_MLP_CT(D, A, cde::MC, false); \
-  } while (0)
-#define CDE_MLP_D(A)                                                                                               \
-  do {                                                                                                             \
-    if (degree == CDE_PATH_CUBIC) CDE_MLP(CDE_PATH_CUBIC, A); else CDE_MLP(CDE_PATH_LINEAR, A);                    \
-  } while (0)
-      if (act == CDE_ACT_NONE) CDE_MLP_D(CDE_ACT_NONE);
-      else if (act == CDE_ACT_TANH) CDE_MLP_D(CDE_ACT_TANH);
-      else if (act == cde::FIELD_SOFTPLUS_NONE) CDE_MLP_D(cde::FIELD_SOFTPLUS_NONE);
-      else CDE_MLP_D(cde::FIELD_SOFTPLUS_TANH);
-#undef CDE_MLP_D
-#undef CDE_MLP
-#undef CDE_MLP_CT
-      return cde::check_launch();
-    }
-    if (first_launch == 0) {
-      if (act == CDE_ACT_NONE)
-        cde::w16_image_kernel<<<(cde::W16_FLOATS + 255) / 256, 256, 0, s>>>((const float*)W, (const float*)bias, w16, dims);
-      else
-        cde::wy16_image_kernel<<<(cde::ACT16_LDS_FLOATS + 255) / 256, 256, 0, s>>>((const float*)W, (const float*)bias, w16, dims);
-    }
+  // up to one tile per CU the 8 waves of a workgroup share a tile (the split forms); never when the batch is sharded
+  const bool may_split = !sh.reduced_sums && sh.B_global == 0;
+  if (mlp) {
+    if (w.first == 0)
+      mlp16_image_kernel<<<(MLP16_LDS_FLOATS + 255) / 256, 256, 0, s>>>(
+          (const float*)f.W1, (const float*)f.bias1, (const float*)f.W2, (const float*)f.bias2, image,
+          MlpDims{(int)H, (int)C, (int)f.width}, C > MC ? 4 : 2);
     const size_t lds = 2 * 512 * sizeof(double) +
-                       (n_knots <= cde::DOPRI_MAX_LDS_KNOTS ? (size_t)((n_knots + 3) / 4 * 4) * sizeof(float) : 0) +
-                       (act == CDE_ACT_NONE ? 0 : cde::ACT16_LDS_FLOATS * sizeof(float));
-    // small batches (at most one tile per CU): the 8 waves of a workgroup share a tile -- tanh fields one unit group each,
-    // identity fields one K group each
-    const int64_t tiles_act = (B + 15) / 16;
-    const bool split_act = tiles_act <= 256 && !ext_sums && B_global == 0 && !cde::option(CDE_OPT_K4_NO_SPLIT);
-    const size_t lds_split = lds + (size_t)8 * 64 * 9 * sizeof(float);
-    // every form may ask for more than the 64 KB a kernel gets by default (knot buffer up to 32 KB + the 33.8 KB tanh
-    // image + the split forms' 18 KB exchange window): the limit is raised per instantiation, as for the other families
-#define CDE_K4_ONE(D, A)                                                                                           \
-  do {                                                                                                             \
-    if (split_act) {                                                                                               \
-      (void)hipFuncSetAttribute((const void*)cde::dopri5_attempt_mfma<D, A, false, cde::MC, true>,                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_split);                       \
-      for (int64_t i = 0; i < n_launches; ++i)                                                                     \
-        cde::dopri5_attempt_mfma<D, A, false, cde::MC, true><<<(unsigned)tiles_act, 512, lds_split, s>>>(          \
-            g, (int)((first_launch + i) & 1));                                                                     \
-    } else {                                                                                                       \
-      (void)hipFuncSetAttribute((const void*)cde::dopri5_attempt_mfma<D, A>,                                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                             \
-      for (int64_t i = 0; i < n_launches; ++i)                                                                     \
-        cde::dopri5_attempt_mfma<D, A><<<grid, 512, lds, s>>>(g, (int)((first_launch + i) & 1));                   \
-    }                                                                                                              \
-  } while (0)
-    if (act == CDE_ACT_NONE) {
-      if (degree == CDE_PATH_CUBIC) CDE_K4_ONE(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_K4_ONE(CDE_PATH_LINEAR, CDE_ACT_NONE);
-    } else {
-      if (degree == CDE_PATH_CUBIC) CDE_K4_ONE(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_K4_ONE(CDE_PATH_LINEAR, CDE_ACT_TANH);
-    }
-#undef CDE_K4_ONE
-    return cde::check_launch();
+                       (n_knots <= DOPRI_MAX_LDS_KNOTS_MLP ? (size_t)((n_knots + 3) / 4 * 4) * sizeof(float) : 0) +
+                       DOPRI_IMAGE_BYTES;
+    const int64_t split_req = option(CDE_OPT_K4M_SPLIT_TILES);                  // (measurements; -1: the default)
+    // (an override can only LOWER the threshold: the split form was measured and tested up to these tile counts)
+    const int64_t split_max = C > MC ? 256 : DOPRI_MLP_SPLIT_TILES;
+    const int64_t split_tiles = split_req >= 0 && split_req < split_max ? split_req : split_max;
+    const bool split = tiles <= split_tiles && may_split && !option(CDE_OPT_K4M_NO_SPLIT);
+    return dispatch_degree_field(x.degree, f.act, [&](auto D, auto A) {
+      auto run = [&](auto CT, auto HI) {
+        if (split)
+          return attempts(dopri5_attempt_mfma<D(), A(), true, CT(), true, HI()>, tiles, 512,
+                          lds + (size_t)DOPRI_XWIN_FLOATS * sizeof(float), g);
+        return attempts(dopri5_attempt_mfma<D(), A(), true, CT(), false, HI()>, dopri_grid(form, n), 512, lds, g);
+      };
+      return mlp_upper ? run(Const<16>{}, std::true_type{}) : C > MC ? run(Const<16>{}, std::false_type{}) : run(Const<MC>{}, std::false_type{});
+    });
   }
-  if (dtype == CDE_F32) CDE_DOPRI(float);
-  else if (dtype == CDE_F64) CDE_DOPRI(double);
-  else return CDE_ERR_DTYPE;
-#undef CDE_DOPRI
-  return cde::check_launch();
+  const Dims dims{(int)H, (int)C};
+  if (w.first == 0) {
+    if (f.act == CDE_ACT_NONE)
+      w16_image_kernel<<<(W16_FLOATS + 255) / 256, 256, 0, s>>>((const float*)f.W2, (const float*)f.bias2, image, dims);
+    else
+      wy16_image_kernel<<<(ACT16_LDS_FLOATS + 255) / 256, 256, 0, s>>>((const float*)f.W2, (const float*)f.bias2, image, dims);
+  }
+  const size_t lds = 2 * 512 * sizeof(double) +
+                     (n_knots <= DOPRI_MAX_LDS_KNOTS ? (size_t)((n_knots + 3) / 4 * 4) * sizeof(float) : 0) +
+                     (f.act == CDE_ACT_NONE ? 0 : ACT16_LDS_FLOATS * sizeof(float));
+  // split: tanh fields one unit group per wave, identity fields one K group each
+  const bool split = tiles <= 256 && may_split && !option(CDE_OPT_K4_NO_SPLIT);
+  return dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+    if (split)
+      return attempts(dopri5_attempt_mfma<D(), A(), false, MC, true>, tiles, 512, lds + (size_t)8 * 64 * 9 * sizeof(float), g);
+    return attempts(dopri5_attempt_mfma<D(), A()>, dopri_grid(form, n), 512, lds, g);
+  });
 }
+
+// this shard's pending partial sums -> sums[0..1]; the live workgroups are the grid of `form` (computed once the shape passed)
+static int dopri_pending_sums(const Workspace& ws, const Shape& n, int dtype, DopriForm form, int64_t total_launches,
+                              double* sums, hipStream_t s) {
+  if (n.B < 1 || n.C < 1 || n.H < 1) return CDE_ERR_SHAPE;
+  if (!ws.base || !sums) return CDE_ERR_NULL;
+  const DopriLayout L = dopri_layout(n.B, n.H, dtype);
+  if (ws.bytes < L.total) return CDE_ERR_WORKSPACE;
+  const double* partial = (const double*)((const unsigned char*)ws.base + L.partial) + (total_launches & 1) * L.blocks * 2;
+  dopri_pending_sums_kernel<<<1, 64, 0, s>>>(partial, dopri_grid(form, n), 2, sums);
+  return check_launch();
+}
+
+}  // namespace cde
 
 extern "C" int cde_dopri5_advance(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
                                   const void* bias, int act, const void* z0, const double* t_out, int64_t n_out,
@@ -1289,9 +1261,9 @@ extern "C" int cde_dopri5_advance(const void* coeffs, const void* knots, int64_t
                                   double ifactor, double dfactor, void* z_out, int64_t B, int64_t C, int64_t H,
                                   int dtype, int variant, void* workspace, size_t workspace_bytes,
                                   int64_t first_launch, int64_t n_launches, void* stream) {
-  return dopri5_advance_impl(coeffs, knots, n_intervals, degree, nullptr, nullptr, 0, W, bias, act, z0, t_out, n_out,
-                             jump_t, n_jump, rtol, atol, safety, ifactor, dfactor, z_out, B, C, H, dtype, variant,
-                             workspace, workspace_bytes, first_launch, n_launches, stream);
+  return cde::dopri5_advance({coeffs, knots, n_intervals, degree}, cde::one_layer(W, bias, act), {z0, t_out, n_out, z_out},
+                             {jump_t, n_jump}, {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, variant,
+                             {workspace, workspace_bytes}, {first_launch, n_launches}, {nullptr, 0}, (hipStream_t)stream);
 }
 
 // Sharded batches with ONE step controller (torchdiffeq's semantics for the whole batch): per attempted step every
@@ -1299,18 +1271,9 @@ extern "C" int cde_dopri5_advance(const void* coeffs, const void* knots, int64_t
 // launch of cde_dopri5_advance_sharded with the reduced sums and the global batch size.
 extern "C" int cde_dopri5_pending_sums(const void* workspace, size_t workspace_bytes, int64_t B, int64_t C, int64_t H,
                                        int dtype, int variant, int act, int64_t total_launches, double* sums, void* stream) {
-  if (B < 1 || C < 1 || H < 1) return CDE_ERR_SHAPE;
-  if (!workspace || !sums) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_workspace_bytes(B, C, H, dtype)) return CDE_ERR_WORKSPACE;
-  const int64_t stride = cde::dopri_blocks_any(B, H);
-  const bool use_mfma = cde::dopri_use_mfma(C, H, dtype, act, variant);
-  const int64_t live = use_mfma ? (B + 127) / 128
-                       : cde::dopri_use_wide(C, H, dtype, act, variant) ? cde::dopri_wide_grid(B, C)
-                                                                        : cde::dopri_blocks(B, H);   // the grid of the attempt kernel
-  const double* partial = (const double*)((const unsigned char*)workspace + cde::al256(2 * sizeof(cde::DopriCtrl))) +
-                          (total_launches & 1) * stride * 2;
-  cde::dopri_pending_sums_kernel<<<1, 64, 0, (hipStream_t)stream>>>(partial, live, 2, sums);
-  return cde::check_launch();
+  const cde::Shape n{B, C, H};
+  return cde::dopri_pending_sums({(void*)workspace, workspace_bytes}, n, dtype, cde::dopri_form(n, dtype, act, variant),
+                                 total_launches, sums, (hipStream_t)stream);
 }
 
 extern "C" int cde_dopri5_advance_sharded(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -1321,9 +1284,9 @@ extern "C" int cde_dopri5_advance_sharded(const void* coeffs, const void* knots,
                                           size_t workspace_bytes, int64_t first_launch, const double* reduced_sums,
                                           int64_t B_global, void* stream) {
   if (!reduced_sums || B_global < B) return reduced_sums ? CDE_ERR_SHAPE : CDE_ERR_NULL;
-  return dopri5_advance_impl(coeffs, knots, n_intervals, degree, nullptr, nullptr, 0, W, bias, act, z0, t_out, n_out,
-                             jump_t, n_jump, rtol, atol, safety, ifactor, dfactor, z_out, B, C, H, dtype, variant,
-                             workspace, workspace_bytes, first_launch, 1, stream, reduced_sums, B_global);
+  return cde::dopri5_advance({coeffs, knots, n_intervals, degree}, cde::one_layer(W, bias, act), {z0, t_out, n_out, z_out},
+                             {jump_t, n_jump}, {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, variant,
+                             {workspace, workspace_bytes}, {first_launch, 1}, {reduced_sums, B_global}, (hipStream_t)stream);
 }
 
 extern "C" int cde_dopri5_advance_mlp(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -1334,24 +1297,18 @@ extern "C" int cde_dopri5_advance_mlp(const void* coeffs, const void* knots, int
                                       int dtype, void* workspace, size_t workspace_bytes, int64_t first_launch,
                                       int64_t n_launches, void* stream) {
   if (!W1) return CDE_ERR_NULL;
-  return dopri5_advance_impl(coeffs, knots, n_intervals, degree, W1, bias1, width, W2, bias2, act, z0, t_out, n_out,
-                             jump_t, n_jump, rtol, atol, safety, ifactor, dfactor, z_out, B, C, H, dtype,
-                             CDE_VARIANT_AUTO, workspace, workspace_bytes, first_launch, n_launches, stream);
+  return cde::dopri5_advance({coeffs, knots, n_intervals, degree}, {W1, bias1, width, W2, bias2, act}, {z0, t_out, n_out, z_out},
+                             {jump_t, n_jump}, {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, CDE_VARIANT_AUTO,
+                             {workspace, workspace_bytes}, {first_launch, n_launches}, {nullptr, 0}, (hipStream_t)stream);
 }
 
-// The same two calls for the two-layer field (round 4): one controller across the shards of a sharded batch for the
-// call every example of the reference makes (cde_dopri5_advance_mlp's arguments + the reduced sums / global batch).
+// The same two calls for the two-layer field: one controller across the shards of a sharded batch for the call every example
+// of the reference makes (cde_dopri5_advance_mlp's arguments + the reduced sums / global batch).
 extern "C" int cde_dopri5_pending_sums_mlp(const void* workspace, size_t workspace_bytes, int64_t B, int64_t C, int64_t H,
                                            int dtype, int64_t total_launches, double* sums, void* stream) {
-  if (B < 1 || C < 1 || H < 1) return CDE_ERR_SHAPE;
-  if (!workspace || !sums) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_workspace_bytes(B, C, H, dtype)) return CDE_ERR_WORKSPACE;
-  const int64_t stride = cde::dopri_blocks_any(B, H);
-  const int64_t live = (B + 127) / 128;                 // the grid of the (never split, when sharded) two-layer attempt kernel
-  const double* partial = (const double*)((const unsigned char*)workspace + cde::al256(2 * sizeof(cde::DopriCtrl))) +
-                          (total_launches & 1) * stride * 2;
-  cde::dopri_pending_sums_kernel<<<1, 64, 0, (hipStream_t)stream>>>(partial, live, 2, sums);
-  return cde::check_launch();
+  const cde::Shape n{B, C, H};
+  return cde::dopri_pending_sums({(void*)workspace, workspace_bytes}, n, dtype, cde::DopriForm::mfma, total_launches, sums,
+                                 (hipStream_t)stream);
 }
 
 extern "C" int cde_dopri5_advance_mlp_sharded(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -1364,7 +1321,7 @@ extern "C" int cde_dopri5_advance_mlp_sharded(const void* coeffs, const void* kn
                                               void* stream) {
   if (!W1) return CDE_ERR_NULL;
   if (!reduced_sums || B_global < B) return reduced_sums ? CDE_ERR_SHAPE : CDE_ERR_NULL;
-  return dopri5_advance_impl(coeffs, knots, n_intervals, degree, W1, bias1, width, W2, bias2, act, z0, t_out, n_out,
-                             jump_t, n_jump, rtol, atol, safety, ifactor, dfactor, z_out, B, C, H, dtype,
-                             CDE_VARIANT_AUTO, workspace, workspace_bytes, first_launch, 1, stream, reduced_sums, B_global);
+  return cde::dopri5_advance({coeffs, knots, n_intervals, degree}, {W1, bias1, width, W2, bias2, act}, {z0, t_out, n_out, z_out},
+                             {jump_t, n_jump}, {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, CDE_VARIANT_AUTO,
+                             {workspace, workspace_bytes}, {first_launch, 1}, {reduced_sums, B_global}, (hipStream_t)stream);
 }

@@ -871,7 +871,6 @@ __global__ __launch_bounds__(256) void dopri5_adjoint_finish_kernel(const float*
   }
 }
 
-static inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
 static inline int adj_grid(int64_t B) { const int64_t t = (B + 15) / 16; return (int)(t < ADJ_MAX_WG ? t : ADJ_MAX_WG); }
 
 }  // namespace cde
@@ -885,9 +884,10 @@ extern "C" int cde_debug_k4a_phase_trace(void* host_out, size_t bytes) {
 #endif
 
 // ================================================================================================ C ABI
-// workspace: [ctrl x2][state sums][parameter sums][carry][state 2x4xBxH][G][G_local][prev A, D (x2, global + local)]
-//            [attempt images][reduced-sum scratch][trace]
 namespace {
+// workspace: [ctrl x2 | partial: state sums | pq: parameter sums | carry | state 2x4xBxH | G | G_local |
+//             prev: S sums (x2, global + local) | att: attempt images | trace | trace_all]; with control gradients behind it
+//            [rec: stage records x2 | cq: control norm sums | ktp: time-term sums | gx]
 struct AdjLayout {
   size_t partial, pq, carry, state, G, G_local, prev, att, trace, trace_all, total;
   size_t rec, cq, ktp, gx, total_dcontrol;
@@ -896,24 +896,24 @@ struct AdjLayout {
 AdjLayout adj_layout(int64_t B, int64_t H) {
   using namespace cde;
   AdjLayout L;
-  L.partial = a256(2 * ADJ_CTRL_STRIDE);
-  L.pq = L.partial + a256((size_t)2 * ADJ_MAX_WG * ADJ_NS * sizeof(double));
-  L.carry = L.pq + a256((size_t)2 * ADJ_RBLOCKS * 4 * sizeof(double));
+  L.partial = align256(2 * ADJ_CTRL_STRIDE);
+  L.pq = L.partial + align256((size_t)2 * ADJ_MAX_WG * ADJ_NS * sizeof(double));
+  L.carry = L.pq + align256((size_t)2 * ADJ_RBLOCKS * 4 * sizeof(double));
   L.state = L.carry + 256;
-  L.G = L.state + a256((size_t)2 * 4 * B * H * sizeof(float));
-  L.G_local = L.G + a256((size_t)ADJ_IMAGE_FLOATS * sizeof(float));
-  L.prev = L.G_local + a256((size_t)ADJ_IMAGE_FLOATS * sizeof(float));
-  L.att = L.prev + a256((size_t)4 * ADJ_IMAGE_FLOATS * sizeof(float));        // prevS, prevS_local, each [2]
-  L.trace = L.att + a256((size_t)ADJ_MAX_WG * 2 * ADJ_IMAGE_FLOATS * sizeof(float));
-  L.trace_all = L.trace + a256((size_t)CDE_DOPRI5_TRACE_STEPS * 3 * sizeof(double));
-  L.total = L.trace_all + a256((size_t)ADJ_TRACE_ATTEMPTS * 5 * sizeof(double));
+  L.G = L.state + align256((size_t)2 * 4 * B * H * sizeof(float));
+  L.G_local = L.G + align256((size_t)ADJ_IMAGE_FLOATS * sizeof(float));
+  L.prev = L.G_local + align256((size_t)ADJ_IMAGE_FLOATS * sizeof(float));
+  L.att = L.prev + align256((size_t)4 * ADJ_IMAGE_FLOATS * sizeof(float));        // prevS, prevS_local, each [2]
+  L.trace = L.att + align256((size_t)ADJ_MAX_WG * 2 * ADJ_IMAGE_FLOATS * sizeof(float));
+  L.trace_all = L.trace + align256((size_t)CDE_DOPRI5_TRACE_STEPS * 3 * sizeof(double));
+  L.total = L.trace_all + align256((size_t)ADJ_TRACE_ATTEMPTS * 5 * sizeof(double));
   // control gradients (cde_dopri5_adjoint_advance_dcontrol): behind everything else, so the plain layout is a prefix
   L.n_cblocks = (int)((B * 8 + 255) / 256);
   L.rec = L.total;
-  L.cq = L.rec + a256(2 * ADJ_REC_STRIDE);
-  L.ktp = L.cq + a256((size_t)2 * (L.n_cblocks + 1) * 2 * sizeof(double));
-  L.gx = L.ktp + a256((size_t)2 * ADJ_MAX_WG * 8 * sizeof(double));
-  L.total_dcontrol = L.gx + a256((size_t)2 * B * ADJ_GX_ROW * sizeof(float));
+  L.cq = L.rec + align256(2 * ADJ_REC_STRIDE);
+  L.ktp = L.cq + align256((size_t)2 * (L.n_cblocks + 1) * 2 * sizeof(double));
+  L.gx = L.ktp + align256((size_t)2 * ADJ_MAX_WG * 8 * sizeof(double));
+  L.total_dcontrol = L.gx + align256((size_t)2 * B * ADJ_GX_ROW * sizeof(float));
   return L;
 }
 }  // namespace
@@ -959,97 +959,65 @@ extern "C" size_t cde_dopri5_adjoint_dcontrol_workspace_bytes(int64_t B, int64_t
   return adj_layout(B, H).total_dcontrol;
 }
 
-static int adjoint_advance(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
-                           const void* bias, int act, const void* y_init, const void* a_init, double s0, double s1,
-                           const double* jump_s, int64_t n_jump, double rtol, double atol, double safety, double ifactor,
-                           double dfactor, int norm_kind, void* a_out, int64_t B, int64_t C, int64_t H, int dtype,
-                           int first_interval, void* workspace, size_t workspace_bytes, int64_t first_launch,
-                           int64_t n_launches, const double* reduced_sums, int64_t B_global, void* grad_coeffs,
-                           int64_t control_numel, void* grad_knots, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || n_intervals < 1 || n_launches < 0 || n_jump < 0 || !(s0 < s1)) return CDE_ERR_SHAPE;
+static int adjoint_advance(const cde::Control& x, const cde::AffineField& f, const cde::AdjInterval& iv, const cde::Jumps& jumps,
+                           const cde::StepControl& tol, const cde::Shape& n, int dtype, const cde::Workspace& ws,
+                           cde::LaunchWindow w, const cde::Sharding& sh, const cde::ControlGrads& cg, hipStream_t s) {
+  using namespace cde;
+  const int64_t B = n.B, C = n.C, H = n.H;
+  if (B < 1 || C < 1 || H < 1 || x.n_intervals < 1 || w.n < 0 || jumps.n < 0 || !(iv.s0 < iv.s1)) return CDE_ERR_SHAPE;
   if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
-  if (H > cde::MH || C > cde::MC) return CDE_ERR_UNSUPPORTED;
-  if (act != CDE_ACT_NONE && act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (norm_kind != 0 && norm_kind != 1) return CDE_ERR_UNSUPPORTED;
-  if (!coeffs || !knots || !W || !bias || !y_init || !a_init || !a_out || !workspace) return CDE_ERR_NULL;
-  if (n_jump > 0 && !jump_s) return CDE_ERR_NULL;
-  const bool dctrl = grad_coeffs != nullptr;
-  if (workspace_bytes < (dctrl ? cde_dopri5_adjoint_dcontrol_workspace_bytes(B, C, H) : cde_dopri5_adjoint_workspace_bytes(B, C, H)))
-    return CDE_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  unsigned char* base = (unsigned char*)workspace;
+  if (H > MH || C > MC) return CDE_ERR_UNSUPPORTED;
+  if (f.act != CDE_ACT_NONE && f.act != CDE_ACT_TANH) return CDE_ERR_UNSUPPORTED;
+  if (x.degree != CDE_PATH_CUBIC && x.degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
+  if (iv.norm_kind != 0 && iv.norm_kind != 1) return CDE_ERR_UNSUPPORTED;
+  if (!x.coeffs || !x.knots || !f.W || !f.bias || !iv.y_init || !iv.a_init || !iv.a_out || !ws.base) return CDE_ERR_NULL;
+  if (jumps.n > 0 && !jumps.t) return CDE_ERR_NULL;
+  const bool dctrl = cg.coeffs != nullptr, sharded = sh.on();
   const AdjLayout L = adj_layout(B, H);
-  const bool sharded = reduced_sums != nullptr || B_global > 0;
-  if (dctrl && (sharded || control_numel < 1)) return CDE_ERR_UNSUPPORTED;          // control gradients: one controller per solve
-  cde::DopriAdjArgs g;
-  g.coeffs = (const float*)coeffs; g.knots = (const float*)knots; g.n_intervals = n_intervals;
-  g.W = (const float*)W; g.bias = (const float*)bias; g.dims = cde::Dims{(int)H, (int)C};
+  if (ws.bytes < (dctrl ? L.total_dcontrol : L.total)) return CDE_ERR_WORKSPACE;
+  if (const int rc = adj_window_check(sh, cg, w, B)) return rc;
+  unsigned char* base = (unsigned char*)ws.base;
+  const int grid = adj_grid(B);
+  DopriAdjArgs g;
+  g.coeffs = (const float*)x.coeffs; g.knots = (const float*)x.knots; g.n_intervals = x.n_intervals;
+  g.W = (const float*)f.W; g.bias = (const float*)f.bias; g.dims = Dims{(int)H, (int)C};
   g.B = B; g.n_tiles = (B + 15) / 16;
   g.ctrl = base;
   g.partial = (double*)(base + L.partial);
   g.pq = (double*)(base + L.pq);
   g.state = (float*)(base + L.state);
   g.att = (float*)(base + L.att);
-  g.y_init = (const float*)y_init; g.a_init = (const float*)a_init; g.a_out = (float*)a_out;
-  g.com.s0 = s0; g.com.s1 = s1; g.com.jump_s = jump_s; g.com.n_jump = n_jump;
-  g.com.rtol = rtol; g.com.atol = atol; g.com.safety = safety; g.com.ifactor = ifactor; g.com.dfactor = dfactor;
-  g.com.n_state = (B_global > 0 ? B_global : B) * H;
-  if (grad_knots && !dctrl) return CDE_ERR_UNSUPPORTED;
-  g.com.n_pt = dctrl ? (grad_knots ? 4 : 3) : 2; g.com.n_param[0] = H * C * H; g.com.n_param[1] = H * C;
-  g.com.n_param[2] = dctrl ? control_numel : 1; g.com.n_param[3] = grad_knots ? n_intervals + 1 : 1;
+  g.y_init = (const float*)iv.y_init; g.a_init = (const float*)iv.a_init; g.a_out = (float*)iv.a_out;
+  g.com = adj_common(iv, jumps, tol, n, x.n_intervals, sh, cg, {H * C * H, H * C}, base, L);
+  g.ext_sums = sh.reduced_sums;
   g.gx = (float*)(base + L.gx); g.rec = base + L.rec; g.cq = (const double*)(base + L.cq); g.n_cblocks = L.n_cblocks;
-  g.ktp = (double*)(base + L.ktp); g.with_knots = grad_knots ? 1 : 0;
-  g.com.norm_kind = norm_kind;
-  g.com.trace = (double*)(base + L.trace);
-  g.com.trace_all = (double*)(base + L.trace_all);
-  g.com.carry = (double*)(base + L.carry);
-  g.ext_sums = reduced_sums;
-  if (sharded && (n_launches != 1 || B_global < B)) return CDE_ERR_SHAPE;      // sharded: one launch per all-reduce
-  if (first_launch > 0 && sharded && !reduced_sums) return CDE_ERR_NULL;
-  const int grid = cde::adj_grid(B);
-  if (first_launch == 0) {
-    cde::zero_async(base, 2 * cde::ADJ_CTRL_STRIDE, s);                                                // phase 0
-    if (first_interval & 1) {
-      // (bit 1: the caller has set vjp_t itself -- output times that require a gradient: torchdiffeq starts every interval
-      //  at vjp_t - f(t_i, y_i) . dL/dy_i, cde_dopri5_adjoint_carry_offset)
-      if (!(first_interval & 2)) cde::zero_async(base + L.carry, 256, s);
-      cde::zero_async(base + L.G, L.att - L.G, s);                                // G, G_local, the prev buffers
-    }
-    if (dctrl) cde::zero_async(base + L.rec, L.gx - L.rec, s);                    // stage records, control norm sums
+  g.ktp = (double*)(base + L.ktp); g.with_knots = cg.knots ? 1 : 0;
+  if (w.first == 0) {
+    // G, G_local, the prev buffers (like every zero fill of the prologue, queued without a look at its code)
+    const int rc = adj_first_launch(base, L, iv, dctrl, s, [&] { zero_async(base + L.G, L.att - L.G, s); return CDE_OK; });
+    if (rc != CDE_OK) return rc;
   }
   // sharded under "seminorm": the parameter blocks take no part in the decision, so only the 8 state sums travel between the
   // shards (cde_dopri5_adjoint_state_sums / _apply_state_sums) and the gradient images stay LOCAL -- reduced, committed and
   // returned per shard like an unsharded solve's (the caller all-reduces gradients once, as for any data-parallel step)
-  const bool images_local = sharded && norm_kind == 1;
-  cde::AdjReduceArgs r = adj_reduce_args(base, L, B, rtol, atol, sharded && !images_local);
-  cde::AdjControlArgs cr;
-  cr.ctrl = base; cr.rec = base + L.rec; cr.gx = (const float*)(base + L.gx); cr.G = (float*)grad_coeffs;
-  cr.knots = (const float*)knots; cr.cq = (double*)(base + L.cq); cr.B = B; cr.n_intervals = n_intervals;
-  cr.C = (int)C; cr.degree = degree; cr.norm_kind = norm_kind; cr.rtol = (float)rtol; cr.atol = (float)atol;
-  cr.G_knots = (float*)grad_knots; cr.ktp = (const double*)(base + L.ktp); cr.n_wg = grid; cr.kt_stride = cde::ADJ_MAX_WG;
-  const size_t lds_dc = cde::ADJ_LDS_BYTES + (size_t)2 * cde::ADJ_GX_TILE * sizeof(float);
-#define CDE_ADJ(D, A)                                                                                                \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)cde::dopri5_adjoint_attempt<D, A>,                                        \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)cde::ADJ_LDS_BYTES);                  \
-    (void)hipFuncSetAttribute((const void*)cde::dopri5_adjoint_attempt<D, A, true>,                                  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dc);                              \
-    for (int64_t i = 0; i < n_launches; ++i) {                                                                       \
-      const int parity = (int)((first_launch + i) & 1);                                                              \
-      if (dctrl) cde::dopri5_adjoint_attempt<D, A, true><<<grid, 512, lds_dc, s>>>(g, parity);                       \
-      else cde::dopri5_adjoint_attempt<D, A><<<grid, 512, cde::ADJ_LDS_BYTES, s>>>(g, parity);                       \
-      if (!sharded || images_local) cde::adjoint_reduce_kernel<<<cde::ADJ_RBLOCKS, 256, 0, s>>>(r, parity, 0);       \
-      if (dctrl) cde::adjoint_control_kernel<D, 8><<<L.n_cblocks, 256, 0, s>>>(cr, parity);                          \
-    }                                                                                                                \
-  } while (0)
-  if (act == CDE_ACT_NONE) {
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ(CDE_PATH_CUBIC, CDE_ACT_NONE); else CDE_ADJ(CDE_PATH_LINEAR, CDE_ACT_NONE);
-  } else {
-    if (degree == CDE_PATH_CUBIC) CDE_ADJ(CDE_PATH_CUBIC, CDE_ACT_TANH); else CDE_ADJ(CDE_PATH_LINEAR, CDE_ACT_TANH);
-  }
-#undef CDE_ADJ
-  return cde::check_launch();
+  const bool images_local = sharded && iv.norm_kind == 1;
+  const AdjReduceArgs r = adj_reduce_args(base, L, B, tol.rtol, tol.atol, sharded && !images_local);
+  const AdjControlArgs cr = adj_control_args(x, iv, tol, n, cg, base, L, grid, ADJ_MAX_WG);
+  const size_t lds_dc = ADJ_LDS_BYTES + (size_t)2 * ADJ_GX_TILE * sizeof(float);
+  return dispatch_degree_act(x.degree, f.act, [&](auto D, auto A) {
+    allow_lds(dopri5_adjoint_attempt<D(), A()>, ADJ_LDS_BYTES);
+    allow_lds(dopri5_adjoint_attempt<D(), A(), true>, lds_dc);
+    // after an attempt: the R kernel (sharded under the mixed norm: the caller's _pending_sums / _apply_reduced instead),
+    // then the kernel that owns the control blocks
+    auto after = [&](int parity) {
+      if (!sharded || images_local) adjoint_reduce_kernel<<<ADJ_RBLOCKS, 256, 0, s>>>(r, parity, 0);
+      if (dctrl) adjoint_control_kernel<D(), 8><<<L.n_cblocks, 256, 0, s>>>(cr, parity);
+      return (int)CDE_OK;
+    };
+    if (dctrl) launch_attempts(dopri5_adjoint_attempt<D(), A(), true>, grid, 512, lds_dc, s, g, w, after);
+    else launch_attempts(dopri5_adjoint_attempt<D(), A()>, grid, 512, ADJ_LDS_BYTES, s, g, w, after);
+    return check_launch();
+  });
 }
 
 extern "C" int cde_dopri5_adjoint_advance(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -1060,9 +1028,10 @@ extern "C" int cde_dopri5_adjoint_advance(const void* coeffs, const void* knots,
                                           int first_interval, void* workspace, size_t workspace_bytes,
                                           int64_t first_launch, int64_t n_launches, const double* reduced_sums,
                                           int64_t B_global, void* stream) {
-  return adjoint_advance(coeffs, knots, n_intervals, degree, W, bias, act, y_init, a_init, s0, s1, jump_s, n_jump, rtol, atol,
-                         safety, ifactor, dfactor, norm_kind, a_out, B, C, H, dtype, first_interval, workspace,
-                         workspace_bytes, first_launch, n_launches, reduced_sums, B_global, nullptr, 0, nullptr, stream);
+  return adjoint_advance({coeffs, knots, n_intervals, degree}, {W, bias, act},
+                         {y_init, a_init, s0, s1, a_out, first_interval, norm_kind}, {jump_s, n_jump},
+                         {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
+                         {first_launch, n_launches}, {reduced_sums, B_global}, {nullptr, 0, nullptr}, (hipStream_t)stream);
 }
 
 // The same with adjoint_params naming the coefficient tensor the path was built from (reference solver.py:207-222,
@@ -1080,14 +1049,14 @@ extern "C" int cde_dopri5_adjoint_advance_dcontrol(const void* coeffs, const voi
                                                    void* grad_coeffs, int64_t control_numel, void* grad_knots,
                                                    void* stream) {
   if (!grad_coeffs) return CDE_ERR_NULL;
-  return adjoint_advance(coeffs, knots, n_intervals, degree, W, bias, act, y_init, a_init, s0, s1, jump_s, n_jump, rtol, atol,
-                         safety, ifactor, dfactor, norm_kind, a_out, B, C, H, dtype, first_interval, workspace,
-                         workspace_bytes, first_launch, n_launches, nullptr, 0, grad_coeffs, control_numel, grad_knots, stream);
+  return adjoint_advance({coeffs, knots, n_intervals, degree}, {W, bias, act},
+                         {y_init, a_init, s0, s1, a_out, first_interval, norm_kind}, {jump_s, n_jump},
+                         {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
+                         {first_launch, n_launches}, {nullptr, 0}, {grad_coeffs, control_numel, grad_knots},
+                         (hipStream_t)stream);
 }
 
-// sharded batches (one controller for all shards), after the single attempt launch `total_launches - 1`: this shard's
-// pending sums -- ADJ_NS state sums, then the S and E gradient images (cde_dopri5_adjoint_reduced_count() doubles) -- to
-// be all-reduced (sum) over the shards and handed to cde_dopri5_adjoint_apply_reduced and to the next advance call.
+// The ADJ_NS pending state sums of one shard, added up in workgroup order (K4a and K4am alike: cde_dopri_ctl.h)
 __global__ __launch_bounds__(64) void dopri_adjoint_pending_sums_kernel(const double* __restrict__ partial, int n_wg,
                                                                         double* __restrict__ out) {
   const int i = threadIdx.x;
@@ -1096,56 +1065,52 @@ __global__ __launch_bounds__(64) void dopri_adjoint_pending_sums_kernel(const do
   for (int b = 0; b < n_wg; ++b) s += partial[cde::ADJ_NS * b + i];
   out[i] = s;
 }
-
-extern "C" int cde_dopri5_adjoint_pending_sums(void* workspace, size_t workspace_bytes, int64_t B, int64_t C,
-                                               int64_t H, int64_t total_launches, double* sums, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || total_launches < 1) return CDE_ERR_SHAPE;
-  if (!workspace || !sums) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_adjoint_workspace_bytes(B, C, H)) return CDE_ERR_WORKSPACE;
-  unsigned char* base = (unsigned char*)workspace;
-  const AdjLayout L = adj_layout(B, H);
-  const int parity = (int)((total_launches - 1) & 1);               // the launch whose sums are pending
-  const double* partial = (const double*)(base + L.partial) + (int64_t)(parity ^ 1) * cde::ADJ_MAX_WG * cde::ADJ_NS;
-  hipStream_t s = (hipStream_t)stream;
-  dopri_adjoint_pending_sums_kernel<<<1, 64, 0, s>>>(partial, cde::adj_grid(B), sums);
-  cde::AdjReduceArgs r = adj_reduce_args(base, L, B, 0.0, 0.0, true);
-  r.sums_out = sums + cde::ADJ_NS;
-  cde::adjoint_reduce_kernel<<<cde::ADJ_RBLOCKS, 256, 0, s>>>(r, parity, 1);
-  return cde::check_launch();
-}
-
-// The "seminorm" form of the two calls: only the ADJ_NS state sums are pending on the other shards (the attempt's launch
-// already ran the R kernel on this shard's own images); after the all-reduce the one number the R kernel took from LOCAL
-// sums -- vjp_t at the end of an interval -- is redone from the reduced ones.
+// The "seminorm" form: only the ADJ_NS state sums are pending on the other shards (the attempt's launch already ran the R
+// kernel on this shard's own images); after the all-reduce the one number the R kernel took from LOCAL sums -- vjp_t at
+// the end of an interval -- is redone from the reduced ones.
 __global__ void dopri_adjoint_carry_kernel(const unsigned char* __restrict__ ctrl, int p2, const double* __restrict__ reduced,
                                            double* __restrict__ carry) {
   const cde::AdjCtrl k = *reinterpret_cast<const cde::AdjCtrl*>(ctrl + p2 * cde::ADJ_CTRL_STRIDE);
   if (k.c.phase == 4 && k.commit == 0) return;
   if (k.mode == 3) carry[0] = (double)((float)k.T + (float)reduced[4]);
 }
+void cde::launch_adjoint_state_sums(const double* partial, int n_wg, double* sums, hipStream_t s) {
+  dopri_adjoint_pending_sums_kernel<<<1, 64, 0, s>>>(partial, n_wg, sums);
+}
+void cde::launch_adjoint_carry(const unsigned char* ctrl, int p2, const double* reduced, double* carry, hipStream_t s) {
+  dopri_adjoint_carry_kernel<<<1, 1, 0, s>>>(ctrl, p2, reduced, carry);
+}
 
+// sharded batches (one controller for all shards), after the single attempt launch `total_launches - 1`: this shard's
+// pending sums -- ADJ_NS state sums, then the S and E gradient images (cde_dopri5_adjoint_reduced_count() doubles) -- to
+// be all-reduced (sum) over the shards and handed to cde_dopri5_adjoint_apply_reduced and to the next advance call.
+extern "C" int cde_dopri5_adjoint_pending_sums(void* workspace, size_t workspace_bytes, int64_t B, int64_t C,
+                                               int64_t H, int64_t total_launches, double* sums, void* stream) {
+  const cde::SumsCall c = cde::sums_call({workspace, workspace_bytes}, {B, C, H}, total_launches, sums, cde_dopri5_adjoint_workspace_bytes);
+  if (c.rc != CDE_OK) return c.rc;
+  const AdjLayout L = adj_layout(B, H);
+  hipStream_t s = (hipStream_t)stream;
+  cde::launch_adjoint_state_sums(c.pending(L.partial, cde::ADJ_MAX_WG), cde::adj_grid(B), sums, s);
+  cde::AdjReduceArgs r = adj_reduce_args(c.base, L, B, 0.0, 0.0, true);
+  r.sums_out = sums + cde::ADJ_NS;
+  cde::adjoint_reduce_kernel<<<cde::ADJ_RBLOCKS, 256, 0, s>>>(r, c.parity, 1);
+  return cde::check_launch();
+}
+
+// The "seminorm" form of the two calls: the state sums alone, and vjp_t from the reduced ones
 extern "C" int cde_dopri5_adjoint_state_sums(void* workspace, size_t workspace_bytes, int64_t B, int64_t C, int64_t H,
                                              int64_t total_launches, double* sums, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || total_launches < 1) return CDE_ERR_SHAPE;
-  if (!workspace || !sums) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_adjoint_workspace_bytes(B, C, H)) return CDE_ERR_WORKSPACE;
-  unsigned char* base = (unsigned char*)workspace;
-  const AdjLayout L = adj_layout(B, H);
-  const int parity = (int)((total_launches - 1) & 1);
-  const double* partial = (const double*)(base + L.partial) + (int64_t)(parity ^ 1) * cde::ADJ_MAX_WG * cde::ADJ_NS;
-  dopri_adjoint_pending_sums_kernel<<<1, 64, 0, (hipStream_t)stream>>>(partial, cde::adj_grid(B), sums);
+  const cde::SumsCall c = cde::sums_call({workspace, workspace_bytes}, {B, C, H}, total_launches, sums, cde_dopri5_adjoint_workspace_bytes);
+  if (c.rc != CDE_OK) return c.rc;
+  cde::launch_adjoint_state_sums(c.pending(adj_layout(B, H).partial, cde::ADJ_MAX_WG), cde::adj_grid(B), sums, (hipStream_t)stream);
   return cde::check_launch();
 }
 
 extern "C" int cde_dopri5_adjoint_apply_state_sums(void* workspace, size_t workspace_bytes, int64_t B, int64_t C, int64_t H,
                                                    int64_t total_launches, const double* reduced, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || total_launches < 1) return CDE_ERR_SHAPE;
-  if (!workspace || !reduced) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_adjoint_workspace_bytes(B, C, H)) return CDE_ERR_WORKSPACE;
-  unsigned char* base = (unsigned char*)workspace;
-  const AdjLayout L = adj_layout(B, H);
-  const int parity = (int)((total_launches - 1) & 1);
-  dopri_adjoint_carry_kernel<<<1, 1, 0, (hipStream_t)stream>>>(base, parity ^ 1, reduced, (double*)(base + L.carry));
+  const cde::SumsCall c = cde::sums_call({workspace, workspace_bytes}, {B, C, H}, total_launches, reduced, cde_dopri5_adjoint_workspace_bytes);
+  if (c.rc != CDE_OK) return c.rc;
+  cde::launch_adjoint_carry(c.base, c.parity ^ 1, reduced, (double*)(c.base + adj_layout(B, H).carry), (hipStream_t)stream);
   return cde::check_launch();
 }
 
@@ -1153,14 +1118,11 @@ extern "C" int cde_dopri5_adjoint_apply_state_sums(void* workspace, size_t works
 extern "C" int cde_dopri5_adjoint_apply_reduced(void* workspace, size_t workspace_bytes, int64_t B, int64_t C, int64_t H,
                                                 double rtol, double atol, int64_t total_launches,
                                                 const double* reduced, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || total_launches < 1) return CDE_ERR_SHAPE;
-  if (!workspace || !reduced) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_adjoint_workspace_bytes(B, C, H)) return CDE_ERR_WORKSPACE;
-  unsigned char* base = (unsigned char*)workspace;
-  const AdjLayout L = adj_layout(B, H);
-  cde::AdjReduceArgs r = adj_reduce_args(base, L, B, rtol, atol, true);
+  const cde::SumsCall c = cde::sums_call({workspace, workspace_bytes}, {B, C, H}, total_launches, reduced, cde_dopri5_adjoint_workspace_bytes);
+  if (c.rc != CDE_OK) return c.rc;
+  cde::AdjReduceArgs r = adj_reduce_args(c.base, adj_layout(B, H), B, rtol, atol, true);
   r.sums_in = reduced;
-  cde::adjoint_reduce_kernel<<<cde::ADJ_RBLOCKS, 256, 0, (hipStream_t)stream>>>(r, (int)((total_launches - 1) & 1), 2);
+  cde::adjoint_reduce_kernel<<<cde::ADJ_RBLOCKS, 256, 0, (hipStream_t)stream>>>(r, c.parity, 2);
   return cde::check_launch();
 }
 

@@ -1164,8 +1164,6 @@ int launch_mlp_adjoint_factor_reduce(const float* G2, const float* U, const floa
                                      int sps, int64_t rows_per_slab, float* part2, float* part1, const unsigned char* ctrl,
                                      int parity, hipStream_t s, const float* G2hi = nullptr, float* part2hi = nullptr);
 
-static inline size_t m256(size_t x) { return (x + 255) / 256 * 256; }
-
 }  // namespace cde
 
 #ifdef CDE_PHASE_TRACE
@@ -1178,6 +1176,9 @@ extern "C" int cde_debug_k4am_phase_trace(void* host_out, size_t bytes) {
 
 // ================================================================================================ C ABI
 namespace {
+// workspace: [ctrl x2 | partial: state sums | pq: parameter sums | carry | image | state 2x4xBxH | G | prev | Gn | prevn |
+//             (G_hi | prev_hi) | slopes | stash | kst (| kst_hi) | part2 (| part2_hi) | part1 | U | G2 (| G2_hi) | G1 | Z | trace |
+//             trace_all]; with control gradients behind it [rec | cq | ktp | gx].  The forms a batch size takes are part of it.
 struct MadjLayout {
   int64_t n_tiles, rows_per_stage, rows_per_slab;
   int sps, nwave, n_wg;
@@ -1224,42 +1225,42 @@ MadjLayout madj_layout(int64_t B, int64_t H, int64_t C) {
   L.rows_per_slab = ((B + L.sps - 1) / L.sps + 15) / 16 * 16;
   L.rows_per_stage = L.rows_per_slab * L.sps;
   const size_t rows = (size_t)MADJ_FSLOTS * L.rows_per_stage;
-  L.partial = m256(2 * ADJ_CTRL_STRIDE);
-  L.pq = L.partial + m256((size_t)2 * L.n_wg * ADJ_NS * sizeof(double));
-  L.carry = L.pq + m256((size_t)2 * L.pq_blocks * 8 * sizeof(double));
+  L.partial = align256(2 * ADJ_CTRL_STRIDE);
+  L.pq = L.partial + align256((size_t)2 * L.n_wg * ADJ_NS * sizeof(double));
+  L.carry = L.pq + align256((size_t)2 * L.pq_blocks * 8 * sizeof(double));
   L.image = L.carry + 256;
-  L.state = L.image + m256(mlp_adjoint_image_bytes());
-  L.G = L.state + m256((size_t)2 * 4 * B * H * sizeof(float));
-  L.prev = L.G + m256((size_t)MADJ_ELEMS * sizeof(float));
-  L.Gn = L.prev + m256((size_t)2 * MADJ_ELEMS * sizeof(float));        // sharded: the GLOBAL running totals and S sums
-  L.prevn = L.Gn + m256((size_t)MADJ_ELEMS * sizeof(float));
+  L.state = L.image + align256(mlp_adjoint_image_bytes());
+  L.G = L.state + align256((size_t)2 * 4 * B * H * sizeof(float));
+  L.prev = L.G + align256((size_t)MADJ_ELEMS * sizeof(float));
+  L.Gn = L.prev + align256((size_t)2 * MADJ_ELEMS * sizeof(float));        // sharded: the GLOBAL running totals and S sums
+  L.prevn = L.Gn + align256((size_t)MADJ_ELEMS * sizeof(float));
   // (the upper instance's blocks sit inside the ranges the first launch zeroes: [G, slopes) and [U, trace))
   const size_t up = L.upper ? 1 : 0;
-  L.G_hi = L.prevn + m256((size_t)2 * MADJ_ELEMS * sizeof(float));
-  L.prev_hi = L.G_hi + up * m256((size_t)MADJ_ELEMS * sizeof(float));
-  L.slopes = L.prev_hi + up * m256((size_t)2 * MADJ_ELEMS * sizeof(float));
-  L.stash = L.slopes + m256((size_t)L.n_tiles * 7 * 4 * 64 * 16);
-  L.kst = L.stash + m256((size_t)3 * B * (2 * H + 4) * sizeof(float));
-  L.kst_hi = L.kst + m256((size_t)3 * MADJ_ELEMS * sizeof(float));
-  L.part2 = L.kst_hi + up * m256((size_t)3 * MADJ_ELEMS * sizeof(float));
-  L.part2_hi = L.part2 + m256((size_t)MADJ_SLOTS * L.sps * MADJ_P2 * sizeof(float));
-  L.part1 = L.part2_hi + up * m256((size_t)MADJ_SLOTS * L.sps * MADJ_P2 * sizeof(float));
-  L.U = L.part1 + m256((size_t)MADJ_SLOTS * L.sps * MADJ_P1 * sizeof(float));
-  L.G2 = L.U + m256(rows * U_COLS * sizeof(float));
-  L.G2_hi = L.G2 + m256(rows * G2_COLS * sizeof(float));
-  L.G1 = L.G2_hi + up * m256(rows * G2_COLS * sizeof(float));
-  L.Z = L.G1 + m256(rows * G1_COLS * sizeof(float));
-  L.trace = L.Z + m256(rows * Z_COLS * sizeof(float));
-  L.trace_all = L.trace + m256((size_t)CDE_DOPRI5_TRACE_STEPS * 3 * sizeof(double));
-  L.total = L.trace_all + m256((size_t)ADJ_TRACE_ATTEMPTS * 5 * sizeof(double));
+  L.G_hi = L.prevn + align256((size_t)2 * MADJ_ELEMS * sizeof(float));
+  L.prev_hi = L.G_hi + up * align256((size_t)MADJ_ELEMS * sizeof(float));
+  L.slopes = L.prev_hi + up * align256((size_t)2 * MADJ_ELEMS * sizeof(float));
+  L.stash = L.slopes + align256((size_t)L.n_tiles * 7 * 4 * 64 * 16);
+  L.kst = L.stash + align256((size_t)3 * B * (2 * H + 4) * sizeof(float));
+  L.kst_hi = L.kst + align256((size_t)3 * MADJ_ELEMS * sizeof(float));
+  L.part2 = L.kst_hi + up * align256((size_t)3 * MADJ_ELEMS * sizeof(float));
+  L.part2_hi = L.part2 + align256((size_t)MADJ_SLOTS * L.sps * MADJ_P2 * sizeof(float));
+  L.part1 = L.part2_hi + up * align256((size_t)MADJ_SLOTS * L.sps * MADJ_P2 * sizeof(float));
+  L.U = L.part1 + align256((size_t)MADJ_SLOTS * L.sps * MADJ_P1 * sizeof(float));
+  L.G2 = L.U + align256(rows * U_COLS * sizeof(float));
+  L.G2_hi = L.G2 + align256(rows * G2_COLS * sizeof(float));
+  L.G1 = L.G2_hi + up * align256(rows * G2_COLS * sizeof(float));
+  L.Z = L.G1 + align256(rows * G1_COLS * sizeof(float));
+  L.trace = L.Z + align256(rows * Z_COLS * sizeof(float));
+  L.trace_all = L.trace + align256((size_t)CDE_DOPRI5_TRACE_STEPS * 3 * sizeof(double));
+  L.total = L.trace_all + align256((size_t)ADJ_TRACE_ATTEMPTS * 5 * sizeof(double));
   // control gradients (cde_dopri5_adjoint_mlp_advance_dcontrol): the plain layout is a prefix
   L.ct = C > MC ? 16 : 8;
   L.n_cblocks = (int)((B * L.ct + 255) / 256);
   L.rec = L.total;
-  L.cq = L.rec + m256(2 * ADJ_REC_STRIDE);
-  L.ktp = L.cq + m256((size_t)2 * (L.n_cblocks + 1) * 2 * sizeof(double));
-  L.gx = L.ktp + m256((size_t)2 * L.n_wg * 8 * sizeof(double));
-  L.total_dcontrol = L.gx + m256((size_t)2 * B * L.ct * 8 * sizeof(float));
+  L.cq = L.rec + align256(2 * ADJ_REC_STRIDE);
+  L.ktp = L.cq + align256((size_t)2 * (L.n_cblocks + 1) * 2 * sizeof(double));
+  L.gx = L.ktp + align256((size_t)2 * L.n_wg * 8 * sizeof(double));
+  L.total_dcontrol = L.gx + align256((size_t)2 * B * L.ct * 8 * sizeof(float));
   return L;
 }
 }  // namespace
@@ -1301,47 +1302,37 @@ cde::MlpReduceArgs madj_reduce_args(unsigned char* base, const MadjLayout& L, do
 }
 }  // namespace
 
-static int dopri5_adjoint_mlp_advance_impl(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
-                                           const void* W1, const void* bias1, int64_t width, const void* W2,
-                                           const void* bias2, int act, const void* y_init, const void* a_init,
-                                           double s0, double s1, const double* jump_s, int64_t n_jump, double rtol,
-                                           double atol, double safety, double ifactor, double dfactor, int norm_kind,
-                                           void* a_out, int64_t B, int64_t C, int64_t H, int dtype, int first_interval,
-                                           void* workspace, size_t workspace_bytes, int64_t first_launch,
-                                           int64_t n_launches, void* stream, const double* reduced_sums, int64_t B_global,
-                                           void* grad_coeffs = nullptr, int64_t control_numel = 0,
-                                           void* grad_knots = nullptr) {
+static int dopri5_adjoint_mlp_advance(const cde::Control& x, const cde::TwoLayerField& f, const cde::AdjInterval& iv,
+                                      const cde::Jumps& jumps, const cde::StepControl& tol, const cde::Shape& n, int dtype,
+                                      const cde::Workspace& ws, cde::LaunchWindow w, const cde::Sharding& sh,
+                                      const cde::ControlGrads& cg, hipStream_t s) {
   using namespace cde;
-  const bool sharded = reduced_sums != nullptr || B_global > 0;
-  const bool dctrl = grad_coeffs != nullptr;
-  if (dctrl && (sharded || control_numel < 1)) return CDE_ERR_UNSUPPORTED;     // control gradients: one controller per solve
-  if (grad_knots && !dctrl) return CDE_ERR_UNSUPPORTED;
-  if (sharded && (n_launches != 1 || B_global < B)) return CDE_ERR_SHAPE;        // sharded: one launch per all-reduce
-  if (first_launch > 0 && sharded && !reduced_sums) return CDE_ERR_NULL;
-  if (B < 1 || C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_launches < 0 || n_jump < 0 || !(s0 < s1)) return CDE_ERR_SHAPE;
+  const int64_t B = n.B, C = n.C, H = n.H;
+  const bool sharded = sh.on(), dctrl = cg.coeffs != nullptr;
+  if (const int rc = adj_window_check(sh, cg, w, B)) return rc;
+  if (B < 1 || C < 1 || H < 1 || f.width < 1 || x.n_intervals < 1 || w.n < 0 || jumps.n < 0 || !(iv.s0 < iv.s1)) return CDE_ERR_SHAPE;
   if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
-  if (!mlp_shape_ok(C, H, width) && !mlp_shape_upper(C, H, width)) return CDE_ERR_UNSUPPORTED;
-  if (mlp_shape_upper(C, H, width) && sharded) return CDE_ERR_UNSUPPORTED;       // (one GPU's batch: no image exchange for the upper half)
-  if (!field_act_known(act)) return CDE_ERR_UNSUPPORTED;
-  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
-  if (norm_kind != 0 && norm_kind != 1) return CDE_ERR_UNSUPPORTED;
-  if (!coeffs || !knots || !W1 || !bias1 || !W2 || !bias2 || !y_init || !a_init || !a_out || !workspace) return CDE_ERR_NULL;
-  if (n_jump > 0 && !jump_s) return CDE_ERR_NULL;
-  if (workspace_bytes < (dctrl ? cde_dopri5_adjoint_mlp_dcontrol_workspace_bytes(B, C, H) : cde_dopri5_adjoint_mlp_workspace_bytes(B, C, H)))
-    return CDE_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  unsigned char* base = (unsigned char*)workspace;
+  if (!mlp_shape_ok(C, H, f.width) && !mlp_shape_upper(C, H, f.width)) return CDE_ERR_UNSUPPORTED;
+  if (mlp_shape_upper(C, H, f.width) && sharded) return CDE_ERR_UNSUPPORTED;     // (one GPU's batch: no image exchange for the upper half)
+  if (!field_act_known(f.act)) return CDE_ERR_UNSUPPORTED;
+  if (x.degree != CDE_PATH_CUBIC && x.degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
+  if (iv.norm_kind != 0 && iv.norm_kind != 1) return CDE_ERR_UNSUPPORTED;
+  if (!x.coeffs || !x.knots || !f.W1 || !f.bias1 || !f.W2 || !f.bias2 || !iv.y_init || !iv.a_init || !iv.a_out || !ws.base)
+    return CDE_ERR_NULL;
+  if (jumps.n > 0 && !jumps.t) return CDE_ERR_NULL;
   const MadjLayout L = madj_layout(B, H, C);
-  if (dctrl && grad_knots && L.n_wg > ADJ_KT_MAX_WG * 64) return CDE_ERR_UNSUPPORTED;
+  if (ws.bytes < (dctrl ? L.total_dcontrol : L.total)) return CDE_ERR_WORKSPACE;
+  if (dctrl && cg.knots && L.n_wg > ADJ_KT_MAX_WG * 64) return CDE_ERR_UNSUPPORTED;
+  unsigned char* base = (unsigned char*)ws.base;
   MlpAdjArgs g;
-  g.coeffs = (const float*)coeffs; g.knots = (const float*)knots; g.n_intervals = n_intervals;
+  g.coeffs = (const float*)x.coeffs; g.knots = (const float*)x.knots; g.n_intervals = x.n_intervals;
   g.img = (const float*)(base + L.image);
   g.dims = Dims{(int)H, (int)C};
   g.B = B; g.n_tiles = L.n_tiles; g.rows_per_stage = L.rows_per_stage;
   g.ctrl = base;
   g.partial = (double*)(base + L.partial); g.pq = (double*)(base + L.pq);
   g.state = (float*)(base + L.state);
-  g.y_init = (const float*)y_init; g.a_init = (const float*)a_init; g.a_out = (float*)a_out;
+  g.y_init = (const float*)iv.y_init; g.a_init = (const float*)iv.a_init; g.a_out = (float*)iv.a_out;
   g.slopes = (float*)(base + L.slopes);
   g.U = (float*)(base + L.U); g.G2 = (float*)(base + L.G2); g.G1 = (float*)(base + L.G1); g.Z = (float*)(base + L.Z);
   g.stash_y = (float*)(base + L.stash); g.stash_a = g.stash_y + 3 * B * H; g.stash_t = g.stash_a + 3 * B * H;
@@ -1350,52 +1341,34 @@ static int dopri5_adjoint_mlp_advance_impl(const void* coeffs, const void* knots
 #ifdef CDE_PHASE_TRACE
   { const char* d = getenv("CDE_K4AM_DBG"); g.dbg |= d ? atoi(d) & 1 : 0; }      // timing experiments (wrong gradients!)
 #endif
-  g.n_pq = L.small && (!sharded || norm_kind == 1) ? MADJ_SMALL_BLOCKS : L.pq_blocks;
+  g.n_pq = L.small && (!sharded || iv.norm_kind == 1) ? MADJ_SMALL_BLOCKS : L.pq_blocks;
   g.pq_blocks = L.pq_blocks;
   g.G2hi = L.upper ? (float*)(base + L.G2_hi) : nullptr;
-  g.com.s0 = s0; g.com.s1 = s1; g.com.jump_s = jump_s; g.com.n_jump = n_jump;
-  g.com.rtol = rtol; g.com.atol = atol; g.com.safety = safety; g.com.ifactor = ifactor; g.com.dfactor = dfactor;
-  g.com.n_state = (B_global > 0 ? B_global : B) * H;
-  g.ext_sums = reduced_sums;
-  g.com.n_pt = dctrl ? (grad_knots ? 6 : 5) : 4;
-  g.com.n_param[0] = width * H; g.com.n_param[1] = width; g.com.n_param[2] = H * C * width; g.com.n_param[3] = H * C;
-  g.com.n_param[4] = dctrl ? control_numel : 1; g.com.n_param[5] = grad_knots ? n_intervals + 1 : 1;
+  g.com = adj_common(iv, jumps, tol, n, x.n_intervals, sh, cg, {f.width * H, f.width, H * C * f.width, H * C}, base, L);
+  g.ext_sums = sh.reduced_sums;
   g.gx = (float*)(base + L.gx); g.rec = base + L.rec; g.cq = (const double*)(base + L.cq); g.n_cblocks = L.n_cblocks;
-  g.ktp = (double*)(base + L.ktp); g.with_knots = grad_knots ? 1 : 0;
-  g.com.norm_kind = norm_kind;
-  g.com.trace = (double*)(base + L.trace);
-  g.com.trace_all = (double*)(base + L.trace_all);
-  g.com.carry = (double*)(base + L.carry);
-  if (first_launch == 0) {
-    zero_async(base, 2 * ADJ_CTRL_STRIDE, s);                                                     // phase 0
-    if (first_interval & 1) {
-      // vjp_t, the running totals and the factor rows (padding rows must hold zeros; the "1" columns are set below)
-      // (bit 1: the caller has set vjp_t itself -- output-time gradients, as for K4a: cde_dopri5_adjoint_mlp_carry_offset)
-      if (!(first_interval & 2)) zero_async(base + L.carry, 256, s);
+  g.ktp = (double*)(base + L.ktp); g.with_knots = cg.knots ? 1 : 0;
+  if (w.first == 0) {
+    // the running totals and the factor rows (padding rows must hold zeros; then their "1" columns), the weight images
+    const int rc = adj_first_launch(base, L, iv, dctrl, s, [&] {
       zero_async(base + L.G, L.slopes - L.G, s);
       zero_async(base + L.U, L.trace - L.U, s);
       const int64_t rows = (int64_t)MADJ_FSLOTS * L.rows_per_stage;
       madj_ones_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, s>>>(g.U, g.Z, rows);
-      const int rc = launch_mlp_adjoint_images(W1, bias1, width, W2, bias2, C, H, (float*)(base + L.image), s,
-                                               CDE_FIELD_HIDDEN(act) == CDE_HIDDEN_SOFTPLUS ? SOFTPLUS_PAD_BIAS : 0.f);
-      if (rc != CDE_OK) return rc;
-    }
-    if (dctrl) zero_async(base + L.rec, L.gx - L.rec, s);                         // stage records, control norm sums, time terms
+      return launch_mlp_adjoint_images(f.W1, f.bias1, f.width, f.W2, f.bias2, C, H, (float*)(base + L.image), s,
+                                       CDE_FIELD_HIDDEN(f.act) == CDE_HIDDEN_SOFTPLUS ? SOFTPLUS_PAD_BIAS : 0.f);
+    });
+    if (rc != CDE_OK) return rc;
   }
-  AdjControlArgs cr;
-  cr.ctrl = base; cr.rec = base + L.rec; cr.gx = (const float*)(base + L.gx); cr.G = (float*)grad_coeffs;
-  cr.knots = (const float*)knots; cr.cq = (double*)(base + L.cq); cr.B = B; cr.n_intervals = n_intervals;
-  cr.C = (int)C; cr.degree = degree; cr.norm_kind = norm_kind; cr.rtol = (float)rtol; cr.atol = (float)atol;
-  cr.G_knots = (float*)grad_knots; cr.ktp = (const double*)(base + L.ktp); cr.n_wg = L.n_wg; cr.kt_stride = L.n_wg;
-  if (dctrl && L.split8 && L.n_tiles > MADJ_SPLIT_MAX_TILES) cr.n_wg = (int)((L.n_tiles + 3) / 4);
-  // sharded under "seminorm": only the 8 state sums travel between the shards (cde_dopri5_adjoint_mlp_state_sums /
-  // _apply_state_sums); the gradient images are reduced, committed and returned per shard like an unsharded solve's
-  const bool images_local = sharded && norm_kind == 1;
-  MlpReduceArgs r = madj_reduce_args(base, L, rtol, atol, sharded && !images_local);
   // control gradients on eight-channel tiles take the four-wave form where the eight-wave form would run -- up to the 256 tiles
   // that form is used (and tested) on; beyond that one wave per tile, on fewer workgroups than the layout provides for
   const bool dctrl_one_wave = dctrl && L.split8 && L.n_tiles > MADJ_SPLIT_MAX_TILES;
   const int grid = dctrl_one_wave ? (int)((L.n_tiles + 3) / 4) : L.n_wg;
+  const AdjControlArgs cr = adj_control_args(x, iv, tol, n, cg, base, L, grid, L.n_wg);
+  // sharded under "seminorm": only the 8 state sums travel between the shards (cde_dopri5_adjoint_mlp_state_sums /
+  // _apply_state_sums); the gradient images are reduced, committed and returned per shard like an unsharded solve's
+  const bool images_local = sharded && iv.norm_kind == 1;
+  MlpReduceArgs r = madj_reduce_args(base, L, tol.rtol, tol.atol, sharded && !images_local);
   r.n_wg = grid;
   MlpReduceArgs r_hi = r;
   if (L.upper) {
@@ -1405,88 +1378,55 @@ static int dopri5_adjoint_mlp_advance_impl(const void* coeffs, const void* knots
   }
   MlpSmallArgs sm;
   sm.r = r; sm.G2 = g.G2; sm.U = g.U; sm.G1 = g.G1; sm.Z = g.Z; sm.rows_per_stage = L.rows_per_stage; sm.B = B;
-  // after an attempt launch: the split-K reduction of its factor rows + the R kernel, or (small batches) both in one launch
-  auto after_attempt = [&](int parity) -> int {
-    if (sharded && !images_local) return CDE_OK;   // the caller goes on with cde_dopri5_adjoint_mlp_pending_sums / _apply_reduced
-    if (L.small && !(sharded && !images_local)) {
-      mlp_adjoint_small_reduce_kernel<<<MADJ_SMALL_BLOCKS, 256, 0, s>>>(sm, parity);
-      return CDE_OK;
-    }
-    const int rc = launch_mlp_adjoint_factor_reduce(g.G2, g.U, g.G1, g.Z, L.rows_per_stage, L.sps, L.rows_per_slab,
-                                                    (float*)(base + L.part2), (float*)(base + L.part1), base, parity, s,
-                                                    g.G2hi, L.upper ? (float*)(base + L.part2_hi) : nullptr);
-    if (rc != CDE_OK) return rc;
-    mlp_adjoint_reduce_kernel<<<MADJ_RBLOCKS, 256, 0, s>>>(r, parity);
-    if (L.upper) mlp_adjoint_reduce_kernel<<<MADJ_RBLOCKS, 256, 0, s>>>(r_hi, parity);
-    return CDE_OK;
-  };
-  // ... and (control gradients) the kernel that owns the coefficient / knot-time blocks (cde_dopri_ctl.h)
-  auto control_after = [&](int parity) {
-    if (!dctrl) return;
-    if (degree == CDE_PATH_CUBIC) {
-      if (C > MC) adjoint_control_kernel<CDE_PATH_CUBIC, 16><<<L.n_cblocks, 256, 0, s>>>(cr, parity);
-      else adjoint_control_kernel<CDE_PATH_CUBIC, 8><<<L.n_cblocks, 256, 0, s>>>(cr, parity);
-    } else {
-      if (C > MC) adjoint_control_kernel<CDE_PATH_LINEAR, 16><<<L.n_cblocks, 256, 0, s>>>(cr, parity);
-      else adjoint_control_kernel<CDE_PATH_LINEAR, 8><<<L.n_cblocks, 256, 0, s>>>(cr, parity);
-    }
-  };
   const size_t lds_bytes = (size_t)ADJ_LDS_FLOATS * sizeof(float) + (size_t)MADJ_NSUM * 8 * sizeof(double) +
                            (L.split ? (size_t)MADJ_XBUF_FLOATS * sizeof(float) : 0);
-#define CDE_MADJ_LAUNCH(D, A, CTV, NWV, SPL, HIV)                                                                    \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)dopri5_mlp_adjoint_attempt<D, A, CTV, NWV, SPL, false, HIV>,              \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                           \
-    (void)hipFuncSetAttribute((const void*)dopri5_mlp_adjoint_attempt<D, A, CTV, NWV, SPL, true, HIV>,               \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                           \
-    for (int64_t i = 0; i < n_launches; ++i) {                                                                       \
-      const int parity = (int)((first_launch + i) & 1);                                                              \
-      if (dctrl) dopri5_mlp_adjoint_attempt<D, A, CTV, NWV, SPL, true, HIV><<<grid, 64 * NWV, lds_bytes, s>>>(g, parity); \
-      else dopri5_mlp_adjoint_attempt<D, A, CTV, NWV, SPL, false, HIV><<<L.n_wg, 64 * NWV, lds_bytes, s>>>(g, parity); \
-      const int rc = after_attempt(parity);                                                                          \
-      if (rc != CDE_OK) return rc;                                                                                   \
-      control_after(parity);                                                                                         \
-    }                                                                                                                \
-  } while (0)
-#define CDE_MADJ_LAUNCH_S8(D, A)                                                                                     \
-  do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)dopri5_mlp_adjoint_attempt_s8<D, A>,                                      \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                           \
-    for (int64_t i = 0; i < n_launches; ++i) {                                                                       \
-      const int parity = (int)((first_launch + i) & 1);                                                              \
-      dopri5_mlp_adjoint_attempt_s8<D, A><<<L.n_wg, 512, lds_bytes, s>>>(g, parity);                                 \
-      const int rc = after_attempt(parity);                                                                          \
-      if (rc != CDE_OK) return rc;                                                                                   \
-    }                                                                                                                \
-  } while (0)
-#define CDE_MADJ_W(D, A, CTV, HIV)                                                                                   \
-  do {                                                                                                               \
-    if (dctrl_one_wave) CDE_MADJ_LAUNCH(D, A, CTV, 4, false, HIV);                                                   \
-    else if (L.split) CDE_MADJ_LAUNCH(D, A, CTV, 4, true, HIV);                                                      \
-    else if (L.nwave == 8) CDE_MADJ_LAUNCH(D, A, CTV, 8, false, HIV);                                                \
-    else CDE_MADJ_LAUNCH(D, A, CTV, 4, false, HIV);                                                                  \
-  } while (0)
-#define CDE_MADJ(D, A)                                                                                               \
-  do {                                                                                                               \
-    if (L.upper) CDE_MADJ_W(D, A, 16, true);                                                                         \
-    else if (C > MC) CDE_MADJ_W(D, A, 16, false);                                                                    \
-    else if (L.split8 && !dctrl) CDE_MADJ_LAUNCH_S8(D, A);       /* (control gradients: the four-wave form) */          \
-    else CDE_MADJ_W(D, A, 8, false);                                                                                 \
-  } while (0)
-#define CDE_MADJ_D(A)                                                                                                \
-  do {                                                                                                               \
-    if (degree == CDE_PATH_CUBIC) CDE_MADJ(CDE_PATH_CUBIC, A); else CDE_MADJ(CDE_PATH_LINEAR, A);                    \
-  } while (0)
-  if (act == CDE_ACT_NONE) CDE_MADJ_D(CDE_ACT_NONE);
-  else if (act == CDE_ACT_TANH) CDE_MADJ_D(CDE_ACT_TANH);
-  else if (act == FIELD_SOFTPLUS_NONE) CDE_MADJ_D(FIELD_SOFTPLUS_NONE);
-  else CDE_MADJ_D(FIELD_SOFTPLUS_TANH);
-#undef CDE_MADJ_D
-#undef CDE_MADJ
-#undef CDE_MADJ_W
-#undef CDE_MADJ_LAUNCH
-#undef CDE_MADJ_LAUNCH_S8
-  return check_launch();
+  return dispatch_degree_field(x.degree, f.act, [&](auto D, auto A) {
+    // after an attempt launch: the split-K reduction of its factor rows + the R kernel, or (small batches) both in one
+    // launch; then (control gradients) the kernel that owns the coefficient / knot-time blocks (cde_dopri_ctl.h)
+    auto after = [&](int parity) -> int {
+      if (!(sharded && !images_local)) {     // (else the caller goes on with cde_dopri5_adjoint_mlp_pending_sums / _apply_reduced)
+        if (L.small) mlp_adjoint_small_reduce_kernel<<<MADJ_SMALL_BLOCKS, 256, 0, s>>>(sm, parity);
+        else {
+          const int rc = launch_mlp_adjoint_factor_reduce(g.G2, g.U, g.G1, g.Z, L.rows_per_stage, L.sps, L.rows_per_slab,
+                                                          (float*)(base + L.part2), (float*)(base + L.part1), base, parity, s,
+                                                          g.G2hi, L.upper ? (float*)(base + L.part2_hi) : nullptr);
+          if (rc != CDE_OK) return rc;
+          mlp_adjoint_reduce_kernel<<<MADJ_RBLOCKS, 256, 0, s>>>(r, parity);
+          if (L.upper) mlp_adjoint_reduce_kernel<<<MADJ_RBLOCKS, 256, 0, s>>>(r_hi, parity);
+        }
+      }
+      if (dctrl) {
+        if (C > MC) adjoint_control_kernel<D(), 16><<<L.n_cblocks, 256, 0, s>>>(cr, parity);
+        else adjoint_control_kernel<D(), 8><<<L.n_cblocks, 256, 0, s>>>(cr, parity);
+      }
+      return CDE_OK;
+    };
+    auto attempts = [&](auto plain, auto with_control, unsigned block) {
+      allow_lds(plain, lds_bytes);
+      allow_lds(with_control, lds_bytes);
+      const int rc = dctrl ? launch_attempts(with_control, grid, block, lds_bytes, s, g, w, after)
+                           : launch_attempts(plain, L.n_wg, block, lds_bytes, s, g, w, after);
+      return rc != CDE_OK ? rc : check_launch();
+    };
+    // tiles of CT channels (HI: the 32 x 16 field's upper half too): NW waves on a tile each, or (SPLIT) four sharing one
+    auto tiles = [&](auto CT, auto HI) {
+      auto waves = [&](auto NW, auto SPLIT) {
+        return attempts(dopri5_mlp_adjoint_attempt<D(), A(), CT(), NW(), SPLIT(), false, HI()>,
+                        dopri5_mlp_adjoint_attempt<D(), A(), CT(), NW(), SPLIT(), true, HI()>, 64 * NW());
+      };
+      if (dctrl_one_wave) return waves(Const<4>{}, std::false_type{});
+      if (L.split) return waves(Const<4>{}, std::true_type{});
+      return L.nwave == 8 ? waves(Const<8>{}, std::false_type{}) : waves(Const<4>{}, std::false_type{});
+    };
+    if (L.upper) return tiles(Const<16>{}, std::true_type{});
+    if (C > MC) return tiles(Const<16>{}, std::false_type{});
+    if (L.split8 && !dctrl) {                                // eight waves sharing a tile (control gradients: the four-wave form)
+      allow_lds(dopri5_mlp_adjoint_attempt_s8<D(), A()>, lds_bytes);
+      const int rc = launch_attempts(dopri5_mlp_adjoint_attempt_s8<D(), A()>, L.n_wg, 512, lds_bytes, s, g, w, after);
+      return rc != CDE_OK ? rc : check_launch();
+    }
+    return tiles(Const<8>{}, std::false_type{});
+  });
 }
 
 extern "C" int cde_dopri5_adjoint_mlp_advance(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -1497,14 +1437,14 @@ extern "C" int cde_dopri5_adjoint_mlp_advance(const void* coeffs, const void* kn
                                               void* a_out, int64_t B, int64_t C, int64_t H, int dtype, int first_interval,
                                               void* workspace, size_t workspace_bytes, int64_t first_launch,
                                               int64_t n_launches, void* stream) {
-  return dopri5_adjoint_mlp_advance_impl(coeffs, knots, n_intervals, degree, W1, bias1, width, W2, bias2, act, y_init, a_init,
-                                         s0, s1, jump_s, n_jump, rtol, atol, safety, ifactor, dfactor, norm_kind, a_out, B, C,
-                                         H, dtype, first_interval, workspace, workspace_bytes, first_launch, n_launches,
-                                         stream, nullptr, 0);
+  return dopri5_adjoint_mlp_advance({coeffs, knots, n_intervals, degree}, {W1, bias1, width, W2, bias2, act},
+                                    {y_init, a_init, s0, s1, a_out, first_interval, norm_kind}, {jump_s, n_jump},
+                                    {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
+                                    {first_launch, n_launches}, {nullptr, 0}, {nullptr, 0, nullptr}, (hipStream_t)stream);
 }
 
-// K4am with control gradients (round 6; cde_mi355x.h): the coefficient tensor -- and optionally the knot times -- as further
-// blocks of the adjoint state.  Eight-channel tiles then run the four-wave / one-wave forms (not the eight-wave one).
+// K4am with control gradients (cde_mi355x.h): the coefficient tensor -- and optionally the knot times -- as further blocks
+// of the adjoint state.  Eight-channel tiles then run the four-wave / one-wave forms (not the eight-wave one).
 extern "C" int cde_dopri5_adjoint_mlp_advance_dcontrol(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
                                                        const void* W1, const void* bias1, int64_t width, const void* W2,
                                                        const void* bias2, int act, const void* y_init, const void* a_init,
@@ -1516,14 +1456,15 @@ extern "C" int cde_dopri5_adjoint_mlp_advance_dcontrol(const void* coeffs, const
                                                        void* grad_coeffs, int64_t control_numel, void* grad_knots,
                                                        void* stream) {
   if (!grad_coeffs) return CDE_ERR_NULL;
-  return dopri5_adjoint_mlp_advance_impl(coeffs, knots, n_intervals, degree, W1, bias1, width, W2, bias2, act, y_init, a_init,
-                                         s0, s1, jump_s, n_jump, rtol, atol, safety, ifactor, dfactor, norm_kind, a_out, B, C,
-                                         H, dtype, first_interval, workspace, workspace_bytes, first_launch, n_launches,
-                                         stream, nullptr, 0, grad_coeffs, control_numel, grad_knots);
+  return dopri5_adjoint_mlp_advance({coeffs, knots, n_intervals, degree}, {W1, bias1, width, W2, bias2, act},
+                                    {y_init, a_init, s0, s1, a_out, first_interval, norm_kind}, {jump_s, n_jump},
+                                    {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
+                                    {first_launch, n_launches}, {nullptr, 0}, {grad_coeffs, control_numel, grad_knots},
+                                    (hipStream_t)stream);
 }
 
-// ---- one step controller for a batch sharded over GPUs, two-layer field (round 4; the one-layer protocol of
-// dopri5_adjoint.hip, see cde_mi355x.h).  Per attempted step n every shard runs
+// ---- one step controller for a batch sharded over GPUs, two-layer field (the one-layer protocol of dopri5_adjoint.hip,
+// see cde_mi355x.h).  Per attempted step n every shard runs
 //   cde_dopri5_adjoint_mlp_advance_sharded   ONE attempt launch (n > 0: with the reduced buffer of step n - 1)
 //   cde_dopri5_adjoint_mlp_pending_sums      its 8 state sums + its S and E gradient images -> `sums` (doubles)
 //   [all-reduce `sums` over the shards]
@@ -1540,43 +1481,29 @@ extern "C" int cde_dopri5_adjoint_mlp_advance_sharded(const void* coeffs, const 
                                                       size_t workspace_bytes, int64_t first_launch,
                                                       const double* reduced_sums, int64_t B_global, void* stream) {
   if (B_global < B) return CDE_ERR_SHAPE;
-  return dopri5_adjoint_mlp_advance_impl(coeffs, knots, n_intervals, degree, W1, bias1, width, W2, bias2, act, y_init, a_init,
-                                         s0, s1, jump_s, n_jump, rtol, atol, safety, ifactor, dfactor, norm_kind, a_out, B, C,
-                                         H, dtype, first_interval, workspace, workspace_bytes, first_launch, 1, stream,
-                                         reduced_sums, B_global);
+  return dopri5_adjoint_mlp_advance({coeffs, knots, n_intervals, degree}, {W1, bias1, width, W2, bias2, act},
+                                    {y_init, a_init, s0, s1, a_out, first_interval, norm_kind}, {jump_s, n_jump},
+                                    {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
+                                    {first_launch, 1}, {reduced_sums, B_global}, {nullptr, 0, nullptr}, (hipStream_t)stream);
 }
-
-namespace cde {
-__global__ __launch_bounds__(64) void madj_state_sums_kernel(const double* __restrict__ partial, int n_wg,
-                                                             double* __restrict__ out) {
-  const int i = threadIdx.x;
-  if (i >= ADJ_NS) return;
-  double s = 0.0;
-  for (int b = 0; b < n_wg; ++b) s += partial[ADJ_NS * b + i];
-  out[i] = s;
-}
-}  // namespace cde
 
 extern "C" int cde_dopri5_adjoint_mlp_pending_sums(void* workspace, size_t workspace_bytes, int64_t B, int64_t C, int64_t H,
                                                    int64_t total_launches, double* sums, void* stream) {
   using namespace cde;
-  if (B < 1 || C < 1 || H < 1 || total_launches < 1) return CDE_ERR_SHAPE;
-  if (!workspace || !sums) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_adjoint_mlp_workspace_bytes(B, C, H)) return CDE_ERR_WORKSPACE;
-  unsigned char* base = (unsigned char*)workspace;
+  const SumsCall c = sums_call({workspace, workspace_bytes}, {B, C, H}, total_launches, sums, cde_dopri5_adjoint_mlp_workspace_bytes);
+  if (c.rc != CDE_OK) return c.rc;
+  unsigned char* base = c.base;
   const MadjLayout L = madj_layout(B, H, C);
   hipStream_t s = (hipStream_t)stream;
-  const int parity = (int)((total_launches - 1) & 1);               // the launch whose sums are pending
-  const double* partial = (const double*)(base + L.partial) + (int64_t)(parity ^ 1) * L.n_wg * ADJ_NS;
-  madj_state_sums_kernel<<<1, 64, 0, s>>>(partial, L.n_wg, sums);
+  launch_adjoint_state_sums(c.pending(L.partial, L.n_wg), L.n_wg, sums, s);
   const int rc = launch_mlp_adjoint_factor_reduce((const float*)(base + L.G2), (const float*)(base + L.U),
                                                   (const float*)(base + L.G1), (const float*)(base + L.Z), L.rows_per_stage,
                                                   L.sps, L.rows_per_slab, (float*)(base + L.part2), (float*)(base + L.part1),
-                                                  base, parity, s);
+                                                  base, c.parity, s);
   if (rc != CDE_OK) return rc;
   MlpReduceArgs r = madj_reduce_args(base, L, 0.0, 0.0, true);
   r.sums_out = sums + ADJ_NS;
-  mlp_adjoint_reduce_kernel<<<MADJ_RBLOCKS, 256, 0, s>>>(r, parity, 1);
+  mlp_adjoint_reduce_kernel<<<MADJ_RBLOCKS, 256, 0, s>>>(r, c.parity, 1);
   return check_launch();
 }
 
@@ -1584,39 +1511,23 @@ extern "C" int cde_dopri5_adjoint_mlp_apply_reduced(void* workspace, size_t work
                                                     double rtol, double atol, int64_t total_launches, const double* reduced,
                                                     void* stream) {
   using namespace cde;
-  if (B < 1 || C < 1 || H < 1 || total_launches < 1) return CDE_ERR_SHAPE;
-  if (!workspace || !reduced) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_adjoint_mlp_workspace_bytes(B, C, H)) return CDE_ERR_WORKSPACE;
-  unsigned char* base = (unsigned char*)workspace;
-  const MadjLayout L = madj_layout(B, H, C);
-  MlpReduceArgs r = madj_reduce_args(base, L, rtol, atol, true);
+  const SumsCall c = sums_call({workspace, workspace_bytes}, {B, C, H}, total_launches, reduced, cde_dopri5_adjoint_mlp_workspace_bytes);
+  if (c.rc != CDE_OK) return c.rc;
+  MlpReduceArgs r = madj_reduce_args(c.base, madj_layout(B, H, C), rtol, atol, true);
   r.sums_in = reduced;
-  mlp_adjoint_reduce_kernel<<<MADJ_RBLOCKS, 256, 0, (hipStream_t)stream>>>(r, (int)((total_launches - 1) & 1), 2);
+  mlp_adjoint_reduce_kernel<<<MADJ_RBLOCKS, 256, 0, (hipStream_t)stream>>>(r, c.parity, 2);
   return check_launch();
 }
 
 // The "seminorm" form: only the ADJ_NS state sums are pending on the other shards; after the all-reduce vjp_t at the end of
 // an interval is redone from the reduced sums (see dopri5_adjoint.hip: cde_dopri5_adjoint_state_sums).
-namespace cde {
-__global__ void madj_carry_kernel(const unsigned char* __restrict__ ctrl, int p2, const double* __restrict__ reduced,
-                                  double* __restrict__ carry) {
-  const AdjCtrl k = *reinterpret_cast<const AdjCtrl*>(ctrl + p2 * ADJ_CTRL_STRIDE);
-  if (k.c.phase == 4 && k.commit == 0) return;
-  if (k.mode == 3) carry[0] = (double)((float)k.T + (float)reduced[4]);
-}
-}  // namespace cde
-
 extern "C" int cde_dopri5_adjoint_mlp_state_sums(void* workspace, size_t workspace_bytes, int64_t B, int64_t C, int64_t H,
                                                  int64_t total_launches, double* sums, void* stream) {
   using namespace cde;
-  if (B < 1 || C < 1 || H < 1 || total_launches < 1) return CDE_ERR_SHAPE;
-  if (!workspace || !sums) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_adjoint_mlp_workspace_bytes(B, C, H)) return CDE_ERR_WORKSPACE;
-  unsigned char* base = (unsigned char*)workspace;
+  const SumsCall c = sums_call({workspace, workspace_bytes}, {B, C, H}, total_launches, sums, cde_dopri5_adjoint_mlp_workspace_bytes);
+  if (c.rc != CDE_OK) return c.rc;
   const MadjLayout L = madj_layout(B, H, C);
-  const int parity = (int)((total_launches - 1) & 1);
-  const double* partial = (const double*)(base + L.partial) + (int64_t)(parity ^ 1) * L.n_wg * ADJ_NS;
-  madj_state_sums_kernel<<<1, 64, 0, (hipStream_t)stream>>>(partial, L.n_wg, sums);
+  launch_adjoint_state_sums(c.pending(L.partial, L.n_wg), L.n_wg, sums, (hipStream_t)stream);
   return check_launch();
 }
 
@@ -1624,13 +1535,8 @@ extern "C" int cde_dopri5_adjoint_mlp_apply_state_sums(void* workspace, size_t w
                                                        int64_t H, int64_t total_launches, const double* reduced,
                                                        void* stream) {
   using namespace cde;
-  if (B < 1 || C < 1 || H < 1 || total_launches < 1) return CDE_ERR_SHAPE;
-  if (!workspace || !reduced) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_dopri5_adjoint_mlp_workspace_bytes(B, C, H)) return CDE_ERR_WORKSPACE;
-  unsigned char* base = (unsigned char*)workspace;
-  const MadjLayout L = madj_layout(B, H, C);
-  const int parity = (int)((total_launches - 1) & 1);
-  madj_carry_kernel<<<1, 1, 0, (hipStream_t)stream>>>(base, parity ^ 1, reduced, (double*)(base + L.carry));
+  const SumsCall c = sums_call({workspace, workspace_bytes}, {B, C, H}, total_launches, reduced, cde_dopri5_adjoint_mlp_workspace_bytes);
+  if (c.rc != CDE_OK) return c.rc;
+  launch_adjoint_carry(c.base, c.parity ^ 1, reduced, (double*)(c.base + madj_layout(B, H, C).carry), (hipStream_t)stream);
   return check_launch();
 }
-
