@@ -17,8 +17,9 @@ _CSRC = os.path.join(_HERE, "csrc")
 PHASE_TRACE = os.environ.get("CDE_PHASE_TRACE", "") == "1"
 SO_PATH = os.path.join(_HERE, "libcde_mi355x_trace.so" if PHASE_TRACE else "libcde_mi355x.so")
 SOURCES = ["interp_kernels.hip", "rk4_generic.hip", "rk4_mfma.hip", "rk4_split.hip", "rk4_wide.hip", "rk4_mlp_adjoint.hip",
-           "rk4_bf16x3.hip", "rk4_backprop.hip", "rk4_adjoint_pair.hip", "dopri5.hip", "dopri5_adjoint.hip", "dopri5_mlp_adjoint.hip", "mlp_grad_reduce.hip", "api.hip"]
+           "rk4_bf16x3.hip", "rk4_bf16x3_adjoint.hip", "rk4_backprop.hip", "rk4_adjoint_pair.hip", "dopri5.hip", "dopri5_adjoint.hip", "dopri5_mlp_adjoint.hip", "mlp_grad_reduce.hip", "api.hip"]
 HEADERS = [os.path.join(_CSRC, "cde_common.h"), os.path.join(_CSRC, "cde_mfma.h"), os.path.join(_CSRC, "cde_split.h"),
+           os.path.join(_CSRC, "cde_bf16x3.h"),
            os.path.join(_CSRC, "cde_dopri.h"), os.path.join(_CSRC, "cde_dopri_adj.h"), os.path.join(_CSRC, "cde_dopri_ctl.h"),
            os.path.join(_CSRC, "cde_mlp_adj.h"), os.path.join(_CSRC, "cde_launch.h"),
            os.path.join(_HERE, "..", "include", "cde_mi355x.h")]
@@ -29,7 +30,10 @@ if PHASE_TRACE:
 # away, and on gfx950 every v_accvgpr_read costs matrix-pipe time (f32 MFMA and VALU do not overlap within a wave).
 # rk4_adjoint_pair.hip: no SLP vectorizer -- it packs the scalar bf16 splits and the chain wave's FMAs into v_pk_* f32
 # instructions, which cost matrix-pipe time beside the partner wave's MFMAs and, in K3p, pushed both forms into scratch.
+# rk4_bf16x3.hip (K2b alone): the flag took 484 of 530 v_accvgpr_read per RK step out of its one wave; K3b, whose scratch the
+# flag would grow from 172 to 388 bytes per lane, is rk4_bf16x3_adjoint.hip and built without it.
 EXTRA_FLAGS = {"rk4_split.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+               "rk4_bf16x3.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "rk4_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "rk4_adjoint_pair.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
                "dopri5_adjoint.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}

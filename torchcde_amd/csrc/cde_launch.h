@@ -175,7 +175,7 @@ size_t backprop_workspace_bytes(int64_t B);
 int launch_backprop_jacobian(const Control& x, const AffineField& f, const BackpropIO& io, const Shape& n, const StageTable& st,
                              float* partial, hipStream_t s);
 
-// ---------------------------------------------------------------- rk4_bf16x3.hip (exact operand splits on the bf16 pipe)
+// ------------------------------------ rk4_bf16x3.hip, rk4_bf16x3_adjoint.hip (exact operand splits on the bf16 pipe)
 template <typename TT>
 int launch_forward_bf16x3(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
                           hipStream_t s);
