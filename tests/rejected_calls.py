@@ -1,10 +1,10 @@
-"""Calls of the fixed-grid and the adaptive entry points that are rejected before anything touches the device, with the code
-each one returns.
+"""Calls of the fixed-grid, the adaptive and the interpolation / log-signature entry points that are rejected before anything
+touches the device, with the code each one returns.
 
 Every row fails an argument check (shape, dtype, unsupported combination, empty batch, NULL pointer, workspace one byte too
 small) that comes before the first HIP call, so the table runs without a GPU -- and must stay that way: the pointers are
-dummies.  The codes pin the ORDER of the checks of each entry point (csrc/api.hip, csrc/dopri5*.hip); a layout table of
-the adaptive workspaces follows them."""
+dummies.  The codes pin the ORDER of the checks of each entry point (csrc/api.hip, csrc/dopri5*.hip, csrc/interp_kernels.hip,
+csrc/logsig_kernels.hip); a layout table of the adaptive workspaces follows them."""
 
 # entry point -> its C parameters in order; "name": a pointer (a non-null dummy, never dereferenced), "name=v": an integer
 # (decimal or 0x..) or, for the doubles of the adaptive protocol, a float ("rtol=1e-4", "s0=-1.0")
@@ -97,6 +97,30 @@ CALLS = {
                                                "stream=0",
     "cde_dopri5_adjoint_mlp_apply_reduced": "workspace workspace_bytes=1073741824 B=64 C=8 H=32 rtol=1e-4 atol=1e-6 "
                                             "total_launches=1 reduced stream=0",
+    # interpolation, fills and log-signature windows (csrc/interp_kernels.hip, csrc/logsig_kernels.hip)
+    "cde_hermite_bdiff_coeffs": "x t coeffs B=2 L=5 C=3 dtype=0 stream=0",
+    "cde_hermite_bdiff_coeffs_checked": "x t coeffs B=2 L=5 C=3 dtype=0 nan_flag stream=0",
+    "cde_hermite_bdiff_coeffs_nonblocking": "x t coeffs scratch B=2 L=5 C=3 dtype=0 nan_flag generation=1 stream=0",
+    "cde_hermite_bdiff_coeffs_backward": "grad_coeffs t grad_x B=2 L=5 C=3 dtype=0 stream=0",
+    "cde_hermite_bdiff_coeffs_backward_dt": "grad_coeffs x t grad_h B=2 L=5 C=3 dtype=0 stream=0",
+    "cde_linear_fill_missing": "x t out B=2 L=5 C=3 dtype=0 stream=0",
+    "cde_linear_fill_missing_backward": "grad_out x t grad_x B=2 L=5 C=3 dtype=0 stream=0",
+    "cde_forward_fill": "x out B=2 L=5 C=3 dtype=0 stream=0",
+    "cde_forward_fill_backward": "grad_out x grad_x B=2 L=5 C=3 dtype=0 stream=0",
+    "cde_rectilinear_prepare": "x out B=2 L=5 C=3 time_index=0 dtype=0 stream=0",
+    "cde_rectilinear_prepare_backward": "grad_out x grad_x B=2 L=5 C=3 time_index=0 dtype=0 stream=0",
+    "cde_natural_cubic_coeffs": "x t coeffs B=2 L=5 C=3 version=0 has_missing=0 dtype=0 stream=0",
+    "cde_natural_cubic_coeffs_backward_workspace_bytes": "L=5 dtype=0",
+    "cde_natural_cubic_coeffs_backward": "grad_coeffs t grad_x workspace workspace_bytes=40 B=2 L=5 C=3 dtype=0 x kd_scratch "
+                                         "grad_t_rows stream=0",
+    "cde_natural_cubic_coeffs_backward_missing": "grad_coeffs x t grad_x workspace B=2 L=5 C=3 version=0 dtype=0 stream=0",
+    "cde_logsig_windows": "x rows scale words out B=2 L=5 C=3 depth=2 n_windows=2 n_words=6 dtype=0 stream=0",
+    "cde_logsig_windows_backward": "grad_out x rows scale words grad_x workspace B=2 L=5 C=3 depth=2 n_windows=2 n_words=6 "
+                                   "dtype=0 stream=0",
+    "cde_interpret_t": "knots n_intervals=4 tq nq=3 index_out frac_out dtype=0 stream=0",
+    "cde_path_eval": "coeffs knots tq nq=3 out B=2 n_intervals=4 C=3 degree=3 what=0 dtype=0 stream=0",
+    "cde_path_eval_backward": "grad_out knots tq nq=3 grad_coeffs B=2 n_intervals=4 C=3 degree=3 what=0 dtype=0 stream=0",
+    "cde_contract": "F dX out B=2 H=4 C=3 dtype=0 stream=0",
 }
 DUMMY = 0x1000
 
@@ -371,6 +395,157 @@ REJECTED = {
         -3: ["B=0", "B=-1", "C=0", "C=-1", "H=0", "H=-1", "total_launches=0", "total_launches=-1"],
         -1: ["workspace=0", "reduced=0"],
         -5: ["workspace_bytes=7474943"],
+    },
+    # ---- interpolation, fills, log-signature windows: sizes, then the empty batch (a no-op whatever else is wrong), then
+    # the pointers, then the dtype -- which nothing looks at before the kernel is chosen
+    "cde_hermite_bdiff_coeffs": {
+        -3: ["B=-1", "L=1", "C=0", "L=1 B=0", "C=0 x=0", "L=1 dtype=7"],
+        0: ["B=0", "B=0 x=0", "B=0 dtype=7"],
+        -1: ["x=0", "t=0", "coeffs=0", "x=0 dtype=7"],
+        -2: ["dtype=7", "dtype=-1"],
+    },
+    "cde_hermite_bdiff_coeffs_checked": {
+        -3: ["B=-1", "L=1", "C=0", "L=1 B=0", "C=0 nan_flag=0"],
+        0: ["B=0", "B=0 nan_flag=0", "B=0 dtype=7"],
+        -1: ["x=0", "t=0", "coeffs=0", "nan_flag=0", "nan_flag=0 dtype=7"],
+        -2: ["dtype=7"],
+    },
+    "cde_hermite_bdiff_coeffs_nonblocking": {
+        -3: ["B=-1", "L=1", "C=0", "generation=0", "generation=-1", "generation=0 B=0", "generation=0 x=0"],
+        0: ["B=0", "B=0 scratch=0", "B=0 dtype=7"],
+        -1: ["x=0", "t=0", "coeffs=0", "scratch=0", "nan_flag=0", "scratch=0 dtype=7"],
+        -2: ["dtype=7"],
+    },
+    "cde_hermite_bdiff_coeffs_backward": {
+        -3: ["B=-1", "L=1", "C=0", "L=1 B=0"],
+        0: ["B=0", "B=0 t=0", "B=0 dtype=7"],
+        -1: ["grad_coeffs=0", "t=0", "grad_x=0", "t=0 dtype=7"],
+        -2: ["dtype=7"],
+    },
+    "cde_hermite_bdiff_coeffs_backward_dt": {
+        -3: ["B=-1", "L=1", "C=0", "L=1 B=0"],
+        0: ["B=0", "B=0 x=0", "B=0 dtype=7"],
+        -1: ["grad_coeffs=0", "x=0", "t=0", "grad_h=0", "grad_h=0 dtype=7"],
+        -2: ["dtype=7"],
+    },
+    "cde_linear_fill_missing": {
+        -3: ["B=-1", "L=1", "C=0", "L=1 B=0"],
+        0: ["B=0", "B=0 out=0", "B=0 dtype=7"],
+        -1: ["x=0", "t=0", "out=0", "out=0 dtype=7"],
+        -2: ["dtype=7"],
+    },
+    "cde_linear_fill_missing_backward": {
+        -3: ["B=-1", "L=1", "C=0", "L=1 B=0"],
+        0: ["B=0", "B=0 grad_x=0", "B=0 dtype=7"],
+        -1: ["grad_out=0", "x=0", "t=0", "grad_x=0", "grad_out=0 dtype=7"],
+        -2: ["dtype=7"],
+    },
+    # (the fills accept a single sample: L=1)
+    "cde_forward_fill": {
+        -3: ["B=-1", "L=0", "C=0", "L=0 B=0"],
+        0: ["B=0", "B=0 x=0", "B=0 dtype=7"],
+        -1: ["x=0", "out=0", "L=1 out=0", "x=0 dtype=7"],
+        -2: ["dtype=7", "L=1 dtype=7"],
+    },
+    "cde_forward_fill_backward": {
+        -3: ["B=-1", "L=0", "C=0", "L=0 B=0"],
+        0: ["B=0", "B=0 x=0", "B=0 dtype=7"],
+        -1: ["grad_out=0", "x=0", "grad_x=0", "L=1 grad_x=0", "x=0 dtype=7"],
+        -2: ["dtype=7"],
+    },
+    "cde_rectilinear_prepare": {
+        -3: ["B=-1", "L=0", "C=0", "time_index=-1", "time_index=3", "time_index=3 B=0", "time_index=-1 x=0"],
+        0: ["B=0", "B=0 x=0", "B=0 dtype=7", "B=0 time_index=2"],
+        -1: ["x=0", "out=0", "time_index=2 out=0", "x=0 dtype=7"],
+        -2: ["dtype=7"],
+    },
+    "cde_rectilinear_prepare_backward": {
+        -3: ["B=-1", "L=0", "C=0", "time_index=-1", "time_index=3", "time_index=3 B=0", "time_index=-1 x=0"],
+        0: ["B=0", "B=0 x=0", "B=0 dtype=7", "B=0 time_index=2"],
+        -1: ["grad_out=0", "x=0", "grad_x=0", "time_index=2 grad_x=0", "x=0 dtype=7"],
+        -2: ["dtype=7"],
+    },
+    "cde_natural_cubic_coeffs": {
+        -3: ["B=-1", "L=1", "C=0", "version=2", "version=-1", "version=2 B=0", "version=2 x=0"],
+        0: ["B=0", "B=0 x=0", "B=0 dtype=7", "B=0 version=1"],
+        -1: ["x=0", "t=0", "coeffs=0", "version=1 coeffs=0", "has_missing=1 x=0", "x=0 dtype=7"],
+        -2: ["dtype=7", "version=1 has_missing=1 dtype=7"],
+    },
+    # a size query: the "code" of a row is the number of bytes (an unknown dtype counts as four-byte elements)
+    "cde_natural_cubic_coeffs_backward_workspace_bytes": {
+        40: ["", "dtype=7"],
+        80: ["dtype=1"],
+        16: ["L=2"],
+        0: ["L=0"],
+    },
+    # (x and kd_scratch are needed only with grad_t_rows; the workspace is sized after the dtype is known)
+    "cde_natural_cubic_coeffs_backward": {
+        -3: ["B=-1", "L=1", "C=0", "L=1 B=0", "C=0 workspace_bytes=0"],
+        0: ["B=0", "B=0 workspace=0", "B=0 dtype=7", "B=0 workspace_bytes=0"],
+        -1: ["grad_coeffs=0", "t=0", "grad_x=0", "workspace=0", "x=0", "kd_scratch=0", "workspace=0 dtype=7",
+             "kd_scratch=0 dtype=7", "x=0 workspace_bytes=0", "grad_t_rows=0 workspace=0"],
+        -2: ["dtype=7", "dtype=7 workspace_bytes=0", "grad_t_rows=0 x=0 kd_scratch=0 dtype=7"],
+        -5: ["workspace_bytes=39", "workspace_bytes=0", "dtype=1 workspace_bytes=79", "dtype=1",
+             "grad_t_rows=0 workspace_bytes=39", "grad_t_rows=0 x=0 kd_scratch=0 workspace_bytes=39",
+             "L=6 workspace_bytes=47"],
+    },
+    "cde_natural_cubic_coeffs_backward_missing": {
+        -3: ["B=-1", "L=1", "C=0", "version=2", "version=-1", "version=2 B=0", "version=2 workspace=0"],
+        0: ["B=0", "B=0 workspace=0", "B=0 dtype=7", "B=0 version=1"],
+        -1: ["grad_coeffs=0", "x=0", "t=0", "grad_x=0", "workspace=0", "version=1 workspace=0", "workspace=0 dtype=7"],
+        -2: ["dtype=7", "version=1 dtype=7"],
+    },
+    # the envelopes (8 channels, depth 3), (5, 4), (32, 2) are looked at before the empty batch and the pointers; the rows
+    # inside an envelope fail a later check
+    "cde_logsig_windows": {
+        -3: ["B=-1", "L=0", "C=0", "n_windows=-1", "n_words=0", "L=0 depth=5", "n_words=0 C=33", "n_windows=-1 B=0"],
+        -4: ["depth=0", "depth=-1", "depth=5", "depth=4 C=6", "depth=3 C=9", "C=33", "depth=1 C=33", "depth=3 C=33",
+             "depth=4 C=6 B=0", "depth=5 B=0", "depth=5 x=0", "depth=3 C=9 dtype=7"],
+        0: ["B=0", "B=0 x=0", "B=0 dtype=7", "B=0 depth=3 C=8", "B=0 depth=4 C=5", "B=0 C=32"],
+        -1: ["x=0", "rows=0", "scale=0", "words=0", "out=0", "depth=3 C=8 x=0", "depth=1 C=8 rows=0", "depth=4 C=5 scale=0",
+             "depth=4 C=1 words=0", "C=32 out=0", "depth=1 C=32 x=0", "depth=3 C=8 out=0 dtype=7", "n_windows=0 x=0"],
+        -2: ["dtype=7", "depth=3 C=8 dtype=7", "depth=4 C=5 dtype=7", "C=32 dtype=7", "n_windows=0 dtype=7", "L=1 dtype=7"],
+    },
+    "cde_logsig_windows_backward": {
+        -3: ["B=-1", "L=0", "C=0", "n_windows=-1", "n_words=0", "L=0 depth=5", "n_words=0 C=33", "n_windows=-1 B=0"],
+        -4: ["depth=0", "depth=-1", "depth=5", "depth=4 C=6", "depth=3 C=9", "C=33", "depth=1 C=33", "depth=3 C=33",
+             "depth=4 C=6 B=0", "depth=5 B=0", "depth=5 x=0", "depth=3 C=9 dtype=7"],
+        0: ["B=0", "B=0 x=0", "B=0 dtype=7", "B=0 depth=3 C=8", "B=0 depth=4 C=5", "B=0 C=32"],
+        -1: ["grad_out=0", "x=0", "rows=0", "scale=0", "words=0", "grad_x=0", "workspace=0", "depth=3 C=8 x=0",
+             "depth=1 C=8 rows=0", "depth=4 C=5 scale=0", "depth=4 C=1 words=0", "C=32 grad_x=0", "depth=1 C=32 workspace=0",
+             "depth=3 C=8 grad_out=0 dtype=7", "n_windows=0 x=0"],
+        -2: ["dtype=7", "depth=3 C=8 dtype=7", "depth=4 C=5 dtype=7", "C=32 dtype=7", "n_windows=0 dtype=7", "L=1 dtype=7"],
+    },
+    "cde_interpret_t": {
+        -3: ["n_intervals=0", "n_intervals=-1", "nq=-1", "n_intervals=0 nq=0", "nq=-1 knots=0"],
+        0: ["nq=0", "nq=0 knots=0", "nq=0 dtype=7"],
+        -1: ["knots=0", "tq=0", "index_out=0", "frac_out=0", "n_intervals=1 tq=0", "frac_out=0 dtype=7"],
+        -2: ["dtype=7", "n_intervals=1 dtype=7"],
+    },
+    # an unknown degree or `what` is noticed where the kernel is chosen: after the pointers and the dtype
+    "cde_path_eval": {
+        -3: ["B=-1", "n_intervals=0", "C=0", "nq=-1", "n_intervals=0 B=0", "nq=-1 B=0", "C=0 degree=2", "C=0 nq=0"],
+        0: ["B=0", "nq=0", "B=0 nq=0", "B=0 coeffs=0", "nq=0 out=0", "B=0 dtype=7", "nq=0 degree=2", "B=0 what=2"],
+        -1: ["coeffs=0", "knots=0", "tq=0", "out=0", "coeffs=0 degree=2", "out=0 what=2", "coeffs=0 dtype=7",
+             "degree=1 knots=0", "what=1 tq=0"],
+        -2: ["dtype=7", "dtype=7 degree=2", "dtype=7 what=2", "dtype=7 degree=1 what=1"],
+        -4: ["degree=2", "degree=0", "degree=-1", "what=2", "what=-1", "degree=2 what=2", "degree=1 what=2",
+             "degree=2 what=1", "dtype=1 degree=2", "dtype=1 what=2"],
+    },
+    "cde_path_eval_backward": {
+        -3: ["B=-1", "n_intervals=0", "C=0", "nq=-1", "n_intervals=0 B=0", "nq=-1 B=0", "C=0 degree=2", "C=0 nq=0"],
+        0: ["B=0", "nq=0", "B=0 nq=0", "B=0 grad_out=0", "nq=0 grad_coeffs=0", "B=0 dtype=7", "nq=0 degree=2", "B=0 what=2"],
+        -1: ["grad_out=0", "knots=0", "tq=0", "grad_coeffs=0", "grad_out=0 degree=2", "grad_coeffs=0 what=2",
+             "grad_out=0 dtype=7", "degree=1 knots=0", "what=1 tq=0"],
+        -2: ["dtype=7", "dtype=7 degree=2", "dtype=7 what=2", "dtype=7 degree=1 what=1"],
+        -4: ["degree=2", "degree=0", "degree=-1", "what=2", "what=-1", "degree=2 what=2", "degree=1 what=2",
+             "degree=2 what=1", "dtype=1 degree=2", "dtype=1 what=2"],
+    },
+    "cde_contract": {
+        -3: ["B=-1", "H=0", "C=0", "H=0 B=0", "C=0 F=0"],
+        0: ["B=0", "B=0 F=0", "B=0 dtype=7"],
+        -1: ["F=0", "dX=0", "out=0", "out=0 dtype=7"],
+        -2: ["dtype=7"],
     },
 }
 

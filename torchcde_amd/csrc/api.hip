@@ -66,18 +66,10 @@ static int fill_stage_table(const Control& x, const void* grid, int64_t n_steps,
   return check_launch();
 }
 
-// A dtype code as a type: `f(Type<float>{})` / `f(Type<double>{})`, CDE_ERR_DTYPE for anything else ...
-template <typename T> struct Type { using type = T; };
-template <typename F>
-static int with_type(int dtype, F&& f) {
-  if (dtype == CDE_F32) return f(Type<float>{});
-  if (dtype == CDE_F64) return f(Type<double>{});
-  return CDE_ERR_DTYPE;
-}
-// ... and the state and time dtypes together: `f(Type<T>{}, Type<TT>{})`
+// The state and time dtypes as types together: `f(Type<T>{}, Type<TT>{})`
 template <typename F>
 static int with_types(Dtypes d, F&& f) {
-  return with_type(d.state, [&](auto t) { return with_type(d.time, [&](auto tt) -> int { return f(t, tt); }); });
+  return dispatch_dtype(d.state, [&](auto t) { return dispatch_dtype(d.time, [&](auto tt) -> int { return f(t, tt); }); });
 }
 
 // The forward direction of every solver: the stage table of `io.grid` into the caller's buffers, then `launch(T, TT)`.
@@ -353,7 +345,7 @@ extern "C" int cde_fixed_adjoint_linear(int method, const void* coeffs, const vo
   const StageWorkspace layout(n_sgrid, sizeof(float));
   const StageBuffers st = layout.table(workspace);
   hipStream_t s = (hipStream_t)stream;
-  return with_type(time_dtype, [&](auto tt) -> int {
+  return dispatch_dtype(time_dtype, [&](auto tt) -> int {
     using TT = typename decltype(tt)::type;
     const int rc = fill_stage_table<float, TT>(x, sgrid, layout.n_steps, 1, method, st, s);
     if (rc != CDE_OK) return rc;
@@ -452,7 +444,7 @@ static int mlp_prepare_impl(int negate, const Control& x, const void* grid, int6
   if (ws.bytes < cde_rk4_adjoint_mlp_workspace_bytes(n_grid)) return CDE_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   const StageWorkspace layout(n_grid, sizeof(float));
-  const int rc = with_type(d.time, [&](auto tt) {
+  const int rc = dispatch_dtype(d.time, [&](auto tt) {
     return fill_stage_table<float, typename decltype(tt)::type>(x, grid, layout.n_steps, negate, CDE_METHOD_RK4,
                                                                 layout.table(ws.base), s);
   });
@@ -519,7 +511,7 @@ static int mlp_sweep_impl(bool backprop, const Control& x, SweepIO io, int64_t n
   const StageTable st = layout.table(ws.base);
   io.image = (const float*)layout.tail(ws.base);
   io.n_steps = n_grid - 1;
-  return with_type(d.time, [&](auto tt) {
+  return dispatch_dtype(d.time, [&](auto tt) {
     using TT = typename decltype(tt)::type;
     return backprop ? launch_mlp_backprop_sweep<TT>(x, io, n, st, (hipStream_t)stream)
                     : launch_mlp_adjoint_sweep<TT>(x, io, n, st, (hipStream_t)stream);

@@ -139,7 +139,7 @@ __device__ __forceinline__ float tanh_t(float x) { return tanhf(x); }
 __device__ __forceinline__ double tanh_t(double x) { return tanh(x); }
 
 // The tuning table (include/cde_mi355x.h, CDE_OPT_*): written by cde_set_option only, read by the layout functions and the
-// launchers.  Defined in interp_kernels.hip.
+// launchers.  Defined in library.hip.
 int64_t option(int key);
 
 inline int check_launch() { return hipGetLastError() == hipSuccess ? CDE_OK : CDE_ERR_LAUNCH; }

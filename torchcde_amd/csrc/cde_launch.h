@@ -3,6 +3,8 @@
 // Host code only: declarations, and the two templates that touch the runtime for the kernel they are handed (allow_lds,
 // launch_attempts -- the latter holds a <<<>>> launch, so only .hip files include this header).  Fixed grid (rk4 / midpoint / euler): api.hip fills the structs where the C ABI's pointers enter,
 // the rk4_*.hip files define the launchers.  Adaptive (dopri5): the entry points of the dopri5*.hip files fill them.
+// Interpolation, fills, log-signature windows (interp_kernels.hip, logsig_kernels.hip): the dtype dispatch and the small
+// things their entry points share.
 #pragma once
 #include <type_traits>
 #include <hip/hip_runtime.h>
@@ -102,6 +104,15 @@ int dispatch_degree_field(int degree, int act, F&& f) {
     return f(D, Const<FIELD_SOFTPLUS_TANH>{});
   });
 }
+// a dtype code as a type: `f(Type<float>{})` / `f(Type<double>{})` (`using T = typename decltype(tag)::type;`),
+// CDE_ERR_DTYPE for anything else
+template <typename T> struct Type { using type = T; };
+template <typename F>
+int dispatch_dtype(int dtype, F&& f) {
+  if (dtype == CDE_F32) return f(Type<float>{});
+  if (dtype == CDE_F64) return f(Type<double>{});
+  return CDE_ERR_DTYPE;
+}
 // `kernel`'s dynamic LDS limit, raised to what the launch asks for
 template <typename K>
 void allow_lds(K kernel, size_t bytes) {
@@ -119,6 +130,27 @@ int launch_attempts(K kernel, unsigned grid, unsigned block, size_t lds, hipStre
     if (rc != CDE_OK) return rc;
   }
   return CDE_OK;
+}
+
+// ---------------------------------------------------------------- interp_kernels.hip, logsig_kernels.hip (f32 / f64)
+template <typename F>
+int dispatch_what(int what, F&& f) {
+  if (what == CDE_EVAL_DERIVATIVE) return f(Const<CDE_EVAL_DERIVATIVE>{});
+  if (what == CDE_EVAL_VALUE) return f(Const<CDE_EVAL_VALUE>{});
+  return CDE_ERR_UNSUPPORTED;
+}
+template <typename F>
+int dispatch_flag(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+// a batch of series (B, L, C); `ok`: the size check of every entry point that takes one (the fills accept L = 1)
+struct Series {
+  int64_t B, L, C;
+  bool ok(int64_t min_L = 2) const { return B >= 0 && L >= min_L && C >= 1; }
+};
+// workgroups for one lane per item; `grid_stride_blocks`: for the kernels that loop, at most 65536
+static inline unsigned blocks_for(int64_t items, int per_block = 256) { return (unsigned)((items + per_block - 1) / per_block); }
+static inline unsigned grid_stride_blocks(int64_t items) {
+  const int64_t g = (items + 255) / 256;
+  return (unsigned)(g > 65536 ? 65536 : g);
 }
 
 // ---------------------------------------------------------------- rk4_generic.hip (any shape, f32 / f64)

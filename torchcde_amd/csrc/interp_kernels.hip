@@ -1,6 +1,8 @@
-// interp_kernels.hip -- K1 (Hermite fit), K1b (interval lookup + path evaluation), contraction.
+// interp_kernels.hip -- K0 / K0b / K0c (fills), K1 / K1n (Hermite and natural-cubic fits), K1b (interval lookup + path
+// evaluation), contraction; each with its backward.  (K5, the log-signature windows: logsig_kernels.hip.)
 // HBM-bound streaming kernels: one lane per 16-byte output vector, fully coalesced stores.
 #include "cde_common.h"
+#include "cde_launch.h"
 
 namespace cde {
 
@@ -135,23 +137,20 @@ __global__ __launch_bounds__(256) void hermite_bdiff_kernel(const T* __restrict_
   *reinterpret_cast<Vec<T, V>*>(o + 3 * C) = three_d;
 }
 
+// one 16-byte vector per lane where the pointers and C allow it, one value otherwise; the NaN scan only with a flag to raise
 template <typename T>
-static int launch_hermite(const void* x, const void* t, void* out, int64_t B, int64_t L, int64_t C, int* nan_flag,
-                          hipStream_t s, int mark = 1, const int* gate = nullptr, int gate_value = 0) {
+static int launch_hermite(const void* x, const void* t, void* out, const Series& n, int* nan_flag, hipStream_t s,
+                          int mark = 1, const int* gate = nullptr, int gate_value = 0) {
   constexpr int VMAX = 16 / sizeof(T);
-  if (B * (L - 1) * C == 0) return CDE_OK;
-  const bool aligned = ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0);
-  auto grid_for = [](int64_t n) { return (unsigned)((n + 255) / 256); };
-#define CDE_K1(V, CHECK, N)                                                                                         \
-  hermite_bdiff_kernel<T, V, CHECK><<<grid_for(N), 256, 0, s>>>((const T*)x, (const T*)t, (T*)out, B, L, C, nan_flag, mark, \
-                                                               gate, gate_value)
-  if (aligned && C % VMAX == 0) {
-    if (nan_flag) CDE_K1(VMAX, true, B * (L - 1) * (C / VMAX)); else CDE_K1(VMAX, false, B * (L - 1) * (C / VMAX));
-  } else {
-    if (nan_flag) CDE_K1(1, true, B * (L - 1) * C); else CDE_K1(1, false, B * (L - 1) * C);
-  }
-#undef CDE_K1
-  return check_launch();
+  const bool vectorised = (uintptr_t)x % 16 == 0 && (uintptr_t)out % 16 == 0 && n.C % VMAX == 0;
+  return dispatch_flag(vectorised, [&](auto wide) {
+    return dispatch_flag(nan_flag != nullptr, [&](auto check) {
+      constexpr int V = wide() ? VMAX : 1;
+      hermite_bdiff_kernel<T, V, check()><<<blocks_for(n.B * (n.L - 1) * (n.C / V)), 256, 0, s>>>(
+          (const T*)x, (const T*)t, (T*)out, n.B, n.L, n.C, nan_flag, mark, gate, gate_value);
+      return check_launch();
+    });
+  });
 }
 
 // K1 backward: the fit is linear in x, so dL/dx is the transposed map applied to dL/dcoeffs.  With
@@ -256,6 +255,14 @@ __global__ __launch_bounds__(256) void linear_fill_kernel(const T* __restrict__ 
       x_lo = xi;
     }
   }
+}
+
+// (queues the launch only: the caller asks for the launch status, the gated pass of K1 after its last launch)
+template <typename T>
+static void launch_linear_fill(const void* x, const void* t, void* out, const Series& n, hipStream_t s,
+                               const int* gate = nullptr, int gate_value = 0) {
+  linear_fill_kernel<T><<<blocks_for(n.B * n.C), 256, 0, s>>>(
+      (const T*)x, (const T*)t, (T*)out, n.B, n.L, n.C, gate, gate_value);
 }
 
 // Backward of linear_fill_kernel w.r.t. the observed values: every filled entry is x_lo + r (x_hi - x_lo) of its two
@@ -708,320 +715,6 @@ __global__ __launch_bounds__(256) void natural_cubic_backward_missing_kernel(con
   }
 }
 
-// ------------------------------------------------------------------------------------------ K5 log-ODE windows
-// logsig_windows / logsignature_windows (reference log_ode.py:15-133) after the host has merged the window
-// boundaries into the series and filled them linearly: for every window the logsignature (depth <= 3) of the
-// piecewise-linear path between two boundary rows, optionally scaled, accumulated along the windows.
-// The arithmetic the reference gets from the `signatory` package (absent here; see oracle/logsig.py): signature by
-// Chen's identity  S <- S (x) exp(d)  over the increments, tensor-algebra logarithm, coefficients of the Lyndon words
-// (`words`: (level, flat index) pairs in signatory's order, built by the host).
-// The signature levels live in per-lane arrays, so the kernel is instantiated for the (channels, depth) envelopes that
-// occur: up to 8 channels to depth 3 (config 5 and the examples), up to 5 channels to depth 4 (the reference's test
-// runs depth 1-4 on 1-3 channels), up to 32 channels to depth 2.
-template <int N, int P> struct IPow { static constexpr int value = N * IPow<N, P - 1>::value; };
-template <int N> struct IPow<N, 0> { static constexpr int value = 1; };
-
-// pass 1: one lane per (series, window) -- the windows of a series are independent until the running sum
-template <typename T, int MAXC, int MAXD>
-__global__ __launch_bounds__(64) void logsig_windows_kernel(const T* __restrict__ x, const int64_t* __restrict__ rows,
-                                                            const T* __restrict__ scale, const int32_t* __restrict__ words,
-                                                            T* __restrict__ out, int64_t B, int64_t L, int C, int depth,
-                                                            int64_t n_windows, int n_words) {
-  const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= B * n_windows) return;
-  const int64_t b = id / n_windows, win = id - b * n_windows;
-  const T* src = x + b * L * C;
-  T* dst = out + (b * (n_windows + 1) + win + 1) * n_words;
-  T S1[MAXC], S2[MAXD >= 2 ? IPow<MAXC, 2>::value : 1], S3[MAXD >= 3 ? IPow<MAXC, 3>::value : 1],
-      S4[MAXD >= 4 ? IPow<MAXC, 4>::value : 1];
-  const int C2 = C * C, C3 = C2 * C;
-  for (int i = 0; i < C; ++i) S1[i] = (T)0;
-  if (MAXD >= 2 && depth >= 2) for (int i = 0; i < C2; ++i) S2[i] = (T)0;
-  if (MAXD >= 3 && depth >= 3) for (int i = 0; i < C3; ++i) S3[i] = (T)0;
-  if (MAXD >= 4 && depth >= 4) for (int i = 0; i < C3 * C; ++i) S4[i] = (T)0;
-  for (int64_t r = rows[win]; r < rows[win + 1]; ++r) {
-    T d[MAXC];
-    for (int i = 0; i < C; ++i) d[i] = src[(r + 1) * C + i] - src[r * C + i];
-    // levels of S (x) exp(d), highest first (they read the old lower levels); exp(d): e1 = d, e2 = e1 (x) d / 2, ...
-    // level k = S_k + e_k + S_1 (x) e_(k-1) + ... + S_(k-1) (x) e_1, added in that order (oracle/logsig.py)
-    if (MAXD >= 4 && depth >= 4)
-      for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j) {
-          const T e2ij = d[i] * d[j] / (T)2;
-          for (int k = 0; k < C; ++k) {
-            const T e3ijk = e2ij * d[k] / (T)3;
-            const T e2jk = d[j] * d[k] / (T)2;
-            for (int l = 0; l < C; ++l) {
-              const int at = ((i * C + j) * C + k) * C + l;
-              T acc = S4[at] + e3ijk * d[l] / (T)4;
-              acc = acc + S1[i] * (e2jk * d[l] / (T)3);
-              acc = acc + S2[i * C + j] * (d[k] * d[l] / (T)2);
-              acc = acc + S3[(i * C + j) * C + k] * d[l];
-              S4[at] = acc;
-            }
-          }
-        }
-    if (MAXD >= 3 && depth >= 3)
-      for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j) {
-          const T e2 = d[i] * d[j] / (T)2;
-          for (int k = 0; k < C; ++k) {
-            T acc = S3[(i * C + j) * C + k] + e2 * d[k] / (T)3;
-            acc = acc + S1[i] * (d[j] * d[k] / (T)2);
-            acc = acc + S2[i * C + j] * d[k];
-            S3[(i * C + j) * C + k] = acc;
-          }
-        }
-    if (MAXD >= 2 && depth >= 2)
-      for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j) S2[i * C + j] = (S2[i * C + j] + d[i] * d[j] / (T)2) + S1[i] * d[j];
-    for (int i = 0; i < C; ++i) S1[i] = S1[i] + d[i];
-  }
-  // logarithm: log(1 + S) = S - S^2/2 + S^3/3 - S^4/4, level by level, then the Lyndon-word coordinates
-  const T sc = scale[win];
-  for (int w = 0; w < n_words; ++w) {
-    const int level = words[2 * w], flat = words[2 * w + 1];
-    T value;
-    if (level == 1) value = S1[flat];
-    else if (level == 2) {
-      const int i = flat / C, j = flat - i * C;
-      value = S2[flat] + (-(S1[i] * S1[j])) / (T)2;
-    } else if (level == 3) {
-      const int i = flat / C2, jk = flat - i * C2, j = jk / C, k = jk - j * C;
-      const T p2 = (S1[i] * S2[j * C + k]) + S2[i * C + j] * S1[k];          // (S^2)_3
-      const T p3 = (S1[i] * S1[j]) * S1[k];                                   // (S^3)_3
-      value = (S3[flat] + (-p2) / (T)2) + p3 / (T)3;
-    } else {
-      const int i = flat / C3, jkl = flat - i * C3, j = jkl / C2, kl = jkl - j * C2, k = kl / C, l = kl - k * C;
-      const int ij = i * C + j, ijk = ij * C + k;
-      const T p2 = ((S1[i] * S3[jkl]) + S2[ij] * S2[kl]) + S3[ijk] * S1[l];                      // (S^2)_4
-      const T s2_3 = (S1[i] * S2[j * C + k]) + S2[ij] * S1[k];                                   // (S^2)_3 at ijk
-      const T p3 = ((S1[i] * S1[j]) * S2[kl]) + s2_3 * S1[l];                                    // (S^3)_4
-      const T p4 = ((S1[i] * S1[j]) * S1[k]) * S1[l];                                            // (S^4)_4
-      value = ((S4[flat] + (-p2) / (T)2) + p3 / (T)3) + (-p4) / (T)4;
-    }
-    dst[w] = value * sc;
-  }
-}
-
-// pass 2: the running sum of log_ode.py:63 (sequential, like torch.cumsum on the CPU), one lane per (series, coordinate);
-// row 0 = the first observation padded with zeros (log_ode.py:50-52)
-template <typename T>
-__global__ __launch_bounds__(256) void logsig_accumulate_kernel(const T* __restrict__ x, T* __restrict__ out, int64_t B,
-                                                                int64_t L, int C, int64_t n_windows, int n_words) {
-  const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= B * n_words) return;
-  const int64_t b = id / n_words;
-  const int w = (int)(id - b * n_words);
-  T* col = out + b * (n_windows + 1) * n_words + w;
-  T run = w < C ? x[b * L * C + w] : (T)0;
-  col[0] = run;
-  for (int64_t win = 1; win <= n_windows; ++win) { run = run + col[win * n_words]; col[win * n_words] = run; }
-}
-
-// ---- K5 backward (autograd through signatory's logsignature and the running sum of log_ode.py:53-63)
-// pass 1: the running sum transposed -- suffix sums of grad_out along the windows, one lane per (series, coordinate);
-// row k of `gsum` = sum of the rows >= k.  Row 0 is the gradient of the first observation (first C coordinates).
-template <typename T>
-__global__ __launch_bounds__(256) void logsig_suffix_kernel(const T* __restrict__ grad_out, T* __restrict__ gsum,
-                                                            T* __restrict__ grad_x, int64_t B, int64_t L, int C,
-                                                            int64_t n_windows, int n_words) {
-  const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= B * n_words) return;
-  const int64_t b = id / n_words;
-  const int w = (int)(id - b * n_words);
-  const T* src = grad_out + b * (n_windows + 1) * n_words + w;
-  T* dst = gsum + b * (n_windows + 1) * n_words + w;
-  T run = (T)0;
-  for (int64_t win = n_windows; win >= 0; --win) { run = run + src[win * n_words]; dst[win * n_words] = run; }
-  if (w < C) grad_x[b * L * C + w] = run;                  // grad_x was zeroed by the caller; pass 2 adds to it
-}
-
-// pass 2: one lane per (series, window).  The signature levels below the top one are rebuilt (the logarithm's and the
-// Chen step's derivatives never read the top level), the word coordinates and the logarithm are differentiated into
-// gS, and the Chen recursion is walked BACKWARDS: before increment r is differentiated the signature is stepped back
-// with  S <- S (x) exp(-d_r)  (the reversibility signatory's own backward relies on), then
-//   new_k = S_k + e_k(d) + sum_j S_j (x) e_(k-j)(d),  e_m(d) = d^(x m) / m!
-// is transposed level by level, LOWEST level first (level k reads gS_k of the new signature, which the lower levels'
-// updates have not touched, and adds to the lower gS).  No atomics, fixed summation order: rows interior to a window get
-// both of their increments' contributions from this lane (one plain store); of a boundary row's two contributions the
-// one from the window BELOW it (that window's last increment) is parked in the first C slots of the window's own `gsum`
-// row -- dead once the lane has read it -- and the one from the window above it is added in place by that window's lane,
-// the row's only writer in this pass; pass 3 then adds the parked values window by window.
-template <typename T, int MAXC, int MAXD>
-__global__ __launch_bounds__(64) void logsig_windows_backward_kernel(T* gsum, const T* __restrict__ x,
-                                                                     const int64_t* __restrict__ rows,
-                                                                     const T* __restrict__ scale,
-                                                                     const int32_t* __restrict__ words,
-                                                                     T* __restrict__ grad_x, int64_t B, int64_t L, int C,
-                                                                     int depth, int64_t n_windows, int n_words) {
-  const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= B * n_windows) return;
-  const int64_t b = id / n_windows, win = id - b * n_windows;
-  const T* src = x + b * L * C;
-  T* gx = grad_x + b * L * C;
-  T* gw = gsum + (b * (n_windows + 1) + win + 1) * n_words;
-  T S1[MAXC], S2[MAXD >= 3 ? IPow<MAXC, 2>::value : 1], S3[MAXD >= 4 ? IPow<MAXC, 3>::value : 1];
-  T g1[MAXC], g2[MAXD >= 2 ? IPow<MAXC, 2>::value : 1], g3[MAXD >= 3 ? IPow<MAXC, 3>::value : 1],
-      g4[MAXD >= 4 ? IPow<MAXC, 4>::value : 1];
-  const int C2 = C * C, C3 = C2 * C;
-  for (int i = 0; i < C; ++i) { S1[i] = (T)0; g1[i] = (T)0; }
-  if (MAXD >= 2 && depth >= 2) for (int i = 0; i < C2; ++i) g2[i] = (T)0;
-  if (MAXD >= 3 && depth >= 3) for (int i = 0; i < C2; ++i) S2[i] = (T)0;
-  if (MAXD >= 3 && depth >= 3) for (int i = 0; i < C3; ++i) g3[i] = (T)0;
-  if (MAXD >= 4 && depth >= 4) for (int i = 0; i < C3; ++i) S3[i] = (T)0;
-  if (MAXD >= 4 && depth >= 4) for (int i = 0; i < C3 * C; ++i) g4[i] = (T)0;
-  const int64_t r_lo = rows[win], r_hi = rows[win + 1];
-  // ---- the signature of the window, levels 1 .. depth-1 (same operations as the forward kernel)
-  for (int64_t r = r_lo; r < r_hi; ++r) {
-    T d[MAXC];
-    for (int i = 0; i < C; ++i) d[i] = src[(r + 1) * C + i] - src[r * C + i];
-    if (MAXD >= 4 && depth >= 4)
-      for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j) {
-          const T e2 = d[i] * d[j] / (T)2;
-          for (int k = 0; k < C; ++k) {
-            T acc = S3[(i * C + j) * C + k] + e2 * d[k] / (T)3;
-            acc = acc + S1[i] * (d[j] * d[k] / (T)2);
-            acc = acc + S2[i * C + j] * d[k];
-            S3[(i * C + j) * C + k] = acc;
-          }
-        }
-    if (MAXD >= 3 && depth >= 3)
-      for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j) S2[i * C + j] = (S2[i * C + j] + d[i] * d[j] / (T)2) + S1[i] * d[j];
-    for (int i = 0; i < C; ++i) S1[i] = S1[i] + d[i];
-  }
-  // ---- word coordinates and logarithm, transposed
-  const T sc = scale[win];
-  for (int w = 0; w < n_words; ++w) {
-    const int level = words[2 * w], flat = words[2 * w + 1];
-    const T g = gw[w] * sc;
-    if (level == 1) g1[flat] += g;
-    else if (level == 2) {
-      if (MAXD >= 2) {
-        const int i = flat / C, j = flat - i * C;
-        g2[flat] += g;
-        const T h = -g / (T)2;
-        const T si = S1[i], sj = S1[j];
-        g1[i] += h * sj; g1[j] += h * si;
-      }
-    } else if (level == 3) {
-      if (MAXD >= 3) {
-        const int i = flat / C2, jk = flat - i * C2, j = jk / C, k = jk - j * C, ij = i * C + j;
-        g3[flat] += g;
-        const T h2 = -g / (T)2, h3 = g / (T)3;
-        const T si = S1[i], sj = S1[j], sk = S1[k], sjk = S2[jk], sij = S2[ij];
-        g1[i] += h2 * sjk + h3 * sj * sk;
-        g1[j] += h3 * si * sk;
-        g1[k] += h2 * sij + h3 * si * sj;
-        g2[jk] += h2 * si;
-        g2[ij] += h2 * sk;
-      }
-    } else {
-      if (MAXD >= 4) {
-        const int i = flat / C3, jkl = flat - i * C3, j = jkl / C2, kl = jkl - j * C2, k = kl / C, l = kl - k * C;
-        const int ij = i * C + j, jk = j * C + k, ijk = ij * C + k;
-        g4[flat] += g;
-        const T h2 = -g / (T)2, h3 = g / (T)3, h4 = -g / (T)4;
-        const T si = S1[i], sj = S1[j], sk = S1[k], sl = S1[l];
-        const T sij = S2[ij], sjk = S2[jk], skl = S2[kl], sijk = S3[ijk], sjkl = S3[jkl];
-        // (S^2)_4 = S1_i S3_jkl + S2_ij S2_kl + S3_ijk S1_l
-        g1[i] += h2 * sjkl; g3[jkl] += h2 * si;
-        g2[ij] += h2 * skl; g2[kl] += h2 * sij;
-        g3[ijk] += h2 * sl; g1[l] += h2 * sijk;
-        // (S^3)_4 = S1_i S1_j S2_kl + (S1_i S2_jk + S2_ij S1_k) S1_l
-        const T s23 = si * sjk + sij * sk, hs = h3 * sl;
-        g1[i] += h3 * sj * skl + hs * sjk;
-        g1[j] += h3 * si * skl;
-        g2[kl] += h3 * si * sj;
-        g1[l] += h3 * s23;
-        g2[jk] += hs * si;
-        g2[ij] += hs * sk;
-        g1[k] += hs * sij;
-        // (S^4)_4 = S1_i S1_j S1_k S1_l
-        g1[i] += h4 * sj * sk * sl; g1[j] += h4 * si * sk * sl; g1[k] += h4 * si * sj * sl; g1[l] += h4 * si * sj * sk;
-      }
-    }
-  }
-  // ---- Chen's recursion backwards
-  T carry[MAXC];                                            // -(dL/dd) of the increment above: what row r+1 still owes
-  for (int i = 0; i < C; ++i) carry[i] = (T)0;
-  for (int64_t r = r_hi - 1; r >= r_lo; --r) {
-    T d[MAXC], gd[MAXC];
-    for (int i = 0; i < C; ++i) d[i] = src[(r + 1) * C + i] - src[r * C + i];
-    // step the signature back: S <- S (x) exp(-d), highest level first
-    if (MAXD >= 4 && depth >= 4)
-      for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j) {
-          const T e2 = d[i] * d[j] / (T)2;
-          for (int k = 0; k < C; ++k)
-            S3[(i * C + j) * C + k] = ((S3[(i * C + j) * C + k] - e2 * d[k] / (T)3) + S1[i] * (d[j] * d[k] / (T)2)) - S2[i * C + j] * d[k];
-        }
-    if (MAXD >= 3 && depth >= 3)
-      for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j) S2[i * C + j] = (S2[i * C + j] + d[i] * d[j] / (T)2) - S1[i] * d[j];
-    if (depth >= 2) for (int i = 0; i < C; ++i) S1[i] = S1[i] - d[i];
-    // transposed step, lowest level first
-    for (int i = 0; i < C; ++i) gd[i] = g1[i];
-    if (MAXD >= 2 && depth >= 2)
-      for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j) {
-          const T G = g2[i * C + j];
-          gd[i] += G * d[j] / (T)2;
-          gd[j] += G * (d[i] / (T)2 + S1[i]);
-          g1[i] += G * d[j];
-        }
-    if (MAXD >= 3 && depth >= 3)
-      for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j)
-          for (int k = 0; k < C; ++k) {
-            const T G = g3[(i * C + j) * C + k];
-            const T s1 = S1[i], s2 = S2[i * C + j];
-            gd[i] += G * d[j] * d[k] / (T)6;
-            gd[j] += G * (d[i] * d[k] / (T)6 + s1 * d[k] / (T)2);
-            gd[k] += G * (d[i] * d[j] / (T)6 + s1 * d[j] / (T)2 + s2);
-            g1[i] += G * d[j] * d[k] / (T)2;
-            g2[i * C + j] += G * d[k];
-          }
-    if (MAXD >= 4 && depth >= 4)
-      for (int i = 0; i < C; ++i)
-        for (int j = 0; j < C; ++j)
-          for (int k = 0; k < C; ++k)
-            for (int l = 0; l < C; ++l) {
-              const T G = g4[((i * C + j) * C + k) * C + l];
-              const T s1 = S1[i], s2 = S2[i * C + j], s3 = S3[(i * C + j) * C + k];
-              gd[i] += G * d[j] * d[k] * d[l] / (T)24;
-              gd[j] += G * (d[i] * d[k] * d[l] / (T)24 + s1 * d[k] * d[l] / (T)6);
-              gd[k] += G * (d[i] * d[j] * d[l] / (T)24 + s1 * d[j] * d[l] / (T)6 + s2 * d[l] / (T)2);
-              gd[l] += G * (d[i] * d[j] * d[k] / (T)24 + s1 * d[j] * d[k] / (T)6 + s2 * d[k] / (T)2 + s3);
-              g1[i] += G * d[j] * d[k] * d[l] / (T)6;
-              g2[i * C + j] += G * d[k] * d[l] / (T)2;
-              g3[(i * C + j) * C + k] += G * d[l];
-            }
-    // d = x_{r+1} - x_r
-    if (r == r_hi - 1) for (int i = 0; i < C; ++i) { gw[i] = gd[i]; carry[i] = -gd[i]; }       // boundary row above: parked
-    else for (int i = 0; i < C; ++i) { gx[(r + 1) * C + i] = gd[i] + carry[i]; carry[i] = -gd[i]; }
-  }
-  if (r_hi > r_lo) for (int i = 0; i < C; ++i) gx[r_lo * C + i] += carry[i];
-  else for (int i = 0; i < C; ++i) gw[i] = (T)0;           // empty window: nothing parked
-}
-
-// pass 3: the parked boundary contributions, one lane per (series, channel), windows in order (several empty windows may
-// share a row)
-template <typename T>
-__global__ __launch_bounds__(256) void logsig_boundary_kernel(const T* __restrict__ gsum, const int64_t* __restrict__ rows,
-                                                              T* __restrict__ grad_x, int64_t B, int64_t L, int C,
-                                                              int64_t n_windows, int n_words) {
-  const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= B * C) return;
-  const int64_t b = id / C;
-  const int i = (int)(id - b * C);
-  T* gx = grad_x + b * L * C + i;
-  const T* parked = gsum + b * (n_windows + 1) * n_words + i;
-  for (int64_t win = 0; win < n_windows; ++win) gx[rows[win + 1] * C] += parked[(win + 1) * n_words];
-}
-
 // ------------------------------------------------------------------------------------------ K1b
 template <typename T>
 __global__ void interpret_t_kernel(const T* __restrict__ knots, int64_t n_intervals, const T* __restrict__ tq,
@@ -1100,40 +793,6 @@ __global__ __launch_bounds__(256) void path_eval_backward_kernel(const T* __rest
   }
 }
 
-template <typename T>
-static int launch_path_eval_backward(const void* grad_out, const void* knots, const void* tq, int64_t nq, void* grad_coeffs,
-                                     int64_t B, int64_t n_intervals, int64_t C, int degree, int what, hipStream_t s) {
-  if (B * C == 0 || nq == 0) return CDE_OK;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-#define CDE_PB(D, W) \
-  path_eval_backward_kernel<T, D, W><<<grid, 256, 0, s>>>((const T*)grad_out, (const T*)knots, (const T*)tq, nq, (T*)grad_coeffs, B, n_intervals, C)
-  if (degree == CDE_PATH_CUBIC && what == CDE_EVAL_DERIVATIVE) CDE_PB(CDE_PATH_CUBIC, CDE_EVAL_DERIVATIVE);
-  else if (degree == CDE_PATH_CUBIC && what == CDE_EVAL_VALUE) CDE_PB(CDE_PATH_CUBIC, CDE_EVAL_VALUE);
-  else if (degree == CDE_PATH_LINEAR && what == CDE_EVAL_DERIVATIVE) CDE_PB(CDE_PATH_LINEAR, CDE_EVAL_DERIVATIVE);
-  else if (degree == CDE_PATH_LINEAR && what == CDE_EVAL_VALUE) CDE_PB(CDE_PATH_LINEAR, CDE_EVAL_VALUE);
-  else return CDE_ERR_UNSUPPORTED;
-#undef CDE_PB
-  return check_launch();
-}
-
-template <typename T>
-static int launch_path_eval(const void* coeffs, const void* knots, const void* tq, int64_t nq, void* out, int64_t B,
-                            int64_t n_intervals, int64_t C, int degree, int what, hipStream_t s) {
-  const int64_t total = B * nq * C;
-  if (total == 0) return CDE_OK;
-  int64_t g = (total + 255) / 256;
-  const unsigned grid = (unsigned)(g > 65536 ? 65536 : g);
-#define CDE_PE(D, W) \
-  path_eval_kernel<T, D, W><<<grid, 256, 0, s>>>((const T*)coeffs, (const T*)knots, (const T*)tq, nq, (T*)out, B, n_intervals, C)
-  if (degree == CDE_PATH_CUBIC && what == CDE_EVAL_DERIVATIVE) CDE_PE(CDE_PATH_CUBIC, CDE_EVAL_DERIVATIVE);
-  else if (degree == CDE_PATH_CUBIC && what == CDE_EVAL_VALUE) CDE_PE(CDE_PATH_CUBIC, CDE_EVAL_VALUE);
-  else if (degree == CDE_PATH_LINEAR && what == CDE_EVAL_DERIVATIVE) CDE_PE(CDE_PATH_LINEAR, CDE_EVAL_DERIVATIVE);
-  else if (degree == CDE_PATH_LINEAR && what == CDE_EVAL_VALUE) CDE_PE(CDE_PATH_LINEAR, CDE_EVAL_VALUE);
-  else return CDE_ERR_UNSUPPORTED;
-#undef CDE_PE
-  return check_launch();
-}
-
 // ------------------------------------------------------------------------------------------ contraction
 // out[b,h] = sum_c F[b,h,c]*dX[b,c]   (solver.py:130); one lane per (b,h), F rows are C contiguous floats.
 template <typename T>
@@ -1153,26 +812,32 @@ __global__ __launch_bounds__(256) void contract_kernel(const T* __restrict__ F, 
 }  // namespace cde
 
 // ================================================================================================ C ABI
+// Every entry point checks, in this order: the sizes, the empty batch (a no-op), the pointers, and -- where the kernel
+// is chosen -- the dtype.  tests/rejected_calls.py pins the order.
+using namespace cde;
+
+static int hermite_fit(const void* x, const void* t, void* coeffs, const Series& n, int dtype, int* nan_flag, void* stream) {
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return launch_hermite<typename decltype(tag)::type>(x, t, coeffs, n, nan_flag, (hipStream_t)stream);
+  });
+}
+
 extern "C" int cde_hermite_bdiff_coeffs(const void* x, const void* t, void* coeffs, int64_t B, int64_t L, int64_t C,
                                         int dtype, void* stream) {
-  if (B < 0 || L < 2 || C < 1) return CDE_ERR_SHAPE;
+  const Series n{B, L, C};
+  if (!n.ok()) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!x || !t || !coeffs) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == CDE_F32) return cde::launch_hermite<float>(x, t, coeffs, B, L, C, nullptr, s);
-  if (dtype == CDE_F64) return cde::launch_hermite<double>(x, t, coeffs, B, L, C, nullptr, s);
-  return CDE_ERR_DTYPE;
+  return hermite_fit(x, t, coeffs, n, dtype, nullptr, stream);
 }
 
 extern "C" int cde_hermite_bdiff_coeffs_checked(const void* x, const void* t, void* coeffs, int64_t B, int64_t L,
                                                 int64_t C, int dtype, int* nan_flag, void* stream) {
-  if (B < 0 || L < 2 || C < 1) return CDE_ERR_SHAPE;
+  const Series n{B, L, C};
+  if (!n.ok()) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!x || !t || !coeffs || !nan_flag) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == CDE_F32) return cde::launch_hermite<float>(x, t, coeffs, B, L, C, nan_flag, s);
-  if (dtype == CDE_F64) return cde::launch_hermite<double>(x, t, coeffs, B, L, C, nan_flag, s);
-  return CDE_ERR_DTYPE;
+  return hermite_fit(x, t, coeffs, n, dtype, nan_flag, stream);
 }
 
 // K1 without a host round trip: the checked fit, then -- gated ON THE DEVICE by the flag the first launch may have raised
@@ -1180,278 +845,180 @@ extern "C" int cde_hermite_bdiff_coeffs_checked(const void* x, const void* t, vo
 extern "C" int cde_hermite_bdiff_coeffs_nonblocking(const void* x, const void* t, void* coeffs, void* scratch, int64_t B,
                                                     int64_t L, int64_t C, int dtype, int* nan_flag, int generation,
                                                     void* stream) {
-  if (B < 0 || L < 2 || C < 1 || generation < 1) return CDE_ERR_SHAPE;
+  const Series n{B, L, C};
+  if (!n.ok() || generation < 1) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!x || !t || !coeffs || !scratch || !nan_flag) return CDE_ERR_NULL;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-  int rc;
-  if (dtype == CDE_F32) {
-    rc = cde::launch_hermite<float>(x, t, coeffs, B, L, C, nan_flag, s, generation);
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const int rc = launch_hermite<T>(x, t, coeffs, n, nan_flag, s, generation);
     if (rc != CDE_OK) return rc;
-    cde::linear_fill_kernel<float><<<grid, 256, 0, s>>>((const float*)x, (const float*)t, (float*)scratch, B, L, C, nan_flag,
-                                                        generation);
-    return cde::launch_hermite<float>(scratch, t, coeffs, B, L, C, nullptr, s, 1, nan_flag, generation);
-  }
-  if (dtype == CDE_F64) {
-    rc = cde::launch_hermite<double>(x, t, coeffs, B, L, C, nan_flag, s, generation);
-    if (rc != CDE_OK) return rc;
-    cde::linear_fill_kernel<double><<<grid, 256, 0, s>>>((const double*)x, (const double*)t, (double*)scratch, B, L, C,
-                                                         nan_flag, generation);
-    return cde::launch_hermite<double>(scratch, t, coeffs, B, L, C, nullptr, s, 1, nan_flag, generation);
-  }
-  return CDE_ERR_DTYPE;
+    launch_linear_fill<T>(x, t, scratch, n, s, nan_flag, generation);
+    return launch_hermite<T>(scratch, t, coeffs, n, nullptr, s, 1, nan_flag, generation);
+  });
 }
 
 extern "C" int cde_linear_fill_missing(const void* x, const void* t, void* out, int64_t B, int64_t L, int64_t C, int dtype,
                                        void* stream) {
-  if (B < 0 || L < 2 || C < 1) return CDE_ERR_SHAPE;
+  const Series n{B, L, C};
+  if (!n.ok()) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!x || !t || !out) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-  if (dtype == CDE_F32)
-    cde::linear_fill_kernel<float><<<grid, 256, 0, s>>>((const float*)x, (const float*)t, (float*)out, B, L, C);
-  else if (dtype == CDE_F64)
-    cde::linear_fill_kernel<double><<<grid, 256, 0, s>>>((const double*)x, (const double*)t, (double*)out, B, L, C);
-  else
-    return CDE_ERR_DTYPE;
-  return cde::check_launch();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    launch_linear_fill<typename decltype(tag)::type>(x, t, out, n, (hipStream_t)stream);
+    return check_launch();
+  });
 }
 
 extern "C" int cde_linear_fill_missing_backward(const void* grad_out, const void* x, const void* t, void* grad_x,
                                                 int64_t B, int64_t L, int64_t C, int dtype, void* stream) {
-  if (B < 0 || L < 2 || C < 1) return CDE_ERR_SHAPE;
+  if (!Series{B, L, C}.ok()) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!grad_out || !x || !t || !grad_x) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-  if (dtype == CDE_F32)
-    cde::linear_fill_backward_kernel<float><<<grid, 256, 0, s>>>((const float*)grad_out, (const float*)x, (const float*)t,
-                                                                 (float*)grad_x, B, L, C);
-  else if (dtype == CDE_F64)
-    cde::linear_fill_backward_kernel<double><<<grid, 256, 0, s>>>((const double*)grad_out, (const double*)x,
-                                                                  (const double*)t, (double*)grad_x, B, L, C);
-  else
-    return CDE_ERR_DTYPE;
-  return cde::check_launch();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    linear_fill_backward_kernel<T><<<blocks_for(B * C), 256, 0, (hipStream_t)stream>>>(
+        (const T*)grad_out, (const T*)x, (const T*)t, (T*)grad_x, B, L, C);
+    return check_launch();
+  });
 }
-
 
 extern "C" int cde_hermite_bdiff_coeffs_backward(const void* grad_coeffs, const void* t, void* grad_x, int64_t B,
                                                  int64_t L, int64_t C, int dtype, void* stream) {
-  if (B < 0 || L < 2 || C < 1) return CDE_ERR_SHAPE;
+  if (!Series{B, L, C}.ok()) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!grad_coeffs || !t || !grad_x) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * L * C + 255) / 256);
-  if (dtype == CDE_F32)
-    cde::hermite_bdiff_backward_kernel<float><<<grid, 256, 0, s>>>((const float*)grad_coeffs, (const float*)t, (float*)grad_x, B, L, C);
-  else if (dtype == CDE_F64)
-    cde::hermite_bdiff_backward_kernel<double><<<grid, 256, 0, s>>>((const double*)grad_coeffs, (const double*)t, (double*)grad_x, B, L, C);
-  else return CDE_ERR_DTYPE;
-  return cde::check_launch();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hermite_bdiff_backward_kernel<T><<<blocks_for(B * L * C), 256, 0, (hipStream_t)stream>>>(
+        (const T*)grad_coeffs, (const T*)t, (T*)grad_x, B, L, C);
+    return check_launch();
+  });
 }
 
 // dL/dh (B, L-1, C) of the fit, h_j = t_{j+1} - t_j (data without missing values): sum over B and C, then
 // dL/dt_{j+1} += dL/dh_j and dL/dt_j -= dL/dh_j give the gradient w.r.t. the knot times.
 extern "C" int cde_hermite_bdiff_coeffs_backward_dt(const void* grad_coeffs, const void* x, const void* t, void* grad_h,
                                                     int64_t B, int64_t L, int64_t C, int dtype, void* stream) {
-  if (B < 0 || L < 2 || C < 1) return CDE_ERR_SHAPE;
+  if (!Series{B, L, C}.ok()) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!grad_coeffs || !x || !t || !grad_h) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * (L - 1) * C + 255) / 256);
-  if (dtype == CDE_F32)
-    cde::hermite_bdiff_backward_dt_kernel<float><<<grid, 256, 0, s>>>((const float*)grad_coeffs, (const float*)x,
-                                                                      (const float*)t, (float*)grad_h, B, L, C);
-  else if (dtype == CDE_F64)
-    cde::hermite_bdiff_backward_dt_kernel<double><<<grid, 256, 0, s>>>((const double*)grad_coeffs, (const double*)x,
-                                                                       (const double*)t, (double*)grad_h, B, L, C);
-  else return CDE_ERR_DTYPE;
-  return cde::check_launch();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hermite_bdiff_backward_dt_kernel<T><<<blocks_for(B * (L - 1) * C), 256, 0, (hipStream_t)stream>>>(
+        (const T*)grad_coeffs, (const T*)x, (const T*)t, (T*)grad_h, B, L, C);
+    return check_launch();
+  });
 }
 
 extern "C" int cde_natural_cubic_coeffs(const void* x, const void* t, void* coeffs, int64_t B, int64_t L, int64_t C,
                                         int version, int has_missing, int dtype, void* stream) {
-  if (B < 0 || L < 2 || C < 1 || (version != 0 && version != 1)) return CDE_ERR_SHAPE;
+  if (!Series{B, L, C}.ok() || (version != 0 && version != 1)) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!x || !t || !coeffs) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-  if (dtype == CDE_F32)
-    cde::natural_cubic_kernel<float><<<grid, 256, 0, s>>>((const float*)x, (const float*)t, (float*)coeffs, B, L, C, version, has_missing);
-  else if (dtype == CDE_F64)
-    cde::natural_cubic_kernel<double><<<grid, 256, 0, s>>>((const double*)x, (const double*)t, (double*)coeffs, B, L, C, version, has_missing);
-  else return CDE_ERR_DTYPE;
-  return cde::check_launch();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    natural_cubic_kernel<T><<<blocks_for(B * C), 256, 0, (hipStream_t)stream>>>(
+        (const T*)x, (const T*)t, (T*)coeffs, B, L, C, version, has_missing);
+    return check_launch();
+  });
 }
 
 extern "C" size_t cde_natural_cubic_coeffs_backward_workspace_bytes(int64_t L, int dtype) {
   return (size_t)2 * (size_t)L * (dtype == CDE_F64 ? 8 : 4);
 }
 
-// grad_t_rows == NULL: gradient w.r.t. the values only.  Otherwise also `x` (the forward input), `kd_scratch` and
-// `grad_t_rows`, each (B, L, C): grad_t_rows receives one partial dL/dt row per scalar path (sum them over B and C).
+// grad_t_rows == NULL: gradient w.r.t. the values only (x and kd_scratch are then not looked at).  Otherwise also `x` (the
+// forward input), `kd_scratch` and `grad_t_rows`, each (B, L, C): grad_t_rows receives one partial dL/dt row per scalar
+// path (sum them over B and C).
 extern "C" int cde_natural_cubic_coeffs_backward(const void* grad_coeffs, const void* t, void* grad_x, void* workspace,
                                                  size_t workspace_bytes, int64_t B, int64_t L, int64_t C, int dtype,
                                                  const void* x, void* kd_scratch, void* grad_t_rows, void* stream) {
-  if (B < 0 || L < 2 || C < 1) return CDE_ERR_SHAPE;
+  if (!Series{B, L, C}.ok()) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!grad_coeffs || !t || !grad_x || !workspace) return CDE_ERR_NULL;
   if (grad_t_rows && (!x || !kd_scratch)) return CDE_ERR_NULL;
-  if (dtype != CDE_F32 && dtype != CDE_F64) return CDE_ERR_DTYPE;
-  if (workspace_bytes < cde_natural_cubic_coeffs_backward_workspace_bytes(L, dtype)) return CDE_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-#define CDE_NCB(T)                                                                                                  \
-  do {                                                                                                              \
-    cde::natural_cubic_aux_kernel<T><<<1, 64, 0, s>>>((const T*)t, (T*)workspace, L);                               \
-    if (grad_t_rows)                                                                                                \
-      cde::natural_cubic_backward_kernel<T, true><<<grid, 256, 0, s>>>((const T*)grad_coeffs, (const T*)t,          \
-          (const T*)workspace, (T*)grad_x, B, L, C, (const T*)x, (T*)kd_scratch, (T*)grad_t_rows);                  \
-    else                                                                                                            \
-      cde::natural_cubic_backward_kernel<T, false><<<grid, 256, 0, s>>>((const T*)grad_coeffs, (const T*)t,         \
-          (const T*)workspace, (T*)grad_x, B, L, C, nullptr, nullptr, nullptr);                                     \
-  } while (0)
-  if (dtype == CDE_F32) CDE_NCB(float); else CDE_NCB(double);
-#undef CDE_NCB
-  return cde::check_launch();
+  return dispatch_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    if (workspace_bytes < cde_natural_cubic_coeffs_backward_workspace_bytes(L, dtype)) return CDE_ERR_WORKSPACE;
+    natural_cubic_aux_kernel<T><<<1, 64, 0, s>>>((const T*)t, (T*)workspace, L);
+    return dispatch_flag(grad_t_rows != nullptr, [&](auto with_t) {
+      natural_cubic_backward_kernel<T, with_t()><<<blocks_for(B * C), 256, 0, s>>>(
+          (const T*)grad_coeffs, (const T*)t, (const T*)workspace, (T*)grad_x, B, L, C, (const T*)(with_t() ? x : nullptr),
+          (T*)(with_t() ? kd_scratch : nullptr), (T*)grad_t_rows);
+      return check_launch();
+    });
+  });
 }
-
 
 // Batches with missing entries (values only): `x` is the forward input, `workspace` has the shape of the coefficients.
 extern "C" int cde_natural_cubic_coeffs_backward_missing(const void* grad_coeffs, const void* x, const void* t,
                                                          void* grad_x, void* workspace, int64_t B, int64_t L, int64_t C,
                                                          int version, int dtype, void* stream) {
-  if (B < 0 || L < 2 || C < 1 || (version != 0 && version != 1)) return CDE_ERR_SHAPE;
+  if (!Series{B, L, C}.ok() || (version != 0 && version != 1)) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!grad_coeffs || !x || !t || !grad_x || !workspace) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-  if (dtype == CDE_F32)
-    cde::natural_cubic_backward_missing_kernel<float><<<grid, 256, 0, s>>>((const float*)grad_coeffs, (const float*)x,
-        (const float*)t, (float*)grad_x, (float*)workspace, B, L, C, version);
-  else if (dtype == CDE_F64)
-    cde::natural_cubic_backward_missing_kernel<double><<<grid, 256, 0, s>>>((const double*)grad_coeffs, (const double*)x,
-        (const double*)t, (double*)grad_x, (double*)workspace, B, L, C, version);
-  else return CDE_ERR_DTYPE;
-  return cde::check_launch();
-}
-
-
-extern "C" int cde_logsig_windows(const void* x, const int64_t* rows, const void* scale, const int32_t* words, void* out,
-                                  int64_t B, int64_t L, int64_t C, int depth, int64_t n_windows, int n_words, int dtype,
-                                  void* stream) {
-  if (B < 0 || L < 1 || C < 1 || n_windows < 0 || n_words < 1) return CDE_ERR_SHAPE;
-  // envelopes of the per-lane signature arrays: (8 channels, depth 3), (5, 4), (32, 2)
-  const int env = (depth >= 1 && depth <= 3 && C <= 8) ? 0 : (depth == 4 && C <= 5) ? 1 : (depth >= 1 && depth <= 2 && C <= 32) ? 2 : -1;
-  if (env < 0) return CDE_ERR_UNSUPPORTED;
-  if (B == 0) return CDE_OK;
-  if (!x || !rows || !scale || !words || !out) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * n_windows + 63) / 64), grid2 = (unsigned)((B * n_words + 255) / 256);
-#define CDE_LS(T, MAXC, MAXD)                                                                                          \
-  cde::logsig_windows_kernel<T, MAXC, MAXD><<<grid, 64, 0, s>>>((const T*)x, rows, (const T*)scale, words, (T*)out, B, L, \
-                                                                (int)C, depth, n_windows, n_words)
-  if (dtype == CDE_F32) {
-    if (n_windows > 0) { if (env == 0) CDE_LS(float, 8, 3); else if (env == 1) CDE_LS(float, 5, 4); else CDE_LS(float, 32, 2); }
-    cde::logsig_accumulate_kernel<float><<<grid2, 256, 0, s>>>((const float*)x, (float*)out, B, L, (int)C, n_windows, n_words);
-  } else if (dtype == CDE_F64) {
-    if (n_windows > 0) { if (env == 0) CDE_LS(double, 8, 3); else if (env == 1) CDE_LS(double, 5, 4); else CDE_LS(double, 32, 2); }
-    cde::logsig_accumulate_kernel<double><<<grid2, 256, 0, s>>>((const double*)x, (double*)out, B, L, (int)C, n_windows, n_words);
-  } else return CDE_ERR_DTYPE;
-#undef CDE_LS
-  return cde::check_launch();
-}
-
-// grad_out (B, n_windows + 1, n_words) -> grad_x (B, L, C) w.r.t. the filled series the forward call was given;
-// `workspace` has the size of grad_out.
-extern "C" int cde_logsig_windows_backward(const void* grad_out, const void* x, const int64_t* rows, const void* scale,
-                                           const int32_t* words, void* grad_x, void* workspace, int64_t B, int64_t L,
-                                           int64_t C, int depth, int64_t n_windows, int n_words, int dtype, void* stream) {
-  if (B < 0 || L < 1 || C < 1 || n_windows < 0 || n_words < 1) return CDE_ERR_SHAPE;
-  const int env = (depth >= 1 && depth <= 3 && C <= 8) ? 0 : (depth == 4 && C <= 5) ? 1 : (depth >= 1 && depth <= 2 && C <= 32) ? 2 : -1;
-  if (env < 0) return CDE_ERR_UNSUPPORTED;
-  if (B == 0) return CDE_OK;
-  if (!grad_out || !x || !rows || !scale || !words || !grad_x || !workspace) return CDE_ERR_NULL;
-  if (dtype != CDE_F32 && dtype != CDE_F64) return CDE_ERR_DTYPE;
-  hipStream_t s = (hipStream_t)stream;
-  cde::zero_async(grad_x, (size_t)(B * L * C) * (dtype == CDE_F64 ? 8 : 4), s);
-  const unsigned grid = (unsigned)((B * n_windows + 63) / 64), grid2 = (unsigned)((B * n_words + 255) / 256);
-#define CDE_LSB(T, MAXC, MAXD)                                                                                         \
-  do {                                                                                                                 \
-    cde::logsig_windows_backward_kernel<T, MAXC, MAXD><<<grid, 64, 0, s>>>((T*)workspace, (const T*)x, rows,           \
-        (const T*)scale, words, (T*)grad_x, B, L, (int)C, depth, n_windows, n_words);                                  \
-    cde::logsig_boundary_kernel<T><<<(unsigned)((B * C + 255) / 256), 256, 0, s>>>((const T*)workspace, rows,          \
-        (T*)grad_x, B, L, (int)C, n_windows, n_words);                                                                 \
-  } while (0)
-  if (dtype == CDE_F32) {
-    cde::logsig_suffix_kernel<float><<<grid2, 256, 0, s>>>((const float*)grad_out, (float*)workspace, (float*)grad_x, B, L, (int)C, n_windows, n_words);
-    if (n_windows > 0) { if (env == 0) CDE_LSB(float, 8, 3); else if (env == 1) CDE_LSB(float, 5, 4); else CDE_LSB(float, 32, 2); }
-  } else {
-    cde::logsig_suffix_kernel<double><<<grid2, 256, 0, s>>>((const double*)grad_out, (double*)workspace, (double*)grad_x, B, L, (int)C, n_windows, n_words);
-    if (n_windows > 0) { if (env == 0) CDE_LSB(double, 8, 3); else if (env == 1) CDE_LSB(double, 5, 4); else CDE_LSB(double, 32, 2); }
-  }
-#undef CDE_LSB
-  return cde::check_launch();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    natural_cubic_backward_missing_kernel<T><<<blocks_for(B * C), 256, 0, (hipStream_t)stream>>>(
+        (const T*)grad_coeffs, (const T*)x, (const T*)t, (T*)grad_x, (T*)workspace, B, L, C, version);
+    return check_launch();
+  });
 }
 
 extern "C" int cde_forward_fill(const void* x, void* out, int64_t B, int64_t L, int64_t C, int dtype, void* stream) {
-  if (B < 0 || L < 1 || C < 1) return CDE_ERR_SHAPE;
+  if (!Series{B, L, C}.ok(1)) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!x || !out) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-  if (dtype == CDE_F32) cde::forward_fill_kernel<float><<<grid, 256, 0, s>>>((const float*)x, (float*)out, B, L, C);
-  else if (dtype == CDE_F64) cde::forward_fill_kernel<double><<<grid, 256, 0, s>>>((const double*)x, (double*)out, B, L, C);
-  else return CDE_ERR_DTYPE;
-  return cde::check_launch();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    forward_fill_kernel<T><<<blocks_for(B * C), 256, 0, (hipStream_t)stream>>>((const T*)x, (T*)out, B, L, C);
+    return check_launch();
+  });
 }
 
 extern "C" int cde_rectilinear_prepare(const void* x, void* out, int64_t B, int64_t L, int64_t C, int64_t time_index,
                                        int dtype, void* stream) {
-  if (B < 0 || L < 1 || C < 1 || time_index < 0 || time_index >= C) return CDE_ERR_SHAPE;
+  if (!Series{B, L, C}.ok(1) || time_index < 0 || time_index >= C) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!x || !out) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-  if (dtype == CDE_F32)
-    cde::rectilinear_prepare_kernel<float><<<grid, 256, 0, s>>>((const float*)x, (float*)out, B, L, C, time_index);
-  else if (dtype == CDE_F64)
-    cde::rectilinear_prepare_kernel<double><<<grid, 256, 0, s>>>((const double*)x, (double*)out, B, L, C, time_index);
-  else return CDE_ERR_DTYPE;
-  return cde::check_launch();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    rectilinear_prepare_kernel<T><<<blocks_for(B * C), 256, 0, (hipStream_t)stream>>>(
+        (const T*)x, (T*)out, B, L, C, time_index);
+    return check_launch();
+  });
+}
+
+// the two fills' backward: it continues its caller's checks (the sizes are done there; the empty batch, the pointers and
+// the dtype follow here, in the order of every entry point).  RECT with the time channel's index, the plain fill with -1
+template <bool RECT>
+static int fill_backward(const void* grad_out, const void* x, void* grad_x, const Series& n, int64_t time_index, int dtype,
+                         void* stream) {
+  if (n.B == 0) return CDE_OK;
+  if (!grad_out || !x || !grad_x) return CDE_ERR_NULL;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    forward_fill_backward_kernel<T, RECT><<<blocks_for(n.B * n.C), 256, 0, (hipStream_t)stream>>>(
+        (const T*)grad_out, (const T*)x, (T*)grad_x, n.B, n.L, n.C, time_index);
+    return check_launch();
+  });
 }
 
 extern "C" int cde_forward_fill_backward(const void* grad_out, const void* x, void* grad_x, int64_t B, int64_t L, int64_t C,
                                          int dtype, void* stream) {
-  if (B < 0 || L < 1 || C < 1) return CDE_ERR_SHAPE;
-  if (B == 0) return CDE_OK;
-  if (!grad_out || !x || !grad_x) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-  if (dtype == CDE_F32)
-    cde::forward_fill_backward_kernel<float, false><<<grid, 256, 0, s>>>((const float*)grad_out, (const float*)x, (float*)grad_x, B, L, C, -1);
-  else if (dtype == CDE_F64)
-    cde::forward_fill_backward_kernel<double, false><<<grid, 256, 0, s>>>((const double*)grad_out, (const double*)x, (double*)grad_x, B, L, C, -1);
-  else return CDE_ERR_DTYPE;
-  return cde::check_launch();
+  const Series n{B, L, C};
+  if (!n.ok(1)) return CDE_ERR_SHAPE;
+  return fill_backward<false>(grad_out, x, grad_x, n, -1, dtype, stream);
 }
 
 extern "C" int cde_rectilinear_prepare_backward(const void* grad_out, const void* x, void* grad_x, int64_t B, int64_t L,
                                                 int64_t C, int64_t time_index, int dtype, void* stream) {
-  if (B < 0 || L < 1 || C < 1 || time_index < 0 || time_index >= C) return CDE_ERR_SHAPE;
-  if (B == 0) return CDE_OK;
-  if (!grad_out || !x || !grad_x) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((B * C + 255) / 256);
-  if (dtype == CDE_F32)
-    cde::forward_fill_backward_kernel<float, true><<<grid, 256, 0, s>>>((const float*)grad_out, (const float*)x, (float*)grad_x, B, L, C, time_index);
-  else if (dtype == CDE_F64)
-    cde::forward_fill_backward_kernel<double, true><<<grid, 256, 0, s>>>((const double*)grad_out, (const double*)x, (double*)grad_x, B, L, C, time_index);
-  else return CDE_ERR_DTYPE;
-  return cde::check_launch();
+  const Series n{B, L, C};
+  if (!n.ok(1) || time_index < 0 || time_index >= C) return CDE_ERR_SHAPE;
+  return fill_backward<true>(grad_out, x, grad_x, n, time_index, dtype, stream);
 }
 
 extern "C" int cde_interpret_t(const void* knots, int64_t n_intervals, const void* tq, int64_t nq, int64_t* index_out,
@@ -1459,15 +1026,20 @@ extern "C" int cde_interpret_t(const void* knots, int64_t n_intervals, const voi
   if (n_intervals < 1 || nq < 0) return CDE_ERR_SHAPE;
   if (nq == 0) return CDE_OK;
   if (!knots || !tq || !index_out || !frac_out) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((nq + 255) / 256);
-  if (dtype == CDE_F32)
-    cde::interpret_t_kernel<float><<<grid, 256, 0, s>>>((const float*)knots, n_intervals, (const float*)tq, nq, index_out, (float*)frac_out);
-  else if (dtype == CDE_F64)
-    cde::interpret_t_kernel<double><<<grid, 256, 0, s>>>((const double*)knots, n_intervals, (const double*)tq, nq, index_out, (double*)frac_out);
-  else
-    return CDE_ERR_DTYPE;
-  return cde::check_launch();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    interpret_t_kernel<T><<<blocks_for(nq), 256, 0, (hipStream_t)stream>>>(
+        (const T*)knots, n_intervals, (const T*)tq, nq, index_out, (T*)frac_out);
+    return check_launch();
+  });
+}
+
+// path evaluation: an unknown `degree` or `what` is noticed where the kernel is chosen, after the pointers and the dtype
+template <typename F>
+static int dispatch_path_eval(int dtype, int degree, int what, F&& f) {
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return dispatch_degree(degree, [&](auto D) { return dispatch_what(what, [&](auto W) { return f(tag, D, W); }); });
+  });
 }
 
 extern "C" int cde_path_eval(const void* coeffs, const void* knots, const void* tq, int64_t nq, void* out, int64_t B,
@@ -1475,10 +1047,12 @@ extern "C" int cde_path_eval(const void* coeffs, const void* knots, const void* 
   if (B < 0 || n_intervals < 1 || C < 1 || nq < 0) return CDE_ERR_SHAPE;
   if (B == 0 || nq == 0) return CDE_OK;
   if (!coeffs || !knots || !tq || !out) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == CDE_F32) return cde::launch_path_eval<float>(coeffs, knots, tq, nq, out, B, n_intervals, C, degree, what, s);
-  if (dtype == CDE_F64) return cde::launch_path_eval<double>(coeffs, knots, tq, nq, out, B, n_intervals, C, degree, what, s);
-  return CDE_ERR_DTYPE;
+  return dispatch_path_eval(dtype, degree, what, [&](auto tag, auto D, auto W) {
+    using T = typename decltype(tag)::type;
+    path_eval_kernel<T, D(), W()><<<grid_stride_blocks(B * nq * C), 256, 0, (hipStream_t)stream>>>(
+        (const T*)coeffs, (const T*)knots, (const T*)tq, nq, (T*)out, B, n_intervals, C);
+    return check_launch();
+  });
 }
 
 extern "C" int cde_path_eval_backward(const void* grad_out, const void* knots, const void* tq, int64_t nq,
@@ -1487,10 +1061,12 @@ extern "C" int cde_path_eval_backward(const void* grad_out, const void* knots, c
   if (B < 0 || n_intervals < 1 || C < 1 || nq < 0) return CDE_ERR_SHAPE;
   if (B == 0 || nq == 0) return CDE_OK;
   if (!grad_out || !knots || !tq || !grad_coeffs) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == CDE_F32) return cde::launch_path_eval_backward<float>(grad_out, knots, tq, nq, grad_coeffs, B, n_intervals, C, degree, what, s);
-  if (dtype == CDE_F64) return cde::launch_path_eval_backward<double>(grad_out, knots, tq, nq, grad_coeffs, B, n_intervals, C, degree, what, s);
-  return CDE_ERR_DTYPE;
+  return dispatch_path_eval(dtype, degree, what, [&](auto tag, auto D, auto W) {
+    using T = typename decltype(tag)::type;
+    path_eval_backward_kernel<T, D(), W()><<<blocks_for(B * C), 256, 0, (hipStream_t)stream>>>(
+        (const T*)grad_out, (const T*)knots, (const T*)tq, nq, (T*)grad_coeffs, B, n_intervals, C);
+    return check_launch();
+  });
 }
 
 extern "C" int cde_contract(const void* F, const void* dX, void* out, int64_t B, int64_t H, int64_t C, int dtype,
@@ -1498,56 +1074,10 @@ extern "C" int cde_contract(const void* F, const void* dX, void* out, int64_t B,
   if (B < 0 || H < 1 || C < 1) return CDE_ERR_SHAPE;
   if (B == 0) return CDE_OK;
   if (!F || !dX || !out) return CDE_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  int64_t g = (B * H + 255) / 256;
-  const unsigned grid = (unsigned)(g > 65536 ? 65536 : g);
-  if (dtype == CDE_F32)
-    cde::contract_kernel<float><<<grid, 256, 0, s>>>((const float*)F, (const float*)dX, (float*)out, B, H, C);
-  else if (dtype == CDE_F64)
-    cde::contract_kernel<double><<<grid, 256, 0, s>>>((const double*)F, (const double*)dX, (double*)out, B, H, C);
-  else
-    return CDE_ERR_DTYPE;
-  return cde::check_launch();
-}
-
-extern "C" int cde_abi_version(void) { return CDE_ABI_VERSION; }
-
-// ---------------------------------------------------------------------------------------------- tuning table
-#include <atomic>
-namespace cde {
-static constexpr int64_t OPTION_DEFAULTS[CDE_OPT_COUNT] = {
-    /* K3_FORM */ 0, /* K3_WAVES */ 0, /* K3D_WAVES */ 0, /* K2M_NO_SPLIT */ 0, /* K3M_NO_SPLIT */ 0, /* K3M_SPLIT4 */ 0,
-    /* K3M_S8_TILES */ -1, /* K4_NO_SPLIT */ 0, /* K4M_NO_SPLIT */ 0, /* K4M_SPLIT_TILES */ -1, /* K4AM_WAVES */ 0,
-    /* K4AM_S8_TILES */ -1, /* K4AM_SPLIT4 */ 0, /* K4AM_NO_SPLIT */ 0, /* K4AM_NO_SMALL_REDUCE */ 0, /* K4AM_SPS */ 0,
-    /* K4AM_NO_FSAL */ 0, /* WIDE_SCRATCH_BYTES */ 0};
-static std::atomic<int64_t> g_options[CDE_OPT_COUNT] = {
-    {0}, {0}, {0}, {0}, {0}, {0}, {-1}, {0}, {0}, {-1}, {0}, {-1}, {0}, {0}, {0}, {0}, {0}, {0}};
-int64_t option(int key) { return g_options[key].load(std::memory_order_relaxed); }
-}  // namespace cde
-
-extern "C" int cde_set_option(int key, int64_t value) {
-  if (key < 0 || key >= CDE_OPT_COUNT) return CDE_ERR_SHAPE;
-  cde::g_options[key].store(value, std::memory_order_relaxed);
-  return CDE_OK;
-}
-extern "C" int64_t cde_get_option(int key) {
-  if (key < 0 || key >= CDE_OPT_COUNT) return INT64_MIN;
-  return cde::option(key);
-}
-extern "C" int cde_reset_options(void) {
-  for (int k = 0; k < CDE_OPT_COUNT; ++k) cde::g_options[k].store(cde::OPTION_DEFAULTS[k], std::memory_order_relaxed);
-  return CDE_OK;
-}
-
-extern "C" const char* cde_error_string(int code) {
-  switch (code) {
-    case CDE_OK: return "ok";
-    case CDE_ERR_NULL: return "a required pointer argument is NULL";
-    case CDE_ERR_DTYPE: return "unknown dtype enum (expected CDE_F32 or CDE_F64)";
-    case CDE_ERR_SHAPE: return "a size argument is out of range";
-    case CDE_ERR_UNSUPPORTED: return "this (dtype, shape, activation, variant) combination is not implemented";
-    case CDE_ERR_WORKSPACE: return "workspace smaller than cde_rk4_adjoint_workspace_bytes()";
-    case CDE_ERR_LAUNCH: return "HIP kernel launch failed";
-    default: return "unknown error code";
-  }
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    contract_kernel<T><<<grid_stride_blocks(B * H), 256, 0, (hipStream_t)stream>>>(
+        (const T*)F, (const T*)dX, (T*)out, B, H, C);
+    return check_launch();
+  });
 }
