@@ -3,7 +3,8 @@ the project's own flags, and in each kernel whose name contains the filter the i
 counted -- for the fixed-grid solvers that is one RK step.
     python scripts/loop_counts.py torchcde_amd/csrc/rk4_bf16x3.hip 'rk4_forward_bf16x3<' [flags in place of the file's own]
 A loop is the span from a label to the last branch back to it, so the count is static: both sides of a branch inside the
-loop are counted once each."""
+loop are counted once each.  Beside the instruction classes the table counts the MFMAs whose SrcA is read from AGPRs
+(`a[...]` as second operand) and the LDS reads and waits of the loop."""
 import os
 import re
 import subprocess
@@ -72,7 +73,11 @@ def classes(body):
             "v_mov_b32": op.count("v_mov_b32"), "copies": sum(op.count(c) for c in COPIES),
             "v_pk_fma_f32": op.count("v_pk_fma_f32"), "v_readlane_b32": op.count("v_readlane_b32"),
             "branches": sum(o.startswith("s_cbranch") or o == "s_branch" for o in op),
-            "scratch": sum(o.startswith("scratch_") for o in op)}
+            "scratch": sum(o.startswith("scratch_") for o in op),
+            "ds_read_b128": op.count("ds_read_b128"), "lds_reads": sum(o.startswith("ds_read") for o in op),
+            "s_waitcnt": op.count("s_waitcnt"),
+            # MFMAs whose SrcA (the second operand) is read straight from accumulator registers
+            "mfma_srca_agpr": sum(bool(re.match(r"v_mfma\S*\s+[^,]+,\s*a\[", ln)) for ln in body)}
 
 
 def loop_table(src, name_filter="", extra_flags=None):
@@ -81,8 +86,8 @@ def loop_table(src, name_filter="", extra_flags=None):
 
 if __name__ == "__main__":
     table = loop_table(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "", sys.argv[3:] or None)
-    cols = ["instructions", "mfma", "valu", "copies", "v_accvgpr_read_b32", "v_accvgpr_write_b32", "v_mov_b32", "v_pk_fma_f32",
-            "v_readlane_b32", "branches", "scratch"]
+    cols = ["instructions", "mfma", "mfma_srca_agpr", "valu", "copies", "v_accvgpr_read_b32", "v_accvgpr_write_b32", "v_mov_b32",
+            "v_pk_fma_f32", "v_readlane_b32", "ds_read_b128", "s_waitcnt", "branches", "scratch"]
     print(" ".join("%-12s" % c[-12:] for c in cols) + " kernel")
     for n, row in table.items():
         print(" ".join("%-12d" % row[c] for c in cols) + " " + n.replace("cde::", ""))

@@ -1,5 +1,8 @@
 // cde_bf16x3.h -- what K2b (rk4_bf16x3.hip) and K3b (rk4_bf16x3_adjoint.hip) share: the exact three-piece bf16 operand
-// split, the weight images in LDS, and the field / vjp evaluations on the bf16 matrix pipe.
+// split, the weight images in LDS, and the field / vjp evaluations on the bf16 matrix pipe.  The field evaluation has two
+// forms that compute the same values through the same MFMAs: bx_field reads the weight pieces from the LDS image in every
+// stage (K3b: its accumulators live in AGPRs, so it has no registers to spare and is built without -amdgpu-mfma-vgpr-form);
+// bx_load_resident + bx_field_resident keep them in AGPRs for the whole solve (K2b: one wave per SIMD, AGPRs otherwise empty).
 //
 // Idea ("bf16x3").  gfx950 has no xf32 / TF32 mode; its exact-f32 MFMA runs at the vector rate, 1/16 of the bf16 rate
 // (MI355X_MICROARCH.md).  A float32 value splits exactly into three bf16 pieces x = x1 + x2 + x3 (8 + 8 + 8 mantissa
@@ -33,7 +36,8 @@ namespace cde {
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
-constexpr int BX_IMG_U4 = 8 * 2 * 3 * 64;                 // uint4 entries of one piece image: [tile 8][ks 2][piece 3][lane 64]
+constexpr int BX_IMG_PER_LANE = 8 * 2 * 3;                // one lane's uint4 entries of a piece image
+constexpr int BX_IMG_U4 = BX_IMG_PER_LANE * 64;           // uint4 entries of one piece image: [tile 8][ks 2][piece 3][lane 64]
 constexpr int BX_BIAS_FLOATS = 8 * 2 * 16;                // [tile][half][register]
 constexpr int BX_FWD_LDS_BYTES = BX_IMG_U4 * 16 + BX_BIAS_FLOATS * 4;
 constexpr int BX_ADJ_LDS_BYTES = 2 * BX_IMG_U4 * 16 + BX_BIAS_FLOATS * 4 + 4 * SCR_FLOATS * 4;
@@ -97,12 +101,13 @@ __device__ __forceinline__ void bx_stage_bias(const float* __restrict__ bias, fl
 }
 
 // six piece products of one 32 x 32 x 16 block for TWO independent accumulators (two tiles), interleaved so that no MFMA
-// waits on its own accumulator; smallest terms first: a3 b1, a2 b2, a1 b3, a2 b1, a1 b2, a1 b1
-__device__ __forceinline__ void bx_block2(const u32x4* a, const u32x4* a_other, const bf16x8 (&b)[3], f32x16& acc,
-                                          f32x16& acc_other) {
-  const bf16x8 a1 = __builtin_bit_cast(bf16x8, a[0]), a2 = __builtin_bit_cast(bf16x8, a[64]), a3 = __builtin_bit_cast(bf16x8, a[128]);
-  const bf16x8 o1 = __builtin_bit_cast(bf16x8, a_other[0]), o2 = __builtin_bit_cast(bf16x8, a_other[64]),
-               o3 = __builtin_bit_cast(bf16x8, a_other[128]);
+// waits on its own accumulator; smallest terms first: a3 b1, a2 b2, a1 b3, a2 b1, a1 b2, a1 b1.  w / w_other: the A operand's
+// three pieces (largest first), wherever they live
+__device__ __forceinline__ void bx_block2_pieces(const u32x4* w, const u32x4* w_other, const bf16x8 (&b)[3], f32x16& acc,
+                                                 f32x16& acc_other) {
+  const bf16x8 a1 = __builtin_bit_cast(bf16x8, w[0]), a2 = __builtin_bit_cast(bf16x8, w[1]), a3 = __builtin_bit_cast(bf16x8, w[2]);
+  const bf16x8 o1 = __builtin_bit_cast(bf16x8, w_other[0]), o2 = __builtin_bit_cast(bf16x8, w_other[1]),
+               o3 = __builtin_bit_cast(bf16x8, w_other[2]);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b[0], acc, 0, 0, 0);
   acc_other = __builtin_amdgcn_mfma_f32_32x32x16_bf16(o3, b[0], acc_other, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b[1], acc, 0, 0, 0);
@@ -115,6 +120,13 @@ __device__ __forceinline__ void bx_block2(const u32x4* a, const u32x4* a_other, 
   acc_other = __builtin_amdgcn_mfma_f32_32x32x16_bf16(o1, b[1], acc_other, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b[0], acc, 0, 0, 0);
   acc_other = __builtin_amdgcn_mfma_f32_32x32x16_bf16(o1, b[0], acc_other, 0, 0, 0);
+}
+
+// the same with the pieces read from an LDS image (a, a_other: the lane's entry of piece 0; pieces are 64 entries apart)
+__device__ __forceinline__ void bx_block2(const u32x4* a, const u32x4* a_other, const bf16x8 (&b)[3], f32x16& acc,
+                                          f32x16& acc_other) {
+  const u32x4 w[3] = {a[0], a[64], a[128]}, w_other[3] = {a_other[0], a_other[64], a_other[128]};
+  bx_block2_pieces(w, w_other, b, acc, acc_other);
 }
 
 // f (register r <-> unit 2 r + half) of the affine field at state z
@@ -143,6 +155,56 @@ __device__ __forceinline__ f32x16 bx_field(const u32x4* imgY, const float* btab,
     const u32x4* a1 = imgY + (((2 * tp + 1) * 2) * 3) * 64 + lane;
     bx_block2(a0, a1, zp0, acc[0], acc[1]);
     bx_block2(a0 + 3 * 64, a1 + 3 * 64, zp1, acc[0], acc[1]);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      float s0 = acc[u][0] * dX[0], s1 = acc[u][1] * dX[0];
+#pragma unroll
+      for (int c = 1; c < MC; ++c) { s0 = __builtin_fmaf(acc[u][2 * c], dX[c], s0); s1 = __builtin_fmaf(acc[u][2 * c + 1], dX[c], s1); }
+      f[2 * (2 * tp + u)] = s0; f[2 * (2 * tp + u) + 1] = s1;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return f;
+}
+
+// K2b's form of bx_field: the weight pieces stay in the wave's registers for the whole solve.  K2b runs one wave per SIMD, so
+// beside its 256 VGPRs the wave owns 256 accumulator registers that -amdgpu-mfma-vgpr-form leaves empty; an MFMA reads SrcA
+// straight from them.  bx_load_resident reads the lane's 48 entries of the staged image once and pins each to an AGPR (the
+// empty asm only fixes the register class: the MFMAs stay builtins and their hazards the compiler's business).
+__device__ __forceinline__ void bx_load_resident(const u32x4* imgY, int lane, u32x4 (&w)[BX_IMG_PER_LANE]) {
+#pragma unroll
+  for (int i = 0; i < BX_IMG_PER_LANE; ++i) {
+    w[i] = imgY[i * 64 + lane];
+    asm volatile("" : "+a"(w[i]));
+  }
+}
+
+// bx_field with the image in registers (w[(2 t + ks) * 3 + piece]): the same bias, MFMAs and fmaf chains in the same order.
+// Only the 1 KB bias table is read from LDS in the time loop.
+__device__ __forceinline__ f32x16 bx_field_resident(const u32x4 (&w)[BX_IMG_PER_LANE], const float* btab, int half, const f32x16& z,
+                                                    const float (&dX)[MC]) {
+  // the bias table is loop invariant too: without this the compiler hoists its 32 LDS reads (128 registers) out of the time loop
+  int opaque = 0;
+  asm volatile("" : "+v"(opaque));
+  bf16x8 zp0[3], zp1[3];
+  bx_split8(z, 0, zp0);
+  bx_split8(z, 8, zp1);
+  f32x16 f;
+  const float4* b4 = reinterpret_cast<const float4*>(btab) + half * 4 + opaque;
+#pragma unroll
+  for (int tp = 0; tp < 4; ++tp) {                                // two tiles at a time: 32 accumulator registers live
+    f32x16 acc[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const float4 bb = b4[(2 * tp + u) * 8 + q4];
+        acc[u][4 * q4] = bb.x; acc[u][4 * q4 + 1] = bb.y; acc[u][4 * q4 + 2] = bb.z; acc[u][4 * q4 + 3] = bb.w;
+      }
+    const u32x4* a0 = w + (2 * tp) * 2 * 3;                       // tile 2 tp, K step 0; K step 1 is 3 entries further on
+    const u32x4* a1 = w + (2 * tp + 1) * 2 * 3;
+    bx_block2_pieces(a0, a1, zp0, acc[0], acc[1]);
+    bx_block2_pieces(a0 + 3, a1 + 3, zp1, acc[0], acc[1]);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       float s0 = acc[u][0] * dX[0], s1 = acc[u][1] * dX[0];

@@ -2,6 +2,9 @@
 // on the BF16 matrix pipe at float32 accuracy (csrc/cde_bf16x3.h).  `variant = CDE_VARIANT_BF16X3` (cdeint(..., variant="bf16x3")),
 // and what AUTO takes at wave-per-tile batch sizes (api.hip).  The one-wave adjoint K3b is rk4_bf16x3_adjoint.hip: this file is
 // built with -amdgpu-mfma-vgpr-form (torchcde_amd/_lib.py), which keeps K2b's accumulators out of AGPRs and would cost K3b scratch.
+// The AGPRs hold the weights instead: the piece image is staged in LDS as in K3b, then every wave reads its lane's 48 entries
+// once (bx_load_resident) and the time loop evaluates the field with bx_field_resident -- the MFMAs take SrcA from a[...] and
+// the only LDS reads left in a stage are the 32 of the bias table.  K3b keeps the LDS form (bx_field): see cde_bf16x3.h.
 #include "cde_bf16x3.h"
 #include "cde_launch.h"
 
@@ -26,6 +29,8 @@ __global__ __launch_bounds__(256, 1) void rk4_forward_bf16x3(
   const int n = lane & 31, half = lane >> 5;
   const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
   if (tile * 32 >= B) return;
+  u32x4 wY[BX_IMG_PER_LANE];                                     // 192 AGPRs: the image is not read again
+  bx_load_resident(imgY, lane, wY);
   const int64_t series = tile * 32 + n;
   const bool valid = series < B;
   const int64_t sc = valid ? series : B - 1;
@@ -60,7 +65,7 @@ __global__ __launch_bounds__(256, 1) void rk4_forward_bf16x3(
       const int64_t nidx = more ? stage_index[e_next] : idx;
       const float nfrac = more ? stage_frac[e_next] : frac;
       if (nidx != idx) row = load_row<DEGREE>(coeffs, sc, n_intervals, nidx, Cr);
-      const f32x16 f = bx_field(imgY, btab, lane, half, z, dX);
+      const f32x16 f = bx_field_resident(wY, btab, half, z, dX);
       // torchdiffeq rk4_alt_step_func (3/8 rule), association order preserved
       const float third = (float)(1.0 / 3.0);
       if (stage == 0) { k1 = f; z = y + dt * k1 * third; }
