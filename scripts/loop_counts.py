@@ -1,10 +1,12 @@
 """Instruction classes of a kernel's hottest loop (no GPU needed): the translation unit is compiled to gfx950 assembly with
 the project's own flags, and in each kernel whose name contains the filter the innermost loop that holds the most MFMAs is
 counted -- for the fixed-grid solvers that is one RK step.
-    python scripts/loop_counts.py torchcde_amd/csrc/rk4_bf16x3.hip 'rk4_forward_bf16x3<' [flags in place of the file's own]
+    python scripts/loop_counts.py torchcde_amd/csrc/rk4_bf16x3.hip 'rk4_forward_bf16x3<' [--mfma N] [flags in place of the file's own]
 A loop is the span from a label to the last branch back to it, so the count is static: both sides of a branch inside the
-loop are counted once each.  Beside the instruction classes the table counts the MFMAs whose SrcA is read from AGPRs
-(`a[...]` as second operand) and the LDS reads and waits of the loop."""
+loop are counted once each.  `--mfma N` takes the loop with exactly N MFMAs instead of the one with the most (the helper
+wave's stage loop of rk4_adjoint_pair.hip has 96).  Beside the instruction classes the table counts the MFMAs whose SrcA is
+read from AGPRs (`a[...]` as second operand), the LDS reads and waits of the loop, and `lds_cover_min` / `lds_wait_cover_min`: how far
+ahead of the waits for them the LDS operands are requested (see lds_cover; `-` = the loop has no such wait)."""
 import os
 import re
 import subprocess
@@ -43,12 +45,13 @@ def kernels(text):
                 lines.append(m.group(1))
             elif ln.startswith("\t") and not ln.startswith("\t.") and not ln.startswith("\t;"):
                 lines.append(ln.strip())
+        name = name.replace("(anonymous namespace)::", "")      # its parenthesis is not the argument list's
         out[re.sub(r"\(.*", "", name).replace("void ", "")] = lines
     return out
 
 
-def hottest_loop(lines):
-    """the instructions of the shortest label-to-back-branch span among those with the most MFMAs"""
+def hottest_loop(lines, mfma=None):
+    """the instructions of the shortest label-to-back-branch span among those with the most MFMAs, or with exactly `mfma`"""
     at = {ln: i for i, ln in enumerate(lines) if ln.startswith(".LBB")}
     last_back = {}
     for i, ln in enumerate(lines):
@@ -58,10 +61,35 @@ def hottest_loop(lines):
     best = None
     for label, end in last_back.items():
         body = [ln for ln in lines[at[label]:end + 1] if not ln.startswith(".LBB")]
-        key = (-sum(ln.startswith("v_mfma") for ln in body), len(body))
+        count = sum(ln.startswith("v_mfma") for ln in body)
+        if mfma is not None and count != mfma:
+            continue
+        key = (-count, len(body))
         if best is None or key < best[0]:
             best = (key, body)
     return best[1] if best else []
+
+
+def lds_cover(body, gating_only=True, mfma_only=False):
+    """For every s_waitcnt with an lgkmcnt field whose next instruction other than s_nop is an MFMA (a wait that gates the
+    matrix pipe): the number of MFMA and VALU instructions between the wait and the nearest ds_read* before it -- the work
+    that covers the LDS round trip.  Waits with no ds_read before them in the loop body are left out.  gating_only=False
+    takes every wait with an lgkmcnt field, whatever follows it (a wait that gates the wave); mfma_only=True counts the
+    MFMAs alone."""
+    cover = []
+    for i, ln in enumerate(body):
+        if not (ln.startswith("s_waitcnt") and "lgkmcnt" in ln):
+            continue
+        nxt = next((b for b in body[i + 1:] if not b.startswith("s_nop")), "")
+        if gating_only and not nxt.startswith("v_mfma"):
+            continue
+        n = 0
+        for b in reversed(body[:i]):
+            if b.startswith("ds_read"):
+                cover.append(n)
+                break
+            n += b.startswith("v_mfma") if mfma_only else b.startswith("v_")
+    return cover
 
 
 def classes(body):
@@ -75,19 +103,27 @@ def classes(body):
             "branches": sum(o.startswith("s_cbranch") or o == "s_branch" for o in op),
             "scratch": sum(o.startswith("scratch_") for o in op),
             "ds_read_b128": op.count("ds_read_b128"), "lds_reads": sum(o.startswith("ds_read") for o in op),
-            "s_waitcnt": op.count("s_waitcnt"),
+            "s_waitcnt": op.count("s_waitcnt"), "lds_cover_min": min(lds_cover(body), default=None),
+            "lds_wait_cover_min": min(lds_cover(body, gating_only=False), default=None),
             # MFMAs whose SrcA (the second operand) is read straight from accumulator registers
             "mfma_srca_agpr": sum(bool(re.match(r"v_mfma\S*\s+[^,]+,\s*a\[", ln)) for ln in body)}
 
 
-def loop_table(src, name_filter="", extra_flags=None):
-    return {n: classes(hottest_loop(lines)) for n, lines in kernels(assembly(src, extra_flags)).items() if name_filter in n}
+def loop_bodies(src, name_filter="", extra_flags=None, mfma=None):
+    return {n: hottest_loop(lines, mfma) for n, lines in kernels(assembly(src, extra_flags)).items() if name_filter in n}
+
+
+def loop_table(src, name_filter="", extra_flags=None, mfma=None):
+    return {n: classes(body) for n, body in loop_bodies(src, name_filter, extra_flags, mfma).items()}
 
 
 if __name__ == "__main__":
-    table = loop_table(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "", sys.argv[3:] or None)
+    rest, mfma = sys.argv[3:], None
+    if rest[:1] == ["--mfma"]:
+        mfma, rest = int(rest[1]), rest[2:]
+    table = loop_table(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "", rest or None, mfma)
     cols = ["instructions", "mfma", "mfma_srca_agpr", "valu", "copies", "v_accvgpr_read_b32", "v_accvgpr_write_b32", "v_mov_b32",
-            "v_pk_fma_f32", "v_readlane_b32", "ds_read_b128", "s_waitcnt", "branches", "scratch"]
+            "v_pk_fma_f32", "v_readlane_b32", "ds_read_b128", "s_waitcnt", "lds_cover_min", "lds_wait_cover_min", "branches", "scratch"]
     print(" ".join("%-12s" % c[-12:] for c in cols) + " kernel")
     for n, row in table.items():
-        print(" ".join("%-12d" % row[c] for c in cols) + " " + n.replace("cde::", ""))
+        print(" ".join("%-12s" % ("-" if row[c] is None else row[c]) for c in cols) + " " + n.replace("cde::", ""))

@@ -23,7 +23,8 @@
 // buffer s & 1 comes after barrier s + 1.  The matrix pipe sees the chain wave's dependent row chains and the helper's
 // eight independent accumulator chains interleaved.
 // Measured (profiles/r05_k3_pair_b.log, 32768 series): 5.26 -> 5.01 ms.  Chain / helper priorities make no difference
-// (CDE_K3P_FLAGS), nor does requesting the helper's LDS operands a K step ahead: what is left is arithmetic -- on gfx950
+// (CDE_K3P_FLAGS), nor does, in the f32 form, requesting the helper's LDS operands a K step ahead (the bf16 form's helper
+// does gain from it: 0.05 ms per launch, profiles/NOTES.md round 11): what is left is arithmetic -- on gfx950
 // the f32 MFMA runs on the vector ALUs (157.3 TFLOP/s is the VECTOR peak), so the other wave's packed FMAs take matrix-pipe
 // time too; the second wave only removes the ISSUE gaps a single wave leaves (~5 cycles per instruction down to its ~4 of
 // ALU time): 260 MFMAs x 64 + ~950 vector instructions x ~4 = 20.4 k cycles per stage, measured ~21 k.
@@ -219,6 +220,16 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
     int par = 0, rs = 0, cs = 0;                                    // (z, a) buffer, ring slot and stage-in-step of stage st
     for (int64_t st = 0; st < n_stages; ++st) {
       kp_stage_barrier();                                           // barrier `st`: buffer `par` holds (z, a) of stage `st`
+      // (BX) the operands of the stage's first block, requested in front of publish / fetch: buffer `par` and ring slot `rs`
+      // are complete at barrier `st`, and publish writes another slot
+      float4 hz0, hz1, ha0, ha1, he0, he1;
+      if constexpr (BX) {
+        const float* base = tile_lds + par * KP_ZA_FLOATS;
+        const float4* zt4 = reinterpret_cast<const float4*>(base + (half * 32 + n) * 20);
+        const float4* at4 = reinterpret_cast<const float4*>(base + 64 * 20 + (half * 32 + n) * 20);
+        const float4* dw4 = reinterpret_cast<const float4*>(ring_dw + rs * 256 + half * 16);
+        hz0 = zt4[0]; hz1 = zt4[1]; ha0 = at4[0]; ha1 = at4[1]; he0 = dw4[0]; he1 = dw4[1];
+      }
       publish(rs >= 1 ? rs - 1 : 2);                                // stage st + 2 -> slot (st + 2) % 3
       fetch();                                                      // stage st + 3: requested, used next iteration
       const bool weighted = METHOD != CDE_METHOD_MIDPOINT || cs == 1;      // midpoint: the first evaluation carries no weight
@@ -228,13 +239,16 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
       // into three bf16 pieces and the six piece products with i + j <= 4 taken, smallest first.  MFMA K = 16 series:
       // this lane supplies K index 8 * half + j = series 2 (8 g + j) + half, row h = n (A: v of a_n), column k = n (B: z_n);
       // two K blocks g per tile.  dL/db as before: sum_series (w ds dX_c) a_n, the same fma order (bitwise the f32 form's).
+      // The operands of block (g, c + 1) -- after c = 7, of block (g + 1, 0) with the next K block's z / a rows -- are
+      // requested from LDS before the MFMAs of block (g, c) are issued, as the f32 form does for its K steps: the wave then
+      // starts a block's splits on operands that have had six MFMAs to arrive, not on a round trip it has just begun.
       const float* base = tile_lds + par * KP_ZA_FLOATS;
       const float4* zt4 = reinterpret_cast<const float4*>(base + (half * 32 + n) * 20);
       const float4* at4 = reinterpret_cast<const float4*>(base + 64 * 20 + (half * 32 + n) * 20);
       const float4* dw4 = reinterpret_cast<const float4*>(ring_dw + rs * 256 + half * 16);   // + c * 8 + g * 2: 8 series
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
-        const float4 z0 = zt4[2 * g], z1 = zt4[2 * g + 1], a0 = at4[2 * g], a1 = at4[2 * g + 1];
+        const float4 z0 = hz0, z1 = hz1, a0 = ha0, a1 = ha1;
         const float zv[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
         const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
         kp_u32x4 zw1, zw2, zw3;
@@ -248,7 +262,7 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
                         zp3 = __builtin_bit_cast(kp_bf16x8, zw3);
 #pragma unroll
         for (int c = 0; c < MC; ++c) {
-          const float4 e0 = dw4[c * 8 + 2 * g], e1 = dw4[c * 8 + 2 * g + 1];
+          const float4 e0 = he0, e1 = he1;
           const float ev[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
           kp_u32x4 vw1, vw2, vw3;
 #pragma unroll
@@ -261,6 +275,13 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
           }
           const kp_bf16x8 vp1 = __builtin_bit_cast(kp_bf16x8, vw1), vp2 = __builtin_bit_cast(kp_bf16x8, vw2),
                           vp3 = __builtin_bit_cast(kp_bf16x8, vw3);
+          __builtin_amdgcn_sched_barrier(0);       // the requests stay behind this block's waits and in front of its MFMAs
+          if (c < MC - 1) {
+            he0 = dw4[(c + 1) * 8 + 2 * g]; he1 = dw4[(c + 1) * 8 + 2 * g + 1];
+          } else if (g == 0) {
+            he0 = dw4[2]; he1 = dw4[3];
+            hz0 = zt4[2]; hz1 = zt4[3]; ha0 = at4[2]; ha1 = at4[3];
+          }
           __builtin_amdgcn_sched_barrier(0);
           f32x16 acc = accW[c];
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vp3, zp1, acc, 0, 0, 0);
