@@ -776,6 +776,81 @@ int cde_dopri5_advance_mlp_sharded(const void* coeffs, const void* knots, int64_
                                    int64_t B, int64_t C, int64_t H, int dtype, void* workspace, size_t workspace_bytes,
                                    int64_t first_launch, const double* reduced_sums, int64_t B_global, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The remaining step-size options of torchdiffeq's adaptive solvers -- first_step, step_t, min_step, max_step -- for the
+ * unsharded dopri5 solves, forward and backward (restated in oracle/odeint.py: _Dopri5.integrate):
+ *   first_step  replaces Hairer's initial step (the three opening launches of a solve stay; NaN: not given)
+ *   min_step, max_step   every attempt's step size is clamped to [min_step, max_step] before it is planned and after the
+ *               step-size update (a non-finite one becomes min_step); an attempt longer than max_step is rejected and one
+ *               no longer than min_step accepted, whatever its error ratio
+ *   step_t      (n_step) float64 DEVICE array, ascending (NULL when n_step == 0): an attempt that would pass the next step
+ *               time is clipped onto it -- unlike a jump time without re-evaluating f after it, and a jump time strictly
+ *               inside the clipped attempt takes over.  The adjoint solves: negated and ascending, like jump_s.  In the
+ *               traces the third value of a row stays "clipped onto a JUMP time": a step-time clip records 0.
+ *   state       DEVICE memory of the byte count the size query below returns, owned by the library between
+ *               first_launch = 0 and the end of a solve (of one output interval of a backward pass): the call with
+ *               first_launch = 0 copies the option values there (the kernels take this one pointer), and what the
+ *               controller carries for them ping-pongs there with the launch parity, like the controller blocks.
+ * The struct itself is read on the HOST by every call that takes it; each entry point below is the one named before its
+ * suffix with one more argument ahead of `stream`, and `options` == NULL is exactly that entry point.  Rejected before any
+ * HIP call: min_step < 0 or NaN, max_step < min_step or NaN, n_step < 0 (CDE_ERR_SHAPE); n_step > 0 without step_t, or
+ * no `state` (CDE_ERR_NULL).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  double first_step, min_step, max_step;
+  const double* step_t;
+  int64_t n_step;
+  void* state;
+} cde_dopri5_step_options;
+size_t cde_dopri5_step_state_bytes(void);
+int cde_dopri5_advance_options(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
+                               const void* bias, int act, const void* z0, const double* t_out, int64_t n_out,
+                               const double* jump_t, int64_t n_jump, double rtol, double atol, double safety,
+                               double ifactor, double dfactor, void* z_out, int64_t B, int64_t C, int64_t H, int dtype,
+                               int variant, void* workspace, size_t workspace_bytes, int64_t first_launch,
+                               int64_t n_launches, const cde_dopri5_step_options* options, void* stream);
+int cde_dopri5_advance_mlp_options(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
+                                   const void* bias1, int64_t width, const void* W2, const void* bias2, int act,
+                                   const void* z0, const double* t_out, int64_t n_out, const double* jump_t, int64_t n_jump,
+                                   double rtol, double atol, double safety, double ifactor, double dfactor, void* z_out,
+                                   int64_t B, int64_t C, int64_t H, int dtype, void* workspace, size_t workspace_bytes,
+                                   int64_t first_launch, int64_t n_launches, const cde_dopri5_step_options* options,
+                                   void* stream);
+int cde_dopri5_adjoint_advance_options(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
+                                       const void* bias, int act, const void* y_init, const void* a_init, double s0,
+                                       double s1, const double* jump_s, int64_t n_jump, double rtol, double atol,
+                                       double safety, double ifactor, double dfactor, int norm_kind, void* a_out, int64_t B,
+                                       int64_t C, int64_t H, int dtype, int first_interval, void* workspace,
+                                       size_t workspace_bytes, int64_t first_launch, int64_t n_launches,
+                                       const cde_dopri5_step_options* options, void* stream);
+int cde_dopri5_adjoint_advance_dcontrol_options(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
+                                                const void* W, const void* bias, int act, const void* y_init,
+                                                const void* a_init, double s0, double s1, const double* jump_s,
+                                                int64_t n_jump, double rtol, double atol, double safety, double ifactor,
+                                                double dfactor, int norm_kind, void* a_out, int64_t B, int64_t C, int64_t H,
+                                                int dtype, int first_interval, void* workspace, size_t workspace_bytes,
+                                                int64_t first_launch, int64_t n_launches, void* grad_coeffs,
+                                                int64_t control_numel, void* grad_knots,
+                                                const cde_dopri5_step_options* options, void* stream);
+int cde_dopri5_adjoint_mlp_advance_options(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
+                                           const void* W1, const void* bias1, int64_t width, const void* W2,
+                                           const void* bias2, int act, const void* y_init, const void* a_init, double s0,
+                                           double s1, const double* jump_s, int64_t n_jump, double rtol, double atol,
+                                           double safety, double ifactor, double dfactor, int norm_kind, void* a_out,
+                                           int64_t B, int64_t C, int64_t H, int dtype, int first_interval, void* workspace,
+                                           size_t workspace_bytes, int64_t first_launch, int64_t n_launches,
+                                           const cde_dopri5_step_options* options, void* stream);
+int cde_dopri5_adjoint_mlp_advance_dcontrol_options(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
+                                                    const void* W1, const void* bias1, int64_t width, const void* W2,
+                                                    const void* bias2, int act, const void* y_init, const void* a_init,
+                                                    double s0, double s1, const double* jump_s, int64_t n_jump, double rtol,
+                                                    double atol, double safety, double ifactor, double dfactor,
+                                                    int norm_kind, void* a_out, int64_t B, int64_t C, int64_t H, int dtype,
+                                                    int first_interval, void* workspace, size_t workspace_bytes,
+                                                    int64_t first_launch, int64_t n_launches, void* grad_coeffs,
+                                                    int64_t control_numel, void* grad_knots,
+                                                    const cde_dopri5_step_options* options, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -309,6 +309,24 @@ _SIGNATURES = {
     "cde_dopri5_advance_sharded": (_i, [_p, _p, _i64, _i, _p, _p, _i, _p, _p, _i64, _p, _i64, _d, _d, _d, _d, _d, _p, _i64,
                                         _i64, _i64, _i, _i, _p, _sz, _i64, _p, _i64, _p]),
     "cde_dopri5_adjoint_finish": (_i, [_p, _sz, _p, _p, _i64, _i64, _i64, _i, _p]),
+    # the unsharded advance calls with first_step / step_t / min_step / max_step: one more pointer (a host StepOptions, or
+    # None) ahead of the stream
+    "cde_dopri5_step_state_bytes": (_sz, []),
+    "cde_dopri5_advance_options": (_i, [_p, _p, _i64, _i, _p, _p, _i, _p, _p, _i64, _p, _i64, _d, _d, _d, _d, _d, _p, _i64, _i64,
+                                        _i64, _i, _i, _p, _sz, _i64, _i64, _p, _p]),
+    "cde_dopri5_advance_mlp_options": (_i, [_p, _p, _i64, _i, _p, _p, _i64, _p, _p, _i, _p, _p, _i64, _p, _i64, _d, _d, _d, _d,
+                                            _d, _p, _i64, _i64, _i64, _i, _p, _sz, _i64, _i64, _p, _p]),
+    "cde_dopri5_adjoint_advance_options": (_i, [_p, _p, _i64, _i, _p, _p, _i, _p, _p, _d, _d, _p, _i64, _d, _d, _d, _d, _d, _i,
+                                                _p, _i64, _i64, _i64, _i, _i, _p, _sz, _i64, _i64, _p, _p]),
+    "cde_dopri5_adjoint_advance_dcontrol_options": (_i, [_p, _p, _i64, _i, _p, _p, _i, _p, _p, _d, _d, _p, _i64, _d, _d, _d, _d,
+                                                         _d, _i, _p, _i64, _i64, _i64, _i, _i, _p, _sz, _i64, _i64, _p, _i64,
+                                                         _p, _p, _p]),
+    "cde_dopri5_adjoint_mlp_advance_options": (_i, [_p, _p, _i64, _i, _p, _p, _i64, _p, _p, _i, _p, _p, _d, _d, _p, _i64, _d,
+                                                    _d, _d, _d, _d, _i, _p, _i64, _i64, _i64, _i, _i, _p, _sz, _i64, _i64, _p,
+                                                    _p]),
+    "cde_dopri5_adjoint_mlp_advance_dcontrol_options": (_i, [_p, _p, _i64, _i, _p, _p, _i64, _p, _p, _i, _p, _p, _d, _d, _p,
+                                                             _i64, _d, _d, _d, _d, _d, _i, _p, _i64, _i64, _i64, _i, _i, _p,
+                                                             _sz, _i64, _i64, _p, _i64, _p, _p, _p]),
     "cde_mlp_grad_reduce_workspace_bytes": (_sz, []),
     "cde_mlp_grad_reduce": (_i, [_p, _p, _i64, _i, _p, _p, _sz, _p]),
     "cde_rk4_adjoint_mlp_workspace_bytes": (_sz, [_i64]),
@@ -331,6 +349,13 @@ class DopriStatus(ctypes.Structure):
                 ("n_reject", ctypes.c_int64), ("phase", ctypes.c_int32), ("on_jump", ctypes.c_int32),
                 ("refresh", ctypes.c_int32), ("pad", ctypes.c_int32), ("slot", ctypes.c_int32),
                 ("stored", ctypes.c_int32), ("hint_lo", ctypes.c_int32), ("hint_hi", ctypes.c_int32)]
+
+
+class StepOptions(ctypes.Structure):
+    """Mirror of cde_dopri5_step_options (include/cde_mi355x.h): read on the host by the *_options entry points; `step_t`
+    and `state` (cde_dopri5_step_state_bytes() bytes) are device addresses."""
+    _fields_ = [("first_step", ctypes.c_double), ("min_step", ctypes.c_double), ("max_step", ctypes.c_double),
+                ("step_t", ctypes.c_void_p), ("n_step", ctypes.c_int64), ("state", ctypes.c_void_p)]
 
 
 def load():

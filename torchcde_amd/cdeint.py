@@ -826,6 +826,50 @@ def _status(workspace, at):
     return _lib.DopriStatus.from_buffer_copy(workspace[at:at + size].cpu().numpy().tobytes())
 
 
+_STEP_KEYS = ("first_step", "step_t", "min_step", "max_step")
+
+
+class _StepOptions:
+    """first_step / step_t / min_step / max_step of one dopri5 solve as torchdiffeq reads them (floats, 0-d tensors; step_t
+    any 1-d tensor or sequence), popped from `options`.  `given` is false when none of them is set: the plans then call the
+    entry points without them.  `block()` builds the host struct of the *_options entry points with fresh kernel state."""
+
+    def __init__(self, options, jump_t, device, kept):
+        """`kept`: the times a solve keeps (torchdiffeq drops those before its start) -- the check for a time shared by
+        step_t and jump_t, or repeated in one of them, runs over these."""
+        number = lambda v: float(v.item() if isinstance(v, torch.Tensor) else v)      # noqa: E731
+        values = {key: options.pop(key, None) for key in _STEP_KEYS}
+        self.given = any(v is not None for v in values.values())
+        self.device = device
+        self.first_step = float("nan") if values["first_step"] is None else number(values["first_step"])
+        self.min_step = 0.0 if values["min_step"] is None else number(values["min_step"])
+        self.max_step = float("inf") if values["max_step"] is None else number(values["max_step"])
+        self.step_t = self.step_s = None
+        self.n_step = 0
+        if values["step_t"] is not None:
+            # torchdiffeq reads the times as float64 (a list: exactly); a reversed-time solve negates `torch.as_tensor(step_t)`
+            # first, which makes a list of floats a float32 tensor -- both are kept, each for the solve that sees it
+            st = values["step_t"]
+            raw = torch.sort(_to_host(torch.as_tensor(st)).reshape(-1)).values
+            st = _to_host(st) if isinstance(st, torch.Tensor) else torch.as_tensor(st, dtype=torch.float64)
+            st = torch.sort(st.to(torch.float64).reshape(-1)).values
+            both = st if jump_t is None else torch.cat([st, _to_host(torch.as_tensor(jump_t)).to(torch.float64).reshape(-1)])
+            if bool((both[kept(both)].unique(return_counts=True)[1] > 1).any()):
+                raise ValueError("`step_t` and `jump_t` must not have any repeated elements between them.")
+            self.n_step = st.numel()
+            self.step_t = st.to(device)
+            self.step_s = (-raw).flip(0).to(torch.float64).contiguous().to(device)       # the backward solve runs in s = -t
+        if self.given and (not self.min_step >= 0.0 or not self.max_step >= self.min_step):
+            raise ValueError("torchcde_amd: dopri5 needs 0 <= min_step <= max_step (got %r, %r)" % (self.min_step, self.max_step))
+
+    def block(self, lib, reverse=False):
+        state = torch.zeros(lib.cde_dopri5_step_state_bytes(), dtype=torch.uint8, device=self.device)
+        times = self.step_s if reverse else self.step_t
+        block = _lib.StepOptions(self.first_step, self.min_step, self.max_step, _lib.ptr(times), self.n_step, _lib.ptr(state))
+        block.keep = (state, times)           # the device memory the struct points at lives as long as the struct
+        return block
+
+
 class _Dopri5Plan:
     def __init__(self, path, field, batch, H, C, t, rtol, atol, options, variant=_lib.VARIANT_AUTO,
                  adjoint_rtol=None, adjoint_atol=None, adjoint_options=None):
@@ -841,7 +885,13 @@ class _Dopri5Plan:
         self.safety = float(options.pop("safety", 0.9))
         self.ifactor = float(options.pop("ifactor", 10.0))
         self.dfactor = float(options.pop("dfactor", 0.2))
-        for key in ("first_step", "step_t", "min_step", "max_step", "max_num_steps", "dtype", "norm"):
+        t_first, t_last = float(_to_host(t)[0]), float(_to_host(t)[-1])
+        self.steps = _StepOptions(options, jump_t, path._native_inputs()[0].device, lambda times: times >= t_first)
+        self.adj_steps = self.steps           # adjoint_options=None: the forward options are the backward's
+        if self.steps.given and self.shared is not None:
+            raise NotImplementedError("torchcde_amd: first_step / step_t / min_step / max_step have no form under "
+                                      "distributed.shared_step_control (one step controller across the shards)")
+        for key in ("max_num_steps", "dtype", "norm"):
             if options.get(key, None) is not None:
                 raise NotImplementedError("torchcde_amd: dopri5 option %r is not supported natively" % key)
             options.pop(key, None)
@@ -879,6 +929,11 @@ class _Dopri5Plan:
             self.adj_safety = float(adj.pop("safety", 0.9))
             self.adj_ifactor = float(adj.pop("ifactor", 10.0))
             self.adj_dfactor = float(adj.pop("dfactor", 0.2))
+            # (every output interval keeps the times after its own start in reversed time: all of them, those up to t[-1])
+            self.adj_steps = _StepOptions(adj, jump_b, self.device, lambda times: times <= t_last)
+            if self.adj_steps.given and self.shared is not None:
+                raise NotImplementedError("torchcde_amd: first_step / step_t / min_step / max_step have no form under "
+                                          "distributed.shared_step_control (one step controller across the shards)")
             if jump_b is None:
                 self.jump_s, self.n_jump_s = None, 0
             else:
@@ -911,8 +966,12 @@ class _Dopri5Plan:
                 _lib.ptr(workspace), workspace.numel())
         stream = _lib.stream_ptr(self.device)
         shared = self.shared
+        steps = ()
         if shared is None:
             advance = "cde_dopri5_advance" + suffix
+            if self.steps.given:
+                block = self.steps.block(lib)
+                advance, steps = advance + "_options", (ctypes.addressof(block),)
         else:
             reduce, global_batch = shared
             sums = torch.zeros(2, dtype=torch.float64, device=self.device)
@@ -922,7 +981,7 @@ class _Dopri5Plan:
         launched = 0
         while True:
             if shared is None:
-                _lib.check(getattr(lib, advance)(*head, launched, _DOPRI_CHUNK, stream), advance)
+                _lib.check(getattr(lib, advance)(*head, launched, _DOPRI_CHUNK, *steps, stream), advance)
                 launched += _DOPRI_CHUNK
             else:
                 for _ in range(_DOPRI_CHUNK):
@@ -984,6 +1043,7 @@ class _Dopri5Plan:
         stride = lib.cde_dopri5_adjoint_status_stride()
         a_out = torch.empty(B, H, dtype=torch.float32, device=dev)
         shared = self.shared
+        with_steps = self.adj_steps.given and shared is None
         reduced = None
         # "seminorm": the parameter blocks are not part of the decision -- only the 8 state sums travel between the shards
         state_only = shared is not None and self.adj_norm_kind == 1
@@ -1019,6 +1079,9 @@ class _Dopri5Plan:
             advance = prefix + ("advance_dcontrol" if want_control else "advance")
             extra = ((_lib.ptr(grad_x), int(self.control_numel), _lib.ptr(grad_k)) if want_control else
                      () if mlp else (None, 0))
+            if with_steps:                     # (the *_options entry points are unsharded: no reduced sums to pass)
+                advance += "_options"
+                extra = extra if want_control else ()
         else:
             advance = prefix + ("advance_sharded" if mlp else "advance")        # (the affine entry point takes the sums)
             count = () if mlp else (1,)
@@ -1032,6 +1095,7 @@ class _Dopri5Plan:
             trace_offset = lambda which: (lib.cde_dopri5_adjoint_trace_offset,                            # noqa: E731
                                           lib.cde_dopri5_adjoint_attempt_trace_offset)[which](B, C, H)
         w_args = _weight_args(weights)
+        step_args = ()
         for i in range(self.n_out - 1, 0, -1):
             y = z_saved[:, i].contiguous()
             s0, s1 = -float(self.t_host[i]), -float(self.t_host[i - 1])
@@ -1042,10 +1106,13 @@ class _Dopri5Plan:
                     self.adj_safety, self.adj_ifactor, self.adj_dfactor, self.adj_norm_kind, _lib.ptr(a_out), B, C, H,
                     _lib.dtype_enum(torch.float32), int(i == self.n_out - 1) | (2 if want_t else 0), _lib.ptr(workspace),
                     workspace.numel())
+            if with_steps:                     # every output interval is a fresh solve: first_step and the step times restart
+                block = self.adj_steps.block(lib, reverse=True)
+                step_args = (ctypes.addressof(block),)
             launched = 0
             while True:
                 if shared is None:
-                    _lib.check(getattr(lib, advance)(*head, launched, _DOPRI_CHUNK, *extra, stream), advance)
+                    _lib.check(getattr(lib, advance)(*head, launched, _DOPRI_CHUNK, *extra, *step_args, stream), advance)
                     launched += _DOPRI_CHUNK
                 else:
                     for _ in range(_DOPRI_CHUNK):
@@ -1393,7 +1460,7 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
                 and tensors[0].untyped_storage().data_ptr() == packed.untyped_storage().data_ptr()):
             control_block = tensors[0]          # (+ optionally the knot times X._t: a fourth block)
 
-    fixed_keys, adaptive_keys = {"step_size"}, {"jump_t", "safety", "ifactor", "dfactor"}
+    fixed_keys, adaptive_keys = {"step_size"}, {"jump_t", "safety", "ifactor", "dfactor", *_STEP_KEYS}
     # ONE normalised view of the options for the fused paths (the step-wise path gets them verbatim, like torchdiffeq):
     # None values and torchdiffeq's own defaults spelled out are the same request as leaving the key away
     fused_options = _strip_noops(options, fixed=method != "dopri5")

@@ -22,6 +22,96 @@ struct DopriCtrl {
 };
 static_assert(sizeof(DopriCtrl) == 112, "cde_dopri5_status (include/cde_mi355x.h) and _lib.DopriStatus mirror this layout");
 
+// torchdiffeq's remaining step-size options (first_step, step_t, min_step, max_step; oracle/odeint.py: _Dopri5.integrate),
+// for the forward and the backward controller alike.  The kernels get ONE pointer for them (null: none of them is set and
+// the controllers take exactly the path they took before these existed) to a device block of the caller's
+// (cde_dopri5_step_options::state): the option values, which the first call of a solve copies there, and what the
+// controller carries from launch to launch, which ping-pongs with the launch parity like the controller blocks -- every
+// workgroup reads state[parity], one lane of workgroup 0 writes state[parity ^ 1].
+struct StepState {
+  int64_t i_step;               // next step time, counted from `first`
+  int32_t on_step;              // pending attempt was clipped onto a step time (and no jump time took over)
+  int32_t first;                // offset of the first kept step time (those >= the solve's start)
+};
+struct StepBlock {              // the device block: cde_dopri5_step_state_bytes() bytes
+  double first_step;            // NaN: Hairer's rule
+  double min_step, max_step;
+  const double* step_t; int64_t n_step;    // ascending; the adjoint solves: in reversed time
+  int64_t reserved;
+  StepState state[2];
+};
+// The controllers' view of the block.  Every value is read where it is used and nothing of it is kept in registers: the
+// attempt kernels have none to spare, and a solve without the options must not pay for them.
+struct StepOptions {
+  const StepBlock* b;           // null: none of the options is set
+  __device__ __forceinline__ bool on() const { return b != nullptr; }
+  // torchdiffeq: `if not isfinite(dt): dt = min_step; dt = dt.clamp(min_step, max_step)`
+  __device__ __forceinline__ double clamp(double dt) const {
+    const double min_step = b->min_step, max_step = b->max_step;
+    if (!(dt - dt == 0.0)) dt = min_step;
+    dt = dt < min_step ? min_step : dt;
+    return dt > max_step ? max_step : dt;
+  }
+  __device__ __forceinline__ double first_step(double hairer) const {
+    const double given = b->first_step;
+    return given == given ? given : hairer;
+  }
+  __device__ __forceinline__ int64_t kept(const StepState& st) const { return b->n_step - st.first; }
+  // phase 0: keep the step times >= t_start, start at min(bisect_right(kept, t_start), len - 1)
+  __device__ __forceinline__ void begin(StepState& st, double t_start) const {
+    const double* step_t = b->step_t;
+    const int64_t n_step = b->n_step;
+    int64_t j = 0;
+    while (j < n_step && step_t[j] < t_start) ++j;
+    const int64_t first = j;
+    while (j < n_step && step_t[j] <= t_start) ++j;
+    st.i_step = j - first;
+    if (n_step - first > 0 && st.i_step > n_step - first - 1) st.i_step = n_step - first - 1;
+    st.first = (int32_t)first; st.on_step = 0;
+  }
+  // the overrides on the decision of an attempt of length dt: longer than max_step is rejected, at most min_step accepted
+  __device__ __forceinline__ bool decide(bool accept, double dt) const {
+    if (dt > b->max_step) accept = false;
+    if (dt <= b->min_step) accept = true;
+    return accept;
+  }
+  // an accepted attempt that was clipped onto a step time moves on to the next one (the last one stays)
+  __device__ __forceinline__ void accepted(StepState& st) const {
+    if (st.on_step && st.i_step != kept(st) - 1) st.i_step++;
+  }
+  // a new attempt [t0, t0 + dt]: clipped onto the next step time when that lies strictly inside
+  __device__ __forceinline__ void clip(StepState& st, double t0, double& t1, double& dt) const {
+    st.on_step = 0;
+    const int64_t at = st.first + st.i_step;
+    if (at >= 0 && at < b->n_step) {                               // (begin() leaves it there whenever a time is kept)
+      const double nxt = b->step_t[at];
+      if (t0 < nxt && nxt < t0 + dt) { st.on_step = 1; t1 = nxt; dt = t1 - t0; }
+    }
+  }
+  __device__ __forceinline__ void publish(const StepState& st, int parity) const {
+    if (blockIdx.x == 0 && threadIdx.x == 0) const_cast<StepBlock*>(b)->state[parity ^ 1] = st;
+  }
+};
+
+// host: what a caller's cde_dopri5_step_options must satisfy (checked before any HIP call; `sharded`: one controller across
+// shards has no form of these options), and the kernels' view of it (null: absent)
+static inline int step_options_check(const cde_dopri5_step_options* o, bool sharded) {
+  if (!o) return CDE_OK;
+  if (sharded) return CDE_ERR_UNSUPPORTED;
+  if (!(o->min_step >= 0.0) || !(o->max_step >= o->min_step) || o->n_step < 0) return CDE_ERR_SHAPE;
+  if ((o->n_step > 0 && !o->step_t) || !o->state) return CDE_ERR_NULL;
+  return CDE_OK;
+}
+static inline const StepBlock* step_block(const cde_dopri5_step_options* o) { return o ? (const StepBlock*)o->state : nullptr; }
+// the first call of a solve: the option values into the block (the struct is the caller's and may be gone when the launches run)
+static inline int step_block_fill(const cde_dopri5_step_options* o, hipStream_t s) {
+  if (!o) return CDE_OK;
+  struct { double first_step, min_step, max_step; const double* step_t; int64_t n_step; int64_t reserved; } head = {
+      o->first_step, o->min_step, o->max_step, o->step_t, o->n_step, 0};
+  static_assert(sizeof(head) == offsetof(StepBlock, state), "the block's head");
+  return hipMemcpyAsync(o->state, &head, sizeof(head), hipMemcpyHostToDevice, s) == hipSuccess ? CDE_OK : CDE_ERR_LAUNCH;
+}
+
 // wave-uniform copies: the controller's outputs derive from LDS reads (the block sums), so the compiler keeps them --
 // and everything computed from them -- in vector registers; read back through lane 0 they live in scalar registers
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -57,6 +147,17 @@ __device__ __forceinline__ void block_total(double (&v)[NV], double* red) {
     for (int w = 0; w < nw; ++w) s += red[k * nw + w];
     v[k] = s;
   }
+}
+
+// what the previous launch left for the step options, as wave-uniform values (scalar registers: the controllers run where
+// the attempt kernels have no vector register to spare)
+__device__ __forceinline__ StepState step_state(const StepOptions& so, int parity) {
+  StepState st{};
+  if (so.on()) {
+    const StepState in = so.b->state[parity];
+    st.i_step = uni(in.i_step); st.on_step = uni(in.on_step); st.first = uni(in.first);
+  }
+  return st;
 }
 
 __device__ __forceinline__ float next_toward(float x, float dir) { return nextafterf(x, x + dir); }

@@ -5,7 +5,8 @@
 // augmented state (vjp_t, y, a, dL/dtheta_1, ..) in reversed time, one odeint call per output interval.  Its step
 // controller sees the WHOLE augmented state through the default "mixed" norm
 //     max(|e_t|, rms(e_y), rms(e_a), max_p rms(e_theta_p))                (e = error / tolerance, elementwise)
-// -- `adjoint_options=dict(norm="seminorm")` drops the parameter blocks -- and the solve of an interval ends by stepping
+// -- `adjoint_options=dict(norm="seminorm")` drops the parameter blocks; first_step / step_t / min_step / max_step of the
+// backward solve are the rules of cde_dopri.h: StepOptions, restarted in every output interval -- and the solve of an interval ends by stepping
 // PAST the interval end and evaluating the 4th-order dense interpolant there (restated in oracle/odeint.py: _Dopri5,
 // _Adjoint, odeint_adjoint).  Round 2's K4a used the state-only norm and clipped the last step: both deviations are gone.
 //
@@ -73,8 +74,13 @@ struct AdjPlan {
 //   mode 2:  S0 = sum (err_y/tol)^2, S1 for a, S4 = dt sum c_sol k_t, S5 = dt sum c_err k_t
 //   mode 3:  S4 = dt sum w_D k_t (consumed by the R kernel, not here)
 // Q[2p], Q[2p+1]: the same two slots for parameter tensor p (from the R kernel).
-__device__ __forceinline__ AdjPlan adj_controller(const AdjCommon& g, AdjCtrl& k, const double* S, const double* Q) {
+// step: first_step / step_t / min_step / max_step of the backward solve, step_t in reversed time (null: none given); every
+// interval starts them afresh.
+__device__ __forceinline__ AdjPlan adj_controller(const AdjCommon& g, AdjCtrl& k, const double* S, const double* Q,
+                                                  const StepBlock* step, int parity) {
   DopriCtrl& c = k.c;
+  const StepOptions so{step};
+  StepState st = step_state(so, parity);
   const double n_elems = (double)g.n_state;
   auto rms = [](double s, double n) { return (float)sqrt(s / n); };
   auto maxf = [](float a, float b) { return a > b ? a : b; };
@@ -100,6 +106,7 @@ __device__ __forceinline__ AdjPlan adj_controller(const AdjCommon& g, AdjCtrl& k
     c.i_jump = j - first;
     if (g.n_jump - first > 0 && c.i_jump > g.n_jump - first - 1) c.i_jump = g.n_jump - first - 1;
     c.pad = (int32_t)first;
+    if (so.on()) so.begin(st, c.t_hi);
     k.T = g.carry[0];
     k.over = 0; k.x_end = 0.0;
   } else if (c.phase == 1) {
@@ -122,12 +129,16 @@ __device__ __forceinline__ AdjPlan adj_controller(const AdjCommon& g, AdjCtrl& k
     h1 = h1 < 0 ? -h1 : h1;
     const float hundred = 100.f * h0;
     c.dt = (double)(hundred < h1 ? hundred : h1);
+    if (so.on()) {                                                // first_step replaces Hairer's value; the clamp of every step
+      c.dt = so.clamp(so.first_step(c.dt));
+    }
     mode = 2;
   } else {
     const float T = (float)k.T, T1 = T + (float)S[4];
     const float tol_t = atol + rtol * maxf(fabsf(T), fabsf(T1));
     const float ratio_t = maxf(maxf(fabsf((float)S[5] / tol_t), params(0)), maxf(rms(S[0], n_elems), rms(S[1], n_elems)));
     accept = ratio_t <= 1.f;
+    if (so.on()) accept = so.decide(accept, c.dt_try);
     if (g.trace_all && blockIdx.x == 0 && threadIdx.x == 0 && c.n_accept + c.n_reject < ADJ_TRACE_ATTEMPTS) {
       double* row = g.trace_all + 5 * (c.n_accept + c.n_reject);
       row[0] = c.t_hi; row[1] = c.t1_try; row[2] = c.on_jump ? 1.0 : 0.0; row[3] = accept ? 1.0 : 0.0; row[4] = (double)ratio_t;
@@ -146,6 +157,7 @@ __device__ __forceinline__ AdjPlan adj_controller(const AdjCommon& g, AdjCtrl& k
         if (c.i_jump != kept - 1) c.i_jump++;
         c.refresh = 1;
       }
+      if (so.on()) so.accepted(st);
       // a step that reached s1 ends the interval: its increment is NOT committed -- this launch repeats the step and
       // accumulates the dense output at s1 instead (mode 3), which the R kernel adds to the running totals
       k.commit = k.over ? 2 : 1;
@@ -164,6 +176,7 @@ __device__ __forceinline__ AdjPlan adj_controller(const AdjCommon& g, AdjCtrl& k
       factor = g.ifactor < f ? g.ifactor : f;
     }
     c.dt = c.dt_try * factor;
+    if (so.on()) c.dt = so.clamp(c.dt);
     mode = 2;
   }
   double t0 = 0, t1 = 0, dt = 0;
@@ -176,13 +189,15 @@ __device__ __forceinline__ AdjPlan adj_controller(const AdjCommon& g, AdjCtrl& k
     k.over = 0; k.x_end = 0.0;
     t0 = c.t_hi;
     dt = c.dt;
-    if (!(dt == dt) || dt > 1e300 || dt < -1e300) dt = 0.0;
+    if (so.on()) dt = so.clamp(dt);
+    else if (!(dt == dt) || dt > 1e300 || dt < -1e300) dt = 0.0;
     t1 = t0 + dt;
+    if (so.on()) so.clip(st, t0, t1, dt);
     int on_jump = 0;
     const int64_t kept = g.n_jump - c.pad;
     if (kept > 0) {
       const double nxt = g.jump_s[c.pad + c.i_jump];
-      if (t0 < nxt && nxt < t0 + dt) { on_jump = 1; t1 = nxt; dt = t1 - t0; }
+      if (t0 < nxt && nxt < t0 + dt) { on_jump = 1; st.on_step = 0; t1 = nxt; dt = t1 - t0; }   // a jump inside takes over
     }
     c.t1_try = t1; c.dt_try = dt; c.on_jump = on_jump;
     // no clipping at the interval end: the step passes it and the dense interpolant is evaluated there
@@ -190,6 +205,7 @@ __device__ __forceinline__ AdjPlan adj_controller(const AdjCommon& g, AdjCtrl& k
     k.kind0 = c.refresh ? 1 : (c.n_accept > 0 ? -1 : 0);
     plan.kind0 = k.kind0;
   }
+  if (so.on()) so.publish(st, parity);
   k.mode = mode;
   plan.accept = accept; plan.mode = mode; plan.t0 = t0; plan.t1 = t1; plan.dt = dt;
   return plan;

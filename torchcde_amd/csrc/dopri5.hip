@@ -8,6 +8,9 @@
 //   * stage times formed in the state dtype: t0 + alpha_i*dt, the two alpha == 1 stages at nextafter(t1, -inf)
 //   * jump_t: steps are clipped to land exactly on the next jump time and f is re-evaluated just after it
 //   * first step by Hairer's rule (two extra evaluations), outputs by the 4th-order dense interpolant
+//   * first_step / step_t / min_step / max_step (the *_options entry points; cde_dopri.h: StepOptions): first_step in place of
+//     Hairer's value, every step size clamped to [min_step, max_step], steps clipped onto the next step time (f is not
+//     re-evaluated there), an attempt longer than max_step rejected and one no longer than min_step accepted
 //
 // Execution model.  A batch-global decision per attempted step needs a grid-wide reduction; instead of a host
 // round trip or a cooperative grid barrier, every launch of `dopri5_attempt_kernel` is "finish the previous
@@ -38,6 +41,7 @@ struct DopriArgs {
   double* trace;                // [CDE_DOPRI5_TRACE_STEPS][3]: (t0, t1, clipped onto a jump time) of every accepted step
   const double* ext_sums;       // sharded batch: the pending sums, already added up over ALL shards (else nullptr)
   int64_t B_global;             // number of series the error norm runs over (0: this call's B)
+  const StepBlock* step;        // first_step / step_t / min_step / max_step (null: none given)
 };
 
 // vector field row for lane (s,h): sum_c act(bias + W z) dX_c, control derivative at time ts
@@ -108,7 +112,10 @@ struct DopriPlan {
 };
 
 template <typename T>
-__device__ __forceinline__ DopriPlan<T> dopri_controller(const DopriArgs<T>& g, DopriCtrl& c, double sum0, double sum1) {
+__device__ __forceinline__ DopriPlan<T> dopri_controller(const DopriArgs<T>& g, DopriCtrl& c, double sum0, double sum1,
+                                                         int parity) {
+  const StepOptions so{g.step};
+  StepState st = step_state(so, parity);
   const double n_elems = (double)((g.B_global > 0 ? g.B_global : g.B) * g.H);
   bool accept = false;
   int mode;                     // what this launch computes: 0 = f0 norms, 1 = f1 norm, 2 = attempt, 3 = nothing more
@@ -127,6 +134,7 @@ __device__ __forceinline__ DopriPlan<T> dopri_controller(const DopriArgs<T>& g, 
     c.i_jump = j - first;
     if (g.n_jump - first > 0 && c.i_jump > g.n_jump - first - 1) c.i_jump = g.n_jump - first - 1;
     c.pad = (int32_t)first;                                    // offset of the first kept jump time
+    if (so.on()) so.begin(st, c.t_hi);
   } else if (c.phase == 1) {
     // Hairer: d0 = ||y0/scale||, d1 = ||f0/scale||
     const T d0 = (T)sqrt(sum0 / n_elems), d1 = (T)sqrt(sum1 / n_elems);
@@ -153,12 +161,16 @@ __device__ __forceinline__ DopriPlan<T> dopri_controller(const DopriArgs<T>& g, 
     h1 = h1 < 0 ? -h1 : h1;
     const T hundred = (T)100 * h0;
     c.dt = (double)(hundred < h1 ? hundred : h1);
+    if (so.on()) {                                              // first_step replaces Hairer's value; the clamp of every step
+      c.dt = so.clamp(so.first_step(c.dt));
+    }
     mode = 2;
   } else {
     // decide the pending attempt: ratio = sqrt(mean((err/tol)^2))
     const T ratio_t = (T)sqrt(sum0 / n_elems);
     accept = ratio_t <= (T)1;
     // (min_step = 0, max_step = inf: the extra accept/reject overrides of torchdiffeq never fire)
+    if (so.on()) accept = so.decide(accept, c.dt_try);
     if (accept) {
       c.n_accept++;
       c.t_lo = c.t_hi; c.t_hi = c.t1_try;
@@ -173,6 +185,7 @@ __device__ __forceinline__ DopriPlan<T> dopri_controller(const DopriArgs<T>& g, 
         if (c.i_jump != kept - 1) c.i_jump++;
         c.refresh = 1;
       }
+      if (so.on()) so.accepted(st);
     } else {
       c.n_reject++;
       c.t_lo = c.t_hi;                                          // oracle: t_lo, t_hi = t0, t0
@@ -188,6 +201,7 @@ __device__ __forceinline__ DopriPlan<T> dopri_controller(const DopriArgs<T>& g, 
       factor = g.ifactor < f ? g.ifactor : f;
     }
     c.dt = c.dt_try * factor;
+    if (so.on()) c.dt = so.clamp(c.dt);
     mode = 2;
   }
 
@@ -205,15 +219,18 @@ __device__ __forceinline__ DopriPlan<T> dopri_controller(const DopriArgs<T>& g, 
     // new attempt from t_hi
     t0 = c.t_hi;
     dt = c.dt;
-    if (!(dt == dt) || dt > 1e300 || dt < -1e300) dt = 0.0;     // non-finite -> min_step (0)
+    if (so.on()) dt = so.clamp(dt);
+    else if (!(dt == dt) || dt > 1e300 || dt < -1e300) dt = 0.0;     // non-finite -> min_step (0)
     t1 = t0 + dt;
+    if (so.on()) so.clip(st, t0, t1, dt);
     const int64_t kept = g.n_jump - c.pad;
     if (kept > 0) {
       const double nxt = g.jump_t[c.pad + c.i_jump];
-      if (t0 < nxt && nxt < t0 + dt) { on_jump = 1; t1 = nxt; dt = t1 - t0; }
+      if (t0 < nxt && nxt < t0 + dt) { on_jump = 1; st.on_step = 0; t1 = nxt; dt = t1 - t0; }   // a jump inside takes over
     }
     c.t1_try = t1; c.dt_try = dt; c.on_jump = on_jump;
   }
+  if (so.on()) so.publish(st, parity);
 
   DopriPlan<T> plan;
   plan.accept = accept; plan.mode = mode; plan.t0 = t0; plan.t1 = t1; plan.dt = dt; plan.dt_done = dt_done;
@@ -254,7 +271,7 @@ __global__ void dopri5_attempt_kernel(DopriArgs<T> g, int parity) {
     block_sum2(sum0, sum1, red);
   }
 
-  DopriPlan<T> plan = dopri_controller<T>(g, c, sum0, sum1);
+  DopriPlan<T> plan = dopri_controller<T>(g, c, sum0, sum1, parity);
   const bool accept = plan.accept;
   const int mode = plan.mode;
   const double t0 = plan.t0, t1 = plan.t1, dt = plan.dt, dt_done = plan.dt_done;
@@ -520,7 +537,7 @@ __global__ __launch_bounds__(512, 2) void dopri5_attempt_mfma(DopriArgs<float> g
   //  still be reading the block sums)
   if constexpr (MLP && SPLIT && CT == MC) __syncthreads();
   CDE_STAMP(3);
-  const DopriPlan<T> plan = dopri_controller<T>(g, c, sums[0], sums[1]);
+  const DopriPlan<T> plan = dopri_controller<T>(g, c, sums[0], sums[1], parity);
   // The controller's outputs derive from LDS reads (the block sums), so the compiler would keep them -- and every
   // stage time, interval index and slot pointer computed from them -- in vector registers; read back through lane 0
   // they are scalars.
@@ -783,7 +800,7 @@ __global__ __launch_bounds__(64 * NW, 2) void dopri5_attempt_wide(DopriArgs<floa
     block_total<2>(sums, red);
   }
   const int phase_in = uni(c.phase), old_slot = uni(c.slot), pending_stored = uni(c.stored);
-  const DopriPlan<T> plan = dopri_controller<T>(g, c, sums[0], sums[1]);
+  const DopriPlan<T> plan = dopri_controller<T>(g, c, sums[0], sums[1], parity);
   const int mode = uni(plan.mode);
   const bool accepted = uni((int)plan.accept) != 0;
   const bool commit = phase_in == 3 && accepted;
@@ -1140,7 +1157,8 @@ static TwoLayerField one_layer(const void* W, const void* bias, int act) { retur
 
 static int dopri5_advance(const Control& x, const TwoLayerField& f, const DopriIO& io, const Jumps& jumps,
                           const StepControl& tol, const Shape& n, int dtype, int variant, const Workspace& ws, LaunchWindow w,
-                          const Sharding& sh, hipStream_t s) {
+                          const Sharding& sh, const cde_dopri5_step_options* opts, hipStream_t s) {
+  if (const int rc = step_options_check(opts, sh.on())) return rc;
   const int64_t B = n.B, C = n.C, H = n.H;
   const bool mlp = f.W1 != nullptr;
   if (B < 1 || C < 1 || H < 1 || H > 256 || x.n_intervals < 1 || io.n_out < 1 || w.n < 0 || jumps.n < 0) return CDE_ERR_SHAPE;
@@ -1160,6 +1178,8 @@ static int dopri5_advance(const Control& x, const TwoLayerField& f, const DopriI
   unsigned char* base = (unsigned char*)ws.base;
   float* image = (float*)(base + L.image);
   if (w.first == 0) zero_async(base + L.ctrl, 2 * sizeof(DopriCtrl), s);                                  // phase 0
+  if (w.first == 0)
+    if (const int rc = step_block_fill(opts, s)) return rc;
   // the kernels' arguments for element type T; `ns`: series per tile, `img`: the MFMA kernels' weight image
   auto args = [&](auto type, int ns, const float* img) {
     using T = decltype(type);
@@ -1167,7 +1187,8 @@ static int dopri5_advance(const Control& x, const TwoLayerField& f, const DopriI
                         f.act, (const T*)io.z0, io.t_out, io.n_out, jumps.t, jumps.n, tol.rtol, tol.atol, tol.safety,
                         tol.ifactor, tol.dfactor, (T*)io.z_out, B, C, H, ns, (DopriCtrl*)(base + L.ctrl),
                         (T*)(base + L.state), img, (double*)(base + L.partial), L.blocks, (const T*)f.W1,
-                        (const T*)f.bias1, (int)f.width, (double*)(base + L.trace), sh.reduced_sums, sh.B_global};
+                        (const T*)f.bias1, (int)f.width, (double*)(base + L.trace), sh.reduced_sums, sh.B_global,
+                        step_block(opts)};
   };
   // every launch of the window; every form may ask for more than the 64 KB of LDS a kernel gets by default (knot buffer up
   // to 32 KB + the 33.8 KB tanh image + the split forms' 18 KB exchange window): the limit is raised per instantiation
@@ -1263,7 +1284,23 @@ extern "C" int cde_dopri5_advance(const void* coeffs, const void* knots, int64_t
                                   int64_t first_launch, int64_t n_launches, void* stream) {
   return cde::dopri5_advance({coeffs, knots, n_intervals, degree}, cde::one_layer(W, bias, act), {z0, t_out, n_out, z_out},
                              {jump_t, n_jump}, {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, variant,
-                             {workspace, workspace_bytes}, {first_launch, n_launches}, {nullptr, 0}, (hipStream_t)stream);
+                             {workspace, workspace_bytes}, {first_launch, n_launches}, {nullptr, 0}, nullptr, (hipStream_t)stream);
+}
+
+// ... with first_step / step_t / min_step / max_step (`options` null: the call above)
+extern "C" size_t cde_dopri5_step_state_bytes(void) { return sizeof(cde::StepBlock); }
+
+extern "C" int cde_dopri5_advance_options(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
+                                          const void* W, const void* bias, int act, const void* z0, const double* t_out,
+                                          int64_t n_out, const double* jump_t, int64_t n_jump, double rtol, double atol,
+                                          double safety, double ifactor, double dfactor, void* z_out, int64_t B, int64_t C,
+                                          int64_t H, int dtype, int variant, void* workspace, size_t workspace_bytes,
+                                          int64_t first_launch, int64_t n_launches,
+                                          const cde_dopri5_step_options* options, void* stream) {
+  return cde::dopri5_advance({coeffs, knots, n_intervals, degree}, cde::one_layer(W, bias, act), {z0, t_out, n_out, z_out},
+                             {jump_t, n_jump}, {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, variant,
+                             {workspace, workspace_bytes}, {first_launch, n_launches}, {nullptr, 0}, options,
+                             (hipStream_t)stream);
 }
 
 // Sharded batches with ONE step controller (torchdiffeq's semantics for the whole batch): per attempted step every
@@ -1286,7 +1323,7 @@ extern "C" int cde_dopri5_advance_sharded(const void* coeffs, const void* knots,
   if (!reduced_sums || B_global < B) return reduced_sums ? CDE_ERR_SHAPE : CDE_ERR_NULL;
   return cde::dopri5_advance({coeffs, knots, n_intervals, degree}, cde::one_layer(W, bias, act), {z0, t_out, n_out, z_out},
                              {jump_t, n_jump}, {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, variant,
-                             {workspace, workspace_bytes}, {first_launch, 1}, {reduced_sums, B_global}, (hipStream_t)stream);
+                             {workspace, workspace_bytes}, {first_launch, 1}, {reduced_sums, B_global}, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int cde_dopri5_advance_mlp(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -1299,7 +1336,22 @@ extern "C" int cde_dopri5_advance_mlp(const void* coeffs, const void* knots, int
   if (!W1) return CDE_ERR_NULL;
   return cde::dopri5_advance({coeffs, knots, n_intervals, degree}, {W1, bias1, width, W2, bias2, act}, {z0, t_out, n_out, z_out},
                              {jump_t, n_jump}, {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, CDE_VARIANT_AUTO,
-                             {workspace, workspace_bytes}, {first_launch, n_launches}, {nullptr, 0}, (hipStream_t)stream);
+                             {workspace, workspace_bytes}, {first_launch, n_launches}, {nullptr, 0}, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int cde_dopri5_advance_mlp_options(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
+                                              const void* W1, const void* bias1, int64_t width, const void* W2,
+                                              const void* bias2, int act, const void* z0, const double* t_out,
+                                              int64_t n_out, const double* jump_t, int64_t n_jump, double rtol, double atol,
+                                              double safety, double ifactor, double dfactor, void* z_out, int64_t B,
+                                              int64_t C, int64_t H, int dtype, void* workspace, size_t workspace_bytes,
+                                              int64_t first_launch, int64_t n_launches,
+                                              const cde_dopri5_step_options* options, void* stream) {
+  if (!W1) return CDE_ERR_NULL;
+  return cde::dopri5_advance({coeffs, knots, n_intervals, degree}, {W1, bias1, width, W2, bias2, act}, {z0, t_out, n_out, z_out},
+                             {jump_t, n_jump}, {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, CDE_VARIANT_AUTO,
+                             {workspace, workspace_bytes}, {first_launch, n_launches}, {nullptr, 0}, options,
+                             (hipStream_t)stream);
 }
 
 // The same two calls for the two-layer field: one controller across the shards of a sharded batch for the call every example
@@ -1323,5 +1375,5 @@ extern "C" int cde_dopri5_advance_mlp_sharded(const void* coeffs, const void* kn
   if (!reduced_sums || B_global < B) return reduced_sums ? CDE_ERR_SHAPE : CDE_ERR_NULL;
   return cde::dopri5_advance({coeffs, knots, n_intervals, degree}, {W1, bias1, width, W2, bias2, act}, {z0, t_out, n_out, z_out},
                              {jump_t, n_jump}, {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, CDE_VARIANT_AUTO,
-                             {workspace, workspace_bytes}, {first_launch, 1}, {reduced_sums, B_global}, (hipStream_t)stream);
+                             {workspace, workspace_bytes}, {first_launch, 1}, {reduced_sums, B_global}, nullptr, (hipStream_t)stream);
 }

@@ -54,6 +54,7 @@ struct DopriAdjArgs {
   double* pq;                       // [2][ADJ_RBLOCKS][4]: the R kernel's partial sums, slots (q0, q1) of W then of b
   float* att;                       // [ADJ_MAX_WG][2][ADJ_IMAGE_FLOATS]: this launch's S and E images
   AdjCommon com;
+  const StepBlock* step;            // (see adj_controller)
   const double* ext_sums;           // sharded batch: the ADJ_NS pending sums added up over all shards (else nullptr)
   // DCTRL
   float* gx;                        // [2][B][ADJ_GX_ROW]: the launch's per-stage d(a.f)/d(dX_c), unweighted
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(512, 1) void dopri5_adjoint_attempt(DopriAdjArgs g,
   }
   CDE_STAMP(2);
   asm volatile("" ::"v"(touched));
-  const AdjPlan plan = adj_controller(g.com, k, sum, sum + ADJ_NS);
+  const AdjPlan plan = adj_controller(g.com, k, sum, sum + ADJ_NS, g.step, p);
   const int mode = plan.mode;
   // mode 3 repeats the accepted step from ITS start state (the dense output at the interval end needs its slopes)
   const bool commit = phase_in == 3 && plan.accept && mode != 3;
@@ -961,8 +962,10 @@ extern "C" size_t cde_dopri5_adjoint_dcontrol_workspace_bytes(int64_t B, int64_t
 
 static int adjoint_advance(const cde::Control& x, const cde::AffineField& f, const cde::AdjInterval& iv, const cde::Jumps& jumps,
                            const cde::StepControl& tol, const cde::Shape& n, int dtype, const cde::Workspace& ws,
-                           cde::LaunchWindow w, const cde::Sharding& sh, const cde::ControlGrads& cg, hipStream_t s) {
+                           cde::LaunchWindow w, const cde::Sharding& sh, const cde::ControlGrads& cg, hipStream_t s,
+                           const cde_dopri5_step_options* opts = nullptr) {
   using namespace cde;
+  if (const int rc = step_options_check(opts, sh.on())) return rc;
   const int64_t B = n.B, C = n.C, H = n.H;
   if (B < 1 || C < 1 || H < 1 || x.n_intervals < 1 || w.n < 0 || jumps.n < 0 || !(iv.s0 < iv.s1)) return CDE_ERR_SHAPE;
   if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
@@ -989,10 +992,12 @@ static int adjoint_advance(const cde::Control& x, const cde::AffineField& f, con
   g.att = (float*)(base + L.att);
   g.y_init = (const float*)iv.y_init; g.a_init = (const float*)iv.a_init; g.a_out = (float*)iv.a_out;
   g.com = adj_common(iv, jumps, tol, n, x.n_intervals, sh, cg, {H * C * H, H * C}, base, L);
+  g.step = step_block(opts);
   g.ext_sums = sh.reduced_sums;
   g.gx = (float*)(base + L.gx); g.rec = base + L.rec; g.cq = (const double*)(base + L.cq); g.n_cblocks = L.n_cblocks;
   g.ktp = (double*)(base + L.ktp); g.with_knots = cg.knots ? 1 : 0;
   if (w.first == 0) {
+    if (const int rc = step_block_fill(opts, s)) return rc;
     // G, G_local, the prev buffers (like every zero fill of the prologue, queued without a look at its code)
     const int rc = adj_first_launch(base, L, iv, dctrl, s, [&] { zero_async(base + L.G, L.att - L.G, s); return CDE_OK; });
     if (rc != CDE_OK) return rc;
@@ -1054,6 +1059,39 @@ extern "C" int cde_dopri5_adjoint_advance_dcontrol(const void* coeffs, const voi
                          {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
                          {first_launch, n_launches}, {nullptr, 0}, {grad_coeffs, control_numel, grad_knots},
                          (hipStream_t)stream);
+}
+
+// ... with first_step / step_t / min_step / max_step of the backward solve (`options` null: the two calls above, unsharded)
+extern "C" int cde_dopri5_adjoint_advance_options(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
+                                                  const void* W, const void* bias, int act, const void* y_init,
+                                                  const void* a_init, double s0, double s1, const double* jump_s,
+                                                  int64_t n_jump, double rtol, double atol, double safety, double ifactor,
+                                                  double dfactor, int norm_kind, void* a_out, int64_t B, int64_t C,
+                                                  int64_t H, int dtype, int first_interval, void* workspace,
+                                                  size_t workspace_bytes, int64_t first_launch, int64_t n_launches,
+                                                  const cde_dopri5_step_options* options, void* stream) {
+  return adjoint_advance({coeffs, knots, n_intervals, degree}, {W, bias, act},
+                         {y_init, a_init, s0, s1, a_out, first_interval, norm_kind}, {jump_s, n_jump},
+                         {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
+                         {first_launch, n_launches}, {nullptr, 0}, {nullptr, 0, nullptr}, (hipStream_t)stream, options);
+}
+
+extern "C" int cde_dopri5_adjoint_advance_dcontrol_options(const void* coeffs, const void* knots, int64_t n_intervals,
+                                                           int degree, const void* W, const void* bias, int act,
+                                                           const void* y_init, const void* a_init, double s0, double s1,
+                                                           const double* jump_s, int64_t n_jump, double rtol, double atol,
+                                                           double safety, double ifactor, double dfactor, int norm_kind,
+                                                           void* a_out, int64_t B, int64_t C, int64_t H, int dtype,
+                                                           int first_interval, void* workspace, size_t workspace_bytes,
+                                                           int64_t first_launch, int64_t n_launches, void* grad_coeffs,
+                                                           int64_t control_numel, void* grad_knots,
+                                                           const cde_dopri5_step_options* options, void* stream) {
+  if (!grad_coeffs) return CDE_ERR_NULL;
+  return adjoint_advance({coeffs, knots, n_intervals, degree}, {W, bias, act},
+                         {y_init, a_init, s0, s1, a_out, first_interval, norm_kind}, {jump_s, n_jump},
+                         {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
+                         {first_launch, n_launches}, {nullptr, 0}, {grad_coeffs, control_numel, grad_knots},
+                         (hipStream_t)stream, options);
 }
 
 // The ADJ_NS pending state sums of one shard, added up in workgroup order (K4a and K4am alike: cde_dopri_ctl.h)

@@ -66,6 +66,7 @@ struct MlpAdjArgs {
   float* U; float* G2; float* G1; float* Z;      // factor rows [block][rows_per_stage], MADJ_FSLOTS blocks
   float* stash_y; float* stash_a; float* stash_t;  // [3][B*H], [3][B*H], [3][B*4]: slopes of a first / last stage (blocks 0, 5, 6)
   AdjCommon com;
+  const StepBlock* step;            // (see adj_controller)
   int n_wg_max;
   const double* ext_sums;           // sharded batch: the ADJ_NS state sums of the pending attempt, added up over ALL shards
   int n_pq;                         // blocks of parameter sums the R kernel of this batch size leaves in `pq`
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(64 * NWAVE, NWAVE == 8 ? 2 : 1) void dopri5_mlp_adj
   block_total<NSUM>(sum, red);                                     // (also the barrier after the LDS image copy)
   CDE_STAMP(1);
   const int phase_in = c.phase;
-  const AdjPlan plan = adj_controller(g.com, k, sum, sum + ADJ_NS);
+  const AdjPlan plan = adj_controller(g.com, k, sum, sum + ADJ_NS, g.step, p);
   const int mode = uni(plan.mode);
   const bool commit = phase_in == 3 && plan.accept && mode != 3;   // mode 3 repeats the accepted step from ITS start state
   const int ns = mode == 0 ? 1 : mode == 1 ? 2 : 7;
@@ -666,7 +667,7 @@ __global__ __launch_bounds__(512, 2) void dopri5_mlp_adjoint_attempt_s8(MlpAdjAr
   block_total<NSUM>(sum, red);                                     // .. and, past its barriers, everybody's
   CDE_STAMP(1);
   const int phase_in = c.phase;
-  const AdjPlan plan = adj_controller(g.com, k, sum, sum + ADJ_NS);
+  const AdjPlan plan = adj_controller(g.com, k, sum, sum + ADJ_NS, g.step, p);
   const int mode = uni(plan.mode);
   const bool commit = phase_in == 3 && plan.accept && mode != 3;
   const int ns = mode == 0 ? 1 : mode == 1 ? 2 : 7;
@@ -1305,8 +1306,10 @@ cde::MlpReduceArgs madj_reduce_args(unsigned char* base, const MadjLayout& L, do
 static int dopri5_adjoint_mlp_advance(const cde::Control& x, const cde::TwoLayerField& f, const cde::AdjInterval& iv,
                                       const cde::Jumps& jumps, const cde::StepControl& tol, const cde::Shape& n, int dtype,
                                       const cde::Workspace& ws, cde::LaunchWindow w, const cde::Sharding& sh,
-                                      const cde::ControlGrads& cg, hipStream_t s) {
+                                      const cde::ControlGrads& cg, hipStream_t s,
+                                      const cde_dopri5_step_options* opts = nullptr) {
   using namespace cde;
+  if (const int rc = step_options_check(opts, sh.on())) return rc;
   const int64_t B = n.B, C = n.C, H = n.H;
   const bool sharded = sh.on(), dctrl = cg.coeffs != nullptr;
   if (const int rc = adj_window_check(sh, cg, w, B)) return rc;
@@ -1345,10 +1348,12 @@ static int dopri5_adjoint_mlp_advance(const cde::Control& x, const cde::TwoLayer
   g.pq_blocks = L.pq_blocks;
   g.G2hi = L.upper ? (float*)(base + L.G2_hi) : nullptr;
   g.com = adj_common(iv, jumps, tol, n, x.n_intervals, sh, cg, {f.width * H, f.width, H * C * f.width, H * C}, base, L);
+  g.step = step_block(opts);
   g.ext_sums = sh.reduced_sums;
   g.gx = (float*)(base + L.gx); g.rec = base + L.rec; g.cq = (const double*)(base + L.cq); g.n_cblocks = L.n_cblocks;
   g.ktp = (double*)(base + L.ktp); g.with_knots = cg.knots ? 1 : 0;
   if (w.first == 0) {
+    if (const int rc = step_block_fill(opts, s)) return rc;
     // the running totals and the factor rows (padding rows must hold zeros; then their "1" columns), the weight images
     const int rc = adj_first_launch(base, L, iv, dctrl, s, [&] {
       zero_async(base + L.G, L.slopes - L.G, s);
@@ -1461,6 +1466,43 @@ extern "C" int cde_dopri5_adjoint_mlp_advance_dcontrol(const void* coeffs, const
                                     {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
                                     {first_launch, n_launches}, {nullptr, 0}, {grad_coeffs, control_numel, grad_knots},
                                     (hipStream_t)stream);
+}
+
+// ... with first_step / step_t / min_step / max_step of the backward solve (`options` null: the two calls above)
+extern "C" int cde_dopri5_adjoint_mlp_advance_options(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
+                                                      const void* W1, const void* bias1, int64_t width, const void* W2,
+                                                      const void* bias2, int act, const void* y_init, const void* a_init,
+                                                      double s0, double s1, const double* jump_s, int64_t n_jump,
+                                                      double rtol, double atol, double safety, double ifactor,
+                                                      double dfactor, int norm_kind, void* a_out, int64_t B, int64_t C,
+                                                      int64_t H, int dtype, int first_interval, void* workspace,
+                                                      size_t workspace_bytes, int64_t first_launch, int64_t n_launches,
+                                                      const cde_dopri5_step_options* options, void* stream) {
+  return dopri5_adjoint_mlp_advance({coeffs, knots, n_intervals, degree}, {W1, bias1, width, W2, bias2, act},
+                                    {y_init, a_init, s0, s1, a_out, first_interval, norm_kind}, {jump_s, n_jump},
+                                    {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
+                                    {first_launch, n_launches}, {nullptr, 0}, {nullptr, 0, nullptr}, (hipStream_t)stream,
+                                    options);
+}
+
+extern "C" int cde_dopri5_adjoint_mlp_advance_dcontrol_options(const void* coeffs, const void* knots, int64_t n_intervals,
+                                                               int degree, const void* W1, const void* bias1, int64_t width,
+                                                               const void* W2, const void* bias2, int act,
+                                                               const void* y_init, const void* a_init, double s0, double s1,
+                                                               const double* jump_s, int64_t n_jump, double rtol,
+                                                               double atol, double safety, double ifactor, double dfactor,
+                                                               int norm_kind, void* a_out, int64_t B, int64_t C, int64_t H,
+                                                               int dtype, int first_interval, void* workspace,
+                                                               size_t workspace_bytes, int64_t first_launch,
+                                                               int64_t n_launches, void* grad_coeffs, int64_t control_numel,
+                                                               void* grad_knots, const cde_dopri5_step_options* options,
+                                                               void* stream) {
+  if (!grad_coeffs) return CDE_ERR_NULL;
+  return dopri5_adjoint_mlp_advance({coeffs, knots, n_intervals, degree}, {W1, bias1, width, W2, bias2, act},
+                                    {y_init, a_init, s0, s1, a_out, first_interval, norm_kind}, {jump_s, n_jump},
+                                    {rtol, atol, safety, ifactor, dfactor}, {B, C, H}, dtype, {workspace, workspace_bytes},
+                                    {first_launch, n_launches}, {nullptr, 0}, {grad_coeffs, control_numel, grad_knots},
+                                    (hipStream_t)stream, options);
 }
 
 // ---- one step controller for a batch sharded over GPUs, two-layer field (the one-layer protocol of dopri5_adjoint.hip,

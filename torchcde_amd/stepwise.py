@@ -280,13 +280,22 @@ _C_MID = [6025192743 / 30085553152 / 2, 0, 51252292925 / 65400821598 / 2, -26918
           187940372067 / 1594534317056 / 2, -1776094331 / 19743644256 / 2, 11237099 / 235043384 / 2]
 
 
+_DOPRI5_OPTIONS = ("jump_t", "safety", "ifactor", "dfactor", "max_num_steps", "first_step", "step_t", "min_step", "max_step")
+
+
 def _solve_dopri5(f, y0, t, rtol, atol, norm, jump_t=None, safety=0.9, ifactor=10.0, dfactor=0.2,
-                  max_num_steps=2 ** 31 - 1):
-    """Host-driven Dormand-Prince with torchdiffeq's controller (float64 time, batch-global RMS error norm)."""
+                  max_num_steps=2 ** 31 - 1, first_step=None, step_t=None, min_step=0, max_step=float("inf"), record=None):
+    """Host-driven Dormand-Prince with torchdiffeq's controller (float64 time, batch-global RMS error norm).
+    first_step / step_t / min_step / max_step as torchdiffeq's adaptive solvers read them (oracle/odeint.py: _Dopri5):
+    every attempt's step size is clamped to [min_step, max_step], clipped onto the next step time, and an attempt longer
+    than max_step is rejected, one no longer than min_step accepted, whatever its error ratio.  `record`: a list that
+    receives (t0, t1, on_jump, accepted) of every attempt."""
     dev, ydt = y0.device, y0.dtype
     td = torch.float64
     as_t = lambda v: torch.as_tensor(v, dtype=td, device=dev)
     rtol, atol, safety, ifactor, dfactor = as_t(rtol), as_t(atol), as_t(safety), as_t(ifactor), as_t(dfactor)
+    min_step = as_t(0 if min_step is None else min_step)
+    max_step = as_t(float("inf") if max_step is None else max_step)
     beta = [torch.tensor(b, dtype=ydt, device=dev) for b in _BETA]
     alpha = torch.tensor(_ALPHA, dtype=ydt, device=dev)
     c_err = torch.tensor(_C_ERR, dtype=ydt, device=dev)
@@ -294,24 +303,33 @@ def _solve_dopri5(f, y0, t, rtol, atol, norm, jump_t=None, safety=0.9, ifactor=1
     t = t.to(td)
     out = [y0]
     f0 = f(t[0], y0)
-    # Hairer's initial step (order 4 -> exponent 1/5)
-    scale = atol + torch.abs(y0) * rtol
-    d0, d1 = norm(y0 / scale).abs(), norm(f0 / scale).abs()
-    h0 = torch.tensor(1e-6, dtype=ydt, device=dev) if (d0 < 1e-5 or d1 < 1e-5) else 0.01 * d0 / d1
-    h0 = h0.abs()
-    f1 = f(t[0] + h0, y0 + h0 * f0)
-    d2 = torch.abs(norm((f1 - f0) / scale) / h0)
-    if d1 <= 1e-15 and d2 <= 1e-15:
-        h1 = torch.max(torch.tensor(1e-6, dtype=ydt, device=dev), h0 * 1e-3)
+    if first_step is not None:
+        dt = as_t(first_step)
     else:
-        h1 = (0.01 / max(d1, d2)) ** (1. / 5.)
-    dt = torch.min(100 * h0, h1.abs()).to(td)
-    if jump_t is None:
-        jumps = []
-    else:
-        jt = torch.as_tensor(jump_t).detach().to(device=dev, dtype=td).reshape(-1)
-        jumps = torch.sort(jt[jt >= t[0]]).values.tolist()
+        # Hairer's initial step (order 4 -> exponent 1/5)
+        scale = atol + torch.abs(y0) * rtol
+        d0, d1 = norm(y0 / scale).abs(), norm(f0 / scale).abs()
+        h0 = torch.tensor(1e-6, dtype=ydt, device=dev) if (d0 < 1e-5 or d1 < 1e-5) else 0.01 * d0 / d1
+        h0 = h0.abs()
+        f1 = f(t[0] + h0, y0 + h0 * f0)
+        d2 = torch.abs(norm((f1 - f0) / scale) / h0)
+        if d1 <= 1e-15 and d2 <= 1e-15:
+            h1 = torch.max(torch.tensor(1e-6, dtype=ydt, device=dev), h0 * 1e-3)
+        else:
+            h1 = (0.01 / max(d1, d2)) ** (1. / 5.)
+        dt = torch.min(100 * h0, h1.abs()).to(td)
+
+    def kept(times):                            # torchdiffeq keeps the times >= t[0], sorted
+        if times is None:
+            return []
+        tt = torch.as_tensor(times, dtype=td, device=dev).detach().reshape(-1)      # (a list of floats: read as float64)
+        return torch.sort(tt[tt >= t[0]]).values.tolist()
+    jumps, steps = kept(jump_t), kept(step_t)
+    both = sorted(steps + jumps)
+    if any(a == b for a, b in zip(both[:-1], both[1:])):
+        raise ValueError("`step_t` and `jump_t` must not have any repeated elements between them.")
     i_jump = min(bisect.bisect(jumps, t[0].item()), len(jumps) - 1)
+    i_step = min(bisect.bisect(steps, t[0].item()), len(steps) - 1)
     y, fy, t_lo, t_hi, dense = y0, f0, t[0], t[0], None
     for i in range(1, len(t)):
         target = t[i]
@@ -320,12 +338,20 @@ def _solve_dopri5(f, y0, t, rtol, atol, norm, jump_t=None, safety=0.9, ifactor=1
             assert n < max_num_steps, "max_num_steps exceeded"
             n += 1
             t0 = t_hi
+            if not torch.isfinite(dt):
+                dt = min_step
+            dt = dt.clamp(min_step, max_step)
             t1 = t0 + dt
-            on_jump = False
+            on_step = on_jump = False
+            if steps:
+                nxt = steps[i_step]
+                if t0.item() < nxt < (t0 + dt).item():
+                    on_step, t1 = True, as_t(nxt)
+                    dt = t1 - t0
             if jumps:
                 nxt = jumps[i_jump]
                 if t0.item() < nxt < (t0 + dt).item():
-                    on_jump, t1 = True, as_t(nxt)
+                    on_jump, on_step, t1 = True, False, as_t(nxt)
                     dt = t1 - t0
             t0y, dty, t1y = t0.to(ydt), dt.to(ydt), t1.to(ydt)
             ks = [fy]
@@ -338,8 +364,17 @@ def _solve_dopri5(f, y0, t, rtol, atol, norm, jump_t=None, safety=0.9, ifactor=1
             y1, f1 = yi, ks[-1]
             tol = atol + rtol * torch.max(y.abs(), y1.abs())
             ratio = norm(k.matmul(dty * c_err) / tol).abs()
-            if bool(ratio <= 1):
+            accept = bool(ratio <= 1)
+            if bool(dt > max_step):
+                accept = False
+            if bool(dt <= min_step):
+                accept = True
+            if record is not None:
+                record.append((t0.item(), t1.item(), float(on_jump), float(accept)))
+            if accept:
                 dense = (y, fy, y1, f1, k, dty)          # the interpolant's coefficients are formed only if it is evaluated
+                if on_step and i_step != len(steps) - 1:
+                    i_step += 1
                 if on_jump:
                     if i_jump != len(jumps) - 1:
                         i_jump += 1
@@ -352,6 +387,7 @@ def _solve_dopri5(f, y0, t, rtol, atol, norm, jump_t=None, safety=0.9, ifactor=1
             else:
                 df = torch.ones((), dtype=td, device=dev) if ratio < 1 else dfactor
                 dt = dt * torch.min(ifactor, torch.max(safety / ratio.to(td) ** 0.2, df))
+            dt = dt.clamp(min_step, max_step)
         ya, fa, yb, fb, k, dty = dense                  # the step that reached the output time: quartic dense output
         ymid = ya + k.matmul(dty * c_mid).view_as(ya)
         coeffs = (ya, dty * fa, dty * (fb - 4 * fa) - 11 * ya - 5 * yb + 16 * ymid,
@@ -377,8 +413,9 @@ def odeint(func, y0, t, *, method, options, rtol, atol):
     reverse = len(t) > 1 and bool(t[0] > t[1])
     if reverse:
         t = -t
-        if options.get("jump_t") is not None:
-            options["jump_t"] = -torch.as_tensor(options["jump_t"]).flip(0)
+        for key in ("jump_t", "step_t"):
+            if options.get(key) is not None:
+                options[key] = -torch.as_tensor(options[key]).flip(0)
     f = _Wrapped(func, shapes, reverse)
     norm = options.pop("norm", None)
     if norm is None:
@@ -395,7 +432,7 @@ def odeint(func, y0, t, *, method, options, rtol, atol):
             raise NotImplementedError("torchcde_amd: unsupported fixed-grid options %s" % sorted(options))
         sol = _solve_fixed(_FIXED[method], f, y0, t, step_size)
     elif method == "dopri5":
-        allowed = {k: options.pop(k) for k in ("jump_t", "safety", "ifactor", "dfactor", "max_num_steps") if k in options}
+        allowed = {k: options.pop(k) for k in _DOPRI5_OPTIONS if k in options}
         if any(v is not None for v in options.values()):
             raise NotImplementedError("torchcde_amd: unsupported dopri5 options %s" % sorted(options))
         sol = _solve_dopri5(f, y0, t, rtol, atol, norm, **allowed)
