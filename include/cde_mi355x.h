@@ -376,6 +376,52 @@ int cde_rk4_adjoint_mlp_sweep(const void* coeffs, const void* knots, int64_t n_i
                               size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K2m3  K2m for the three-layer vector field
+ *        f(z) = reshape_{HxC}( act( W2 hid( Wm hid(W1 z + b1) + bm ) + b2 ) )
+ * (Linear(H,width1) -> hid -> Linear(width1,width2) -> hid -> Linear(width2,H*C) -> act: the reference's example model
+ * one layer deeper); replaces the same reference code as K2 plus the user module's three nn.Linear calls per stage.
+ *   W1 (width1, H), bias1 (width1), Wm (width2, width1), biasm (width2), W2 (H*C, width2), bias2 (H*C).
+ * `act` = CDE_FIELD_ACT(final, hidden) as for K2m; the hidden activation applies after BOTH hidden layers.
+ * One tile form: f32, H <= 32, C <= 8, width1 <= 128, width2 <= 128, one wave per 16 series at every batch size;
+ * anything else CDE_ERR_UNSUPPORTED (no 16-channel layout, no shared-tile forms).  The middle layer's operands are read
+ * from Wm itself (L2): as 16-byte rows when width1 is a multiple of 4 and Wm is 16-byte aligned, element by element
+ * otherwise.  All other arguments as cde_rk4_forward_mlp.
+ * ------------------------------------------------------------------------------------------- */
+int cde_rk4_forward_mlp3(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
+                         const void* bias1, int64_t width1, const void* Wm, const void* biasm, int64_t width2,
+                         const void* W2, const void* bias2, int act, const void* z0, const void* grid, int64_t n_grid,
+                         const void* t_out, int64_t n_out, void* z_out, int64_t B, int64_t C, int64_t H, int dtype,
+                         int time_dtype, int64_t* stage_index, void* stage_frac, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K3m3  Continuous-adjoint reverse sweep for K2m3: K3m's protocol (prepare once per backward, sweep in chunks of steps,
+ * the caller reduces the streamed factor rows) with the middle layer's two factors added:
+ *     [dL/dW2 | dL/db2] = G2^T U        [dL/dWm | dL/dbm] = Gm^T U1        [dL/dW1 | dL/db1] = G1^T Z
+ *   scratch rows: row = (local_stage * B + series), local_stage = 4*(k - k_begin) + rk_stage
+ *     U1 (rows, 132) f32: hid(W1 z + b1) in columns 0..127; the CALLER sets column 128 to 1 and 129..131 to 0 once
+ *     U  (rows, 132) f32: hid(Wm u1 + bm), likewise.  With CDE_HIDDEN_SOFTPLUS the columns beyond width1 / width2 of
+ *                         both hold softplus(0) = ln 2: the caller takes the real columns of the reduced images
+ *     Gm (rows, 256) f32: quadrature-weighted dL/d(Wm u1 + bm) in columns 0..127; the CALLER zeroes the buffer once (the
+ *                         kernel never writes columns 128..255) -- the row stride of G2, so that cde_mlp_grad_reduce's
+ *                         layer = 2 form reduces Gm^T U1 unchanged (rows 0..127 of its [256][132] image)
+ *     G2, G1, Z           as K3m
+ *   cde_rk4_adjoint_mlp3_prepare   stage table of `sgrid` and the weight images (K3m's, the two middle-layer images
+ *                                  and its bias) into `workspace`
+ *   cde_rk4_adjoint_mlp3_sweep     integrates steps k_begin .. k_end-1 of `sgrid`; y_state / a_state as K3m
+ * No control-coefficient gradients (there is no `grad_coeffs`).  Envelope as K2m3; one wave per 16 series.
+ * ------------------------------------------------------------------------------------------- */
+size_t cde_rk4_adjoint_mlp3_workspace_bytes(int64_t n_sgrid);
+int cde_rk4_adjoint_mlp3_prepare(const void* knots, int64_t n_intervals, const void* sgrid, int64_t n_sgrid,
+                                 const void* W1, const void* bias1, int64_t width1, const void* Wm, const void* biasm,
+                                 int64_t width2, const void* W2, const void* bias2, int64_t C, int64_t H, int dtype,
+                                 int time_dtype, void* workspace, size_t workspace_bytes, void* stream);
+int cde_rk4_adjoint_mlp3_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
+                               void* y_state, void* a_state, const void* sgrid, int64_t n_sgrid, int64_t k_begin,
+                               int64_t k_end, void* U, void* U1, void* G2, void* Gm, void* G1, void* Z, int64_t B,
+                               int64_t C, int64_t H, int dtype, int time_dtype, const void* workspace,
+                               size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K3  Fused continuous-adjoint reverse sweep for K2.
  * Replaces torchdiffeq.odeint_adjoint's backward (behind solver.py:226): for every output
  * interval, RK4 (3/8) integration in reversed time of the augmented state (z, a_z, a_W, a_b),

@@ -622,6 +622,114 @@ def _mlp_fusable(field, H, C, z0, packed):
             and w1.size(0) <= 128 and tuple(w1.shape) == (w1.size(0), H) and tuple(w2.shape) == (H * C, w1.size(0)))
 
 
+def _mlp3_fusable(field, H, C, z0, packed):
+    """The envelope of the three-layer kernels (csrc/rk4_mlp3.hip; cde_mi355x.h: cde_rk4_forward_mlp3): float32, H <= 32,
+    C <= 8, both hidden widths <= 128 -- one tile form, no 16-channel layout."""
+    w1, wm, w2 = (lin.weight for lin in field.linears)
+    return (z0.dtype == packed.dtype == w1.dtype == wm.dtype == w2.dtype == torch.float32 and H <= 32 and C <= 8
+            and w1.size(0) <= 128 and wm.size(0) <= 128 and tuple(w1.shape) == (w1.size(0), H)
+            and tuple(wm.shape) == (wm.size(0), w1.size(0)) and tuple(w2.shape) == (H * C, wm.size(0)))
+
+
+class _Mlp3Plan(_MlpPlan):
+    """Fused RK4 solves for the three-layer field: forward (K2m3, cde_rk4_forward_mlp3) and continuous-adjoint backward (K3m3
+    sweep + three factor reductions, cde_rk4_adjoint_mlp3_*).  One wave per 16 series at every batch size."""
+
+    def _weights(self, saved=None):
+        tensors = tuple(p for lin in self.field.linears for p in (lin.weight, lin.bias)) if saved is None else saved
+        return tuple(p.detach().contiguous() for p in tensors)
+
+    @staticmethod
+    def _weight_args(weights):
+        """(W1, b1, width1, Wm, bm, width2, W2, b2) of the C ABI."""
+        w1, b1, wm, bm, w2, b2 = weights
+        return (_lib.ptr(w1), _lib.ptr(b1), w1.size(0), _lib.ptr(wm), _lib.ptr(bm), wm.size(0), _lib.ptr(w2), _lib.ptr(b2))
+
+    def run(self, z0, stages=False):
+        if stages:
+            raise NotImplementedError("torchcde_amd: the three-layer field has no reverse-mode (adjoint=False) kernels")
+        lib = _lib.load()
+        g = self.grids
+        out = torch.empty(self.B, g.n_out, self.H, dtype=torch.float32, device=self.device)
+        n_steps = max(g.grid.numel() - 1, 0)
+        stage_index = torch.empty(max(4 * n_steps, 1), dtype=torch.int64, device=self.device)
+        stage_frac = torch.empty(max(4 * n_steps, 1), dtype=torch.float32, device=self.device)
+        z0c = z0.detach().reshape(self.B, self.H).contiguous()
+        weights = self._weights()
+        _lib.check(lib.cde_rk4_forward_mlp3(
+            _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, *self._weight_args(weights), self.act,
+            _lib.ptr(z0c), _lib.ptr(g.grid), g.grid.numel(), _lib.ptr(g.t_out), g.n_out, _lib.ptr(out), self.B, self.C, self.H,
+            _lib.dtype_enum(torch.float32), _lib.dtype_enum(g.time_dtype), _lib.ptr(stage_index), _lib.ptr(stage_frac),
+            _lib.stream_ptr(self.device)), "cde_rk4_forward_mlp3")
+        return out.reshape(*self.batch, g.n_out, self.H)
+
+    def run_adjoint(self, z_saved, grad_out, w1, b1, wm, bm, w2, b2, want_control=False):
+        """As _MlpPlan.run_adjoint, with the middle layer's factors: per chunk of steps the sweep streams (U, U1, G2, Gm, G1, Z)
+        and three reductions follow -- G2^T U, Gm^T U1 (Gm padded to G2's 256 columns: the reduction's layer-2 form), G1^T Z."""
+        if want_control:
+            raise NotImplementedError("torchcde_amd: the three-layer sweep has no control gradients")
+        lib = _lib.load()
+        g = self.grids
+        B, H, C = self.B, self.H, self.C
+        dev, f32 = self.device, _lib.dtype_enum(torch.float32)
+        weights = self._weights((w1, b1, wm, bm, w2, b2))
+        width1, width2 = weights[0].size(0), weights[2].size(0)
+        nbytes = lib.cde_rk4_adjoint_mlp3_workspace_bytes(g.n_sgrid)
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        stream = _lib.stream_ptr(dev)
+        tdt = _lib.dtype_enum(g.time_dtype)
+        z_saved = z_saved.detach().reshape(B, self.n_out, H)
+        grad_out = grad_out.detach().reshape(B, self.n_out, H)
+        # the sweep integrates (y, a) IN PLACE: private copies (see _MlpPlan.run_adjoint)
+        y = z_saved[:, -1].clone(memory_format=torch.contiguous_format)
+        a = grad_out[:, -1].to(torch.float32).clone(memory_format=torch.contiguous_format)
+        acc2 = torch.zeros(256, 132, dtype=torch.float32, device=dev)
+        accm = torch.zeros(256, 132, dtype=torch.float32, device=dev)
+        acc1 = torch.zeros(128, 36, dtype=torch.float32, device=dev)
+        longest = max((g.seg_off_host[p + 1] - 1 - g.seg_off_host[p] for p in range(self.n_out - 1)), default=0)
+        if g.n_sgrid > 1 and longest > 0:
+            _lib.check(lib.cde_rk4_adjoint_mlp3_prepare(
+                _lib.ptr(self.knots), self.n_intervals, _lib.ptr(g.sgrid), g.n_sgrid, *self._weight_args(weights), C, H, f32,
+                tdt, _lib.ptr(workspace), nbytes, stream), "cde_rk4_adjoint_mlp3_prepare")
+            row_bytes = (132 + 132 + 256 + 256 + 128 + 36) * 4
+            chunk = max(1, min(longest, self.scratch_budget // (row_bytes * 4 * B)))
+            rows = chunk * 4 * B
+            U, U1 = (torch.zeros(rows, 132, dtype=torch.float32, device=dev) for _ in range(2))
+            U[:, 128] = 1
+            U1[:, 128] = 1
+            Z = torch.zeros(rows, 36, dtype=torch.float32, device=dev)
+            Z[:, 32] = 1
+            G2 = torch.empty(rows, 256, dtype=torch.float32, device=dev)
+            Gm = torch.zeros(rows, 256, dtype=torch.float32, device=dev)      # the sweep writes columns 0..127 only
+            G1 = torch.empty(rows, 128, dtype=torch.float32, device=dev)
+            reduce_ws = torch.empty(lib.cde_mlp_grad_reduce_workspace_bytes(), dtype=torch.uint8, device=dev)
+            for p in range(self.n_out - 1):
+                k, k_end = g.seg_off_host[p], g.seg_off_host[p + 1] - 1
+                while k < k_end:
+                    ke = min(k_end, k + chunk)
+                    _lib.check(lib.cde_rk4_adjoint_mlp3_sweep(
+                        _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, self.act, _lib.ptr(y),
+                        _lib.ptr(a), _lib.ptr(g.sgrid), g.n_sgrid, k, ke, _lib.ptr(U), _lib.ptr(U1), _lib.ptr(G2), _lib.ptr(Gm),
+                        _lib.ptr(G1), _lib.ptr(Z), B, C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream),
+                        "cde_rk4_adjoint_mlp3_sweep")
+                    n = 4 * (ke - k) * B
+                    for G, X, layer, acc in ((G2, U, 2, acc2), (Gm, U1, 2, accm), (G1, Z, 1, acc1)):
+                        _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G), _lib.ptr(X), n, layer, _lib.ptr(acc), _lib.ptr(reduce_ws),
+                                                           reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
+                    k = ke
+                i_out = self.n_out - 1 - p
+                y.copy_(z_saved[:, i_out - 1])                 # torchdiffeq: re-seed z from the stored forward solution
+                a.add_(grad_out[:, i_out - 1])                 # and add the incoming gradient at that output time
+        # real widths only: with softplus the padded hidden units hold softplus(0) = ln 2 in U and U1
+        g_w1, g_b1 = _mlp_gradients(acc1, acc2[None], H, C, width1)[:2]
+        g_w2, g_b2 = _mlp_gradients(acc1, acc2[None], H, C, width2)[2:]
+        g_wm, g_bm = accm[:width2, :width1].contiguous(), accm[:width2, 128].contiguous()
+        return (a.reshape(*self.batch, H), g_w1, g_b1, g_wm, g_bm, g_w2, g_b2, None)
+
+    def run_backprop(self, *args, **kwargs):
+        raise NotImplementedError("torchcde_amd: the three-layer field has no reverse-mode (adjoint=False) kernels")
+
+
 def _reaches(tensor, leaf):
     """Does the autograd graph of `tensor` reach the leaf `leaf`?  (The coefficient tensor of a control fitted with the same
     knot tensor the spline is evaluated on: test/test_tricks.py:21-49.)"""
@@ -776,6 +884,18 @@ class _FusedMlpRK4(torch.autograd.Function):
     def forward(ctx, z0, w1, b1, w2, b2, plan, wants, t, knots, *control):
         out = plan.run(z0)
         _keep(ctx, plan, wants, t, knots, control, out, w1, b1, w2, b2)
+        return out
+
+    backward = staticmethod(_adjoint_backward)
+
+
+class _FusedMlp3RK4(torch.autograd.Function):
+    """The same for the three-layer field: K2m3 forward, K3m3 backward (six parameter inputs)."""
+
+    @staticmethod
+    def forward(ctx, z0, w1, b1, wm, bm, w2, b2, plan, wants, t, knots, *control):
+        out = plan.run(z0)
+        _keep(ctx, plan, wants, t, knots, control, out, w1, b1, wm, bm, w2, b2)
         return out
 
     backward = staticmethod(_adjoint_backward)
@@ -1382,6 +1502,9 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
     mlp = None
     if field is not None and field.kind == "mlp2":
         mlp, field = (field if _mlp_fusable(field, H, C, z0, packed) else None), None
+    mlp3 = None
+    if field is not None and field.kind == "mlp3":
+        mlp3, field = (field if _mlp3_fusable(field, H, C, z0, packed) else None), None
     if field is not None:
         weight, bias = field.weight, field.bias
         if tuple(weight.shape) != (H * C, H) or not (z0.dtype == packed.dtype == weight.dtype):
@@ -1435,15 +1558,15 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
     increasing = t_is_vector and (t_host.numel() == 1 or bool((t_host[1:] > t_host[:-1]).all()))
 
     # ---- how the caller's adjoint_params relate to the field's own parameters and the control's tensors
-    known = field if field is not None else mlp
+    known = field if field is not None else mlp if mlp is not None else mlp3
     own = () if known is None else (
         (field.weight, field.bias) if field is not None else
-        (mlp.hidden.weight, mlp.hidden.bias, mlp.output.weight, mlp.output.bias))
+        tuple(p for lin in known.linears for p in (lin.weight, lin.bias)))     # two / three layers: all four / all six
     params_kind = "default"
     if given_params is not None and known is not None:
         extra = [p for p in given_params if not any(p is o for o in own)]
         extra_ok = all(isinstance(p, torch.Tensor) and p.untyped_storage().data_ptr() in control_ids for p in extra)
-        complete = field is not None or all(any(p is o for p in given_params) for o in own)    # K3m / K4am: all four or none
+        complete = field is not None or all(any(p is o for p in given_params) for o in own)    # K3m / K4am: all four or none; K3m3: all six
         params_kind = "own" if (extra_ok and complete) else "foreign"
         if field is None and any(p is X._t for p in extra) and method not in ("rk4", "dopri5"):
             params_kind = "foreign"             # knot-time gradients of a two-layer solve: under rk4 and (with the coefficient
@@ -1525,6 +1648,16 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
                              "adjoint_params"}
     if unknown:
         raise NotImplementedError("torchcde_amd: unsupported cdeint keyword arguments {}".format(sorted(unknown)))
+
+    # ---- three-layer fields (rk4 only: forward, and the continuous adjoint for z0 and the six parameters)
+    if mlp3 is not None:
+        step = _parse_fixed_options(fused_options, "solver")
+        if choice.path == "mlp_rk4_forward":
+            with torch.no_grad():
+                return _Mlp3Plan(X, mlp3, batch, H, C, t, step).run(z0)
+        adj_step = step if fused_adj_opts is None else _parse_fixed_options(fused_adj_opts, "adjoint")
+        plan = _Mlp3Plan(X, mlp3, batch, H, C, t, step, adj_step)
+        return _FusedMlp3RK4.apply(z0, *(p for lin in mlp3.linears for p in (lin.weight, lin.bias)), plan, None, None, None)
 
     # ---- two-layer fields
     if choice.path == "mlp_rk4_adjoint":

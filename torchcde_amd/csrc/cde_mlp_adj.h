@@ -463,6 +463,35 @@ __device__ __forceinline__ void mlp_adjoint_eval_split8(const float* lds_base, f
 #undef CDE_EVAL_STAMP
 }
 
+// value of the sweeps' image [W1 image | b1 | W2 plain | b2 | W1^T image] at flat index e (rk4_mlp_adjoint.hip's header: the
+// permuted rows of the plain W2 copy); rk4_mlp3.hip builds the same parts for its own widths
+__device__ __forceinline__ float mlp_adj_image(const float* __restrict__ W1, const float* __restrict__ b1,
+                                               const float* __restrict__ W2, const float* __restrict__ b2, int e,
+                                               MlpDims d, int nb) {
+  if (e < W1M_FLOATS + B1M_FLOATS) return mlp16_image(W1, b1, W2, b2, e, d, nb);    // same layer-1 image as K2m
+  e -= W1M_FLOATS + B1M_FLOATS;
+  if (e < W2P_FLOATS) {
+    const int pr = e / W2P_STRIDE, col = e - pr * W2P_STRIDE;
+    const int r8 = pr & 7, hi = pr >> 3, hb = hi & 1, T = hi >> 1, tb = T % nb, P = T / nb;   // tile T = nb*P + tb
+    // invert w2p_residue: r8 = (2*(h&3) + g(c&3)) % 8 with (h&3)>>1 == hb
+    int h3 = 0, c3 = 0;
+    for (int hh = 2 * hb; hh < 2 * hb + 2; ++hh)
+      for (int cc = 0; cc < 4; ++cc)
+        if (w2p_residue(hh, cc) == r8) { h3 = hh; c3 = cc; }
+    const int h = 4 * P + h3, c = 4 * tb + c3;
+    return (col < d.width && h < d.H && c < d.C) ? W2[(h * d.C + c) * d.width + col] : 0.f;
+  }
+  e -= W2P_FLOATS;
+  if (e < BY_FLOATS) return by16_image(b2, e >> 4, (e >> 2) & 3, e & 3, Dims{d.H, d.C}, nb);
+  e -= BY_FLOATS;
+  // va tile T (row i <-> z unit 4*(4T + (i&3)) + (i>>2), so register r of lane (n, q) is unit 4*(4T+r) + q),
+  // K step (T1, r = j): lane quarter kq feeds hidden-layer unit 16*T1 + 4*kq + j
+  const int j = e & 3, l = (e >> 2) & 63, i = l & 15, kq = l >> 4;
+  const int g = (e >> 8), T = g >> 3, T1 = g & 7;
+  const int unit = 16 * T1 + 4 * kq + j, k = 4 * (4 * T + (i & 3)) + (i >> 2);
+  return (unit < d.width && k < d.H) ? W1[unit * d.H + k] : 0.f;
+}
+
 // host side of the images (rk4_mlp_adjoint.hip).  `b1_pad`: the bias of the hidden-layer units beyond `width` -- relu(0) = 0
 // keeps them out of every product, softplus(0) = ln 2 would put them into the U rows (harmless for the weights, whose columns
 // beyond `width` are zero, but K4am's error norm runs over the whole gradient image): K4am pads with SOFTPLUS_PAD_BIAS there,

@@ -15,7 +15,8 @@ import warnings
 # what cdeint knows about a call once the compatibility probe has run
 Request = collections.namedtuple("Request", [
     "prod",              # func.prod exists (solver.py:48-53): the module multiplies by dX itself
-    "kind",              # None: unrecognised module; "affine": act(Linear(z)); "mlp2": act(Linear(relu(Linear(z))))
+    "kind",              # None: unrecognised module; "affine": act(Linear(z)); "mlp2": act(Linear(relu(Linear(z))));
+                         # "mlp3": act(Linear(hid(Linear(hid(Linear(z)))))) -- fused under rk4 only (K2m3 / K3m3)
     "tiles_ok",          # the field's shape / dtype fit some fused kernel (cde_rk4_supported; _mlp_fusable)
     "mfma_shape",        # affine field on the 32 x 8 MFMA tiles (float32, H <= 32, C <= 8, variant != "generic")
     "method",            # "rk4" | "dopri5" | any other torchdiffeq method name
@@ -59,8 +60,8 @@ FUSED_PATHS = (
     "rk4",                    # K2 / K3 (+ split, wide, generic variants behind CDE_VARIANT_AUTO), incl. time / control gradients
     "dopri5_forward",         # K4 (MFMA, wide or generic attempt kernel), nothing to differentiate
     "dopri5_adjoint",         # K4 + K4a: the reference's default training call
-    "mlp_rk4_forward",        # K2m
-    "mlp_rk4_adjoint",        # K2m + K3m + factor reduction (optionally with control gradients)
+    "mlp_rk4_forward",        # K2m (three-layer field: K2m3)
+    "mlp_rk4_adjoint",        # K2m + K3m + factor reduction (optionally with control gradients); three-layer field: K2m3 + K3m3
     "mlp_dopri5_forward",     # K4 with the two-layer field
     "mlp_dopri5_adjoint",     # K4 + K4am: the reference examples' training call with their own model
     "rk4_backprop",           # adjoint=False: K2 storing its stage states + K3d, reverse mode through the solver's steps
@@ -84,6 +85,17 @@ def select_path(q):
         return _stepwise("the field's shape or dtype is beyond the fused kernels' tiles")
     if not q.t_ok:
         return _stepwise("the output times are not strictly increasing")
+    if q.kind == "mlp3":
+        # Linear -> hid -> Linear -> hid -> Linear -> act: K2m3 / K3m3 (csrc/rk4_mlp3.hip) under rk4, nothing else
+        if q.method == "rk4" and not q.variant_generic and q.options_ok:
+            if not q.wants_grad:
+                return Choice("mlp_rk4_forward", "")
+            if (q.adjoint and q.adjoint_method_ok and q.adjoint_options_ok and q.params != "foreign" and not q.wants_t
+                    and not q.wants_control):
+                return Choice("mlp_rk4_adjoint", "")
+        return _stepwise(("variant='generic' was requested (the step-wise reference path); " if q.variant_generic else "") +
+                         "the three-layer field is fused under method='rk4' only: forward, and adjoint=True for z0 and all six "
+                         "parameters (step_size options, no time / control gradients)")
     if q.method in ("midpoint", "euler"):
         # torchdiffeq's other fixed-grid methods (reference test/test_cdeint.py:49-63): K2 / K3p with two stages / one per step
         grads_ok = not q.wants_grad or (q.adjoint and q.adjoint_method_ok and q.adjoint_options_ok and q.params != "foreign")

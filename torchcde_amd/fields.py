@@ -1,13 +1,16 @@
 """Vector-field recognition for the fused solvers.
 
 ``cdeint`` accepts an arbitrary callable ``func(t, z) -> (..., H, C)`` (reference solver.py:159-165).
-The fused kernels implement two families:
+The fused kernels implement three families:
         f(t, z) = act( Linear(H, H*C)(z) ) viewed as (..., H, C),      act in {identity, tanh}
 i.e. the README field (reference README.md:42-49) and ``example/irregular_data.py:36-46``, and
         f(t, z) = act( Linear(W, H*C)( hidden( Linear(H, W)(z) ) ) ) viewed as (..., H, C),   hidden in {relu, softplus}
 i.e. ``example/time_series_classification.py:20-51`` and its smooth variant with ``torch.nn.functional.softplus`` (torch's
-defaults only: beta 1, threshold 20; any other beta / threshold is refused) in place of the relu.  A module is recognised by
-*probing*, not by tracing source: it must own exactly one (two) nn.Linear and no other parameter; during
+defaults only: beta 1, threshold 20; any other beta / threshold is refused) in place of the relu, and
+        f(t, z) = act( Linear(W2, H*C)( hidden( Linear(W1, W2)( hidden( Linear(H, W1)(z) ) ) ) ) ) viewed as (..., H, C)
+with the SAME hidden activation after both hidden layers (kind "mlp3": fused under rk4 -- forward and adjoint=True -- and solved
+step by step in closed form everywhere else).  A module is recognised by
+*probing*, not by tracing source: it must own exactly one (two, three) nn.Linear and no other parameter; during
 the compatibility evaluation ``func(t[0], z0)`` that the reference performs anyway, forward hooks record
 the Linears' inputs and outputs, and the module's result must be BITWISE equal to the family's formula
 applied to those recordings -- view/reshape never change values, so any other arithmetic (scaling, skip
@@ -77,6 +80,31 @@ class MLPField:
         return self.output.bias
 
 
+class MLP3Field:
+    """Linear -> hid -> Linear -> hid -> Linear -> act with one hidden activation hid = relu | softplus for both hidden layers:
+    (first, middle, output Linear, final activation enum, hidden activation enum)."""
+    kind = "mlp3"
+
+    def __init__(self, hidden, middle, output, act, hidden_act=_lib.HIDDEN_RELU):
+        self.hidden, self.middle, self.output = hidden, middle, output
+        self.linears = (hidden, middle, output)
+        self.act = act
+        self.hidden_act = hidden_act
+        self.shapes = {}
+
+    @property
+    def code(self):              # the `int act` of the three-layer entry points: CDE_FIELD_ACT(final, hidden), as MLPField's
+        return _lib.field_act(self.act, self.hidden_act)
+
+    @property
+    def weight(self):
+        return self.output.weight
+
+    @property
+    def bias(self):
+        return self.output.bias
+
+
 class LinearCDEFunc(torch.nn.Module):
     """Ready-made member of the fused family: ``Linear(H, H*C)`` (+ optional tanh) viewed (..., H, C)."""
 
@@ -137,13 +165,13 @@ def _fingerprint(func):
 
 
 def _linears(func):
-    """The module's nn.Linear layers if they hold ALL of its parameters (1 or 2 layers, with bias), else None."""
+    """The module's nn.Linear layers if they hold ALL of its parameters (1 to 3 layers, with bias), else None."""
     if isinstance(func, LinearCDEFunc):
         return (func.linear,)
     if not isinstance(func, torch.nn.Module):
         return None
     linears = tuple(m for m in func.modules() if isinstance(m, torch.nn.Linear))
-    if len(linears) not in (1, 2) or any(m.bias is None for m in linears) or len({id(m) for m in linears}) != len(linears):
+    if len(linears) not in (1, 2, 3) or any(m.bias is None for m in linears) or len({id(m) for m in linears}) != len(linears):
         return None
     own = {id(p) for m in linears for p in m.parameters()}
     if any(id(p) not in own for p in func.parameters()):
@@ -190,10 +218,10 @@ def _hidden_activation(hidden_in, first_out):
 
 
 def _classify(system, calls, z):
-    """(kind, act, ordered layers) -- act = (final, hidden) for the two-layer family -- if ``system`` is exactly one of the fused formulas applied to the recorded layer
+    """(kind, act, ordered layers) -- act = (final, hidden) for the two- and three-layer families -- if ``system`` is exactly one of the fused formulas applied to the recorded layer
     inputs/outputs, else None (bitwise comparison: view/reshape never change values, so any other arithmetic in
     ``func`` is detected)."""
-    if not isinstance(system, torch.Tensor) or len(calls) not in (1, 2):
+    if not isinstance(system, torch.Tensor) or len(calls) not in (1, 2, 3):
         return None
     first, seen_input, first_out = calls[0]
     if seen_input.shape != z.shape or not torch.equal(seen_input, z):
@@ -205,6 +233,13 @@ def _classify(system, calls, z):
     hidden = None if second is first else _hidden_activation(hidden_in, first_out)
     if hidden is None:
         return None
+    if len(calls) == 3:
+        # the same hidden activation once more, on a third layer that is neither of the other two
+        third, hidden_in2, third_out = calls[2]
+        if third is first or third is second or _hidden_activation(hidden_in2, second_out) != hidden:
+            return None
+        act = _final_activation(system, third_out)
+        return None if act is None else ("mlp3", (act, hidden), (first, second, third))
     act = _final_activation(system, second_out)
     return None if act is None else ("mlp2", (act, hidden), (first, second))
 
@@ -244,13 +279,14 @@ def probe(func, t0, z0):
     system3, calls3, foreign3 = _evaluate_recording(func, linears, t0, far)
     if foreign3 or _classify(system3, calls3, far) != found:
         return None, system
-    if kind == "mlp2":
+    if kind in ("mlp2", "mlp3"):
         act, hidden = act
     else:
         hidden = None
     if (known is None or known.kind != kind or known.act != act or getattr(known, "hidden_act", None) != hidden
             or known.linears != ordered):
-        known = AffineField(ordered[0], act) if kind == "affine" else MLPField(ordered[0], ordered[1], act, hidden)
+        known = (AffineField(ordered[0], act) if kind == "affine" else MLPField(ordered[0], ordered[1], act, hidden)
+                 if kind == "mlp2" else MLP3Field(ordered[0], ordered[1], ordered[2], act, hidden))
         try:
             _verified[func] = known
         except TypeError:

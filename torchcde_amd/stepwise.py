@@ -92,7 +92,8 @@ class ForeignControlField(ControlledField):
 
 def _explicit_dynamics(field, params):
     """The augmented dynamics of the continuous adjoint in closed form for a RECOGNISED vector field (fields.py: the
-    probe established bitwise that func is act(Linear(z)) or act(Linear(relu | softplus (Linear(z)))) viewed (..., H, C)):
+    probe established bitwise that func is act(Linear(z)), act(Linear(hid(Linear(z)))) or act(Linear(hid(Linear(hid(Linear(z))))))
+    with hid = relu | softplus, viewed (..., H, C)):
     (t, y, a) -> (f, -a^T df/dy, [-a^T df/dp for p in params]) with a dozen matrix / elementwise launches instead of an
     autograd graph of about forty per evaluation -- the step-wise adaptive backward of the reference's example models
     (two-layer field, default dopri5 + adjoint call) is bound by launches, not by arithmetic.  Returns None when a
@@ -111,9 +112,10 @@ def _explicit_dynamics(field, params):
             return None
         slots.append(where[0])
     tanh = rec.act == _lib.ACT_TANH
-    two = len(layers) == 2
-    softplus = two and rec.hidden_act == _lib.HIDDEN_SOFTPLUS
+    hidden_layers = layers[:-1]                  # none (affine), one (two-layer field) or two (three-layer field)
+    softplus = bool(hidden_layers) and rec.hidden_act == _lib.HIDDEN_SOFTPLUS
     out_layer = layers[-1]
+    last = len(layers) - 1
 
     def run(tt, yy, aa):
         H = yy.size(-1)
@@ -121,12 +123,14 @@ def _explicit_dynamics(field, params):
         dX = field.X.derivative(tt)
         C = dX.size(-1)
         dX = dX.reshape(-1, C)
-        if two:
-            w1, b1 = layers[0].weight, layers[0].bias
-            h1 = z @ w1.t() if b1 is None else torch.addmm(b1, z, w1.t())
+        r = z
+        inputs, pres = [], []                    # per hidden layer: what it was applied to, its pre-activation
+        for lin in hidden_layers:
+            w1, b1 = lin.weight, lin.bias
+            h1 = r @ w1.t() if b1 is None else torch.addmm(b1, r, w1.t())
+            inputs.append(r)
+            pres.append(h1)
             r = torch.nn.functional.softplus(h1) if softplus else h1.relu()
-        else:
-            r = z
         w, b = out_layer.weight, out_layer.bias
         u = r @ w.t() if b is None else torch.addmm(b, r, w.t())
         th = u.tanh() if tanh else u
@@ -136,19 +140,19 @@ def _explicit_dynamics(field, params):
             gu = torch.addcmul(gu, gu * th, th, value=-1)                             # * (1 - tanh^2)
         grads = {}
         need = set(slots)
-        if (len(layers) - 1, "weight") in need:
-            grads[(len(layers) - 1, "weight")] = gu.t() @ r
-        if (len(layers) - 1, "bias") in need:
-            grads[(len(layers) - 1, "bias")] = gu.sum(0)
-        if two:
-            gh1 = (gu @ w) * (torch.sigmoid(h1).masked_fill(h1 > 20, 1.0) if softplus else (h1 > 0))   # softplus' = sigmoid; torch: 1 above its threshold
-            if (0, "weight") in need:
-                grads[(0, "weight")] = gh1.t() @ z
-            if (0, "bias") in need:
-                grads[(0, "bias")] = gh1.sum(0)
-            vy = gh1 @ layers[0].weight
-        else:
-            vy = gu @ w
+        if (last, "weight") in need:
+            grads[(last, "weight")] = gu.t() @ r
+        if (last, "bias") in need:
+            grads[(last, "bias")] = gu.sum(0)
+        vy = gu @ w
+        for i in range(len(hidden_layers) - 1, -1, -1):                               # back through the hidden layers
+            h1 = pres[i]
+            gh1 = vy * (torch.sigmoid(h1).masked_fill(h1 > 20, 1.0) if softplus else (h1 > 0))   # softplus' = sigmoid; torch: 1 above its threshold
+            if (i, "weight") in need:
+                grads[(i, "weight")] = gh1.t() @ inputs[i]
+            if (i, "bias") in need:
+                grads[(i, "bias")] = gh1.sum(0)
+            vy = gh1 @ hidden_layers[i].weight
         return fe.reshape(yy.shape), vy.reshape(yy.shape), [grads[slot].reshape(p.shape) for slot, p in zip(slots, params)]
 
     return run
