@@ -496,6 +496,42 @@ int cde_fixed_adjoint_linear(int method, const void* coeffs, const void* knots, 
                              size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The reversible Heun method (arXiv 2105.13493, Algorithms 1 and 2): cdeint(..., backend="torchsde",
+ * method="reversible_heun") for the one-layer fields, f32, H <= 32, C <= 8, act CDE_ACT_NONE / CDE_ACT_TANH, cubic and
+ * linear controls, f32 / f64 times (cde_revheun_supported; otherwise CDE_ERR_UNSUPPORTED and the Python host steps the
+ * solve itself).  csrc/revheun.hip.  State (y, zh, f), zh_0 = y_0 = z0, f_0 = F(t_0, z0), and per step of
+ * dt = float32(grid[k+1] - grid[k]):   zh' = 2 y - zh + f dt;   f' = F(t_{k+1}, zh');   y' = y + (f + f') dt/2.
+ *   cde_revheun_forward_linear   the arguments of cde_rk4_forward_linear without `variant`, plus
+ *       zhat_out (B, H)          zh at the last grid node (the backward pass starts from z_out[:, -1] and this)
+ *       node_index / node_frac   n_grid int64 / n_grid f32 of device scratch: the control interval and fractional part at
+ *                                every grid node (one slot per NODE, not four per step)
+ *   cde_revheun_adjoint_linear   the exact gradient of the discrete solve, from (y_final, zhat_final) alone: walks the nodes
+ *       backwards, rebuilds the state and differentiates the steps (one field evaluation + one vector-Jacobian product per
+ *       node, n_grid of them):
+ *         y_final, zhat_final (B, H)   y and zh at the last grid node
+ *         grad_out (B, n_out, H)       dL/dz_out
+ *         grid (n_grid)                the FORWARD grid (time dtype)
+ *         node_ptr (n_grid + 1) int64, node_out / node_weight: the CSR lists of cde_rk4_backprop_linear (n_steps = n_grid - 1)
+ *         grad_z0 (B, H), grad_W (H*C, H), grad_b (H*C)   out
+ *         workspace   cde_revheun_adjoint_workspace_bytes(B, n_grid) bytes: the node table and the per-wave partial
+ *                     parameter gradients, reduced in a fixed order (deterministic)
+ * Checks, in this order and before the first HIP call: sizes (CDE_ERR_SHAPE), unknown dtype (CDE_ERR_DTYPE), the forward
+ * solve's empty batch (CDE_OK), the envelope (CDE_ERR_UNSUPPORTED), NULL pointers, the workspace size.
+ * ------------------------------------------------------------------------------------------- */
+int cde_revheun_supported(int64_t C, int64_t H, int dtype, int act);
+int cde_revheun_forward_linear(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
+                               const void* bias, int act, const void* z0, const void* grid, int64_t n_grid,
+                               const void* t_out, int64_t n_out, void* z_out, void* zhat_out, int64_t B, int64_t C,
+                               int64_t H, int dtype, int time_dtype, int64_t* node_index, void* node_frac, void* stream);
+size_t cde_revheun_adjoint_workspace_bytes(int64_t B, int64_t n_grid);
+int cde_revheun_adjoint_linear(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W,
+                               const void* bias, int act, const void* y_final, const void* zhat_final,
+                               const void* grad_out, const void* grid, int64_t n_grid, const int64_t* node_ptr,
+                               const int64_t* node_out, const float* node_weight, int64_t n_out, void* grad_z0,
+                               void* grad_W, void* grad_b, int64_t B, int64_t C, int64_t H, int dtype, int time_dtype,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K3d  The backward pass of cdeint(..., method='rk4', adjoint=False) for the affine field (reference solver.py:144,
  * 226-227: torchdiffeq.odeint differentiated by autograd through the solver's own operations -- the EXACT gradient of
  * the discrete 3/8-rule map, README.md:103; not the continuous adjoint of K3).  Two calls:

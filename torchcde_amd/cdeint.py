@@ -14,6 +14,8 @@ Native scope (round 1):
     (``adjoint=True``) for z0 and the field's weight / bias
   * ``method='dopri5'`` (also the default when no method is passed, as in the reference): adaptive solve with
     torchdiffeq's batch-global controller, ``rtol/atol`` and ``options={'jump_t': ...}``; fused forward
+  * backend "torchsde": ``method='reversible_heun'`` (arXiv 2105.13493; fused for the affine family in float32, csrc/revheun.hip,
+    step-wise otherwise) and ``method='midpoint'`` (rewritten as the torchdiffeq request with ``step_size=dt``)
   * everything else -- arbitrary ``func`` modules (MLPs ...), ``midpoint``/``euler``, ``adjoint=False`` backprop,
     gradients through ``dopri5`` -- runs step-wise (``torchcde_amd/stepwise.py``): host-driven stepping on the GPU
     with the native control-derivative and contraction kernels under every vector-field evaluation
@@ -1312,6 +1314,199 @@ class _FusedMlpDopri5(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------ front end
+# ------------------------------------------------------------------------------------------ backend="torchsde"
+_TORCHSDE_DT = 1e-3              # torchsde.sdeint's default step (from memory: DESIGN.md section 8 lists it as unchecked)
+_TORCHSDE_KEYS = {"method", "dt", "adjoint_method", "adjoint_params", "rtol", "atol", "adjoint_rtol", "adjoint_atol",
+                  "adaptive", "adjoint_adaptive", "options", "adjoint_options"}
+
+
+def _parse_torchsde(kwargs, adjoint):
+    """The keywords of cdeint(..., backend="torchsde") (reference solver.py:171-176, :228-230 forwards them to
+    torchsde.sdeint[_adjoint]).  Returns (kwargs, revheun): method="reversible_heun" -> revheun = {dt, adjoint_params} for
+    this package's reversible Heun solver; method="midpoint" -> revheun None and `kwargs` rewritten as the torchdiffeq
+    request with the same step (the reference's own test equates the two, test/test_cdeint.py:49-63).  Anything else --
+    Brownian motion, names, logqp, extra solver state, dt_min, adaptive stepping, another method -- raises
+    NotImplementedError naming the key or method."""
+    method = kwargs.get("method")
+    if method not in ("reversible_heun", "midpoint"):
+        raise NotImplementedError("torchcde_amd: backend='torchsde' is implemented for method='reversible_heun' and "
+                                  "method='midpoint', not for method=%r." % (method,))
+    unknown = sorted(set(kwargs) - _TORCHSDE_KEYS)
+    if unknown:
+        raise NotImplementedError("torchcde_amd: backend='torchsde' does not take the keyword argument(s) %s (accepted: %s)."
+                                  % (", ".join(repr(k) for k in unknown), ", ".join(sorted(_TORCHSDE_KEYS))))
+    for key in ("adaptive", "adjoint_adaptive"):
+        if kwargs.get(key):
+            raise NotImplementedError("torchcde_amd: backend='torchsde' takes fixed steps only: %s=%r is not implemented."
+                                      % (key, kwargs[key]))
+    for key in ("options", "adjoint_options"):
+        if kwargs.get(key):
+            raise NotImplementedError("torchcde_amd: backend='torchsde' takes no %s (got %r)." % (key, kwargs[key]))
+    dt = kwargs.get("dt")
+    dt = _TORCHSDE_DT if dt is None else dt
+    adjoint_method = kwargs.get("adjoint_method")
+    expected = "adjoint_reversible_heun" if method == "reversible_heun" else "midpoint"
+    if adjoint_method not in (None, expected):
+        raise NotImplementedError("torchcde_amd: backend='torchsde', method=%r is differentiated with adjoint_method=%r, "
+                                  "not adjoint_method=%r." % (method, expected, adjoint_method))
+    given = kwargs.get("adjoint_params")
+    if method == "reversible_heun":
+        return kwargs, {"dt": dt, "adjoint_params": None if given is None else tuple(given)}
+    out = {k: kwargs[k] for k in ("rtol", "atol", "adjoint_rtol", "adjoint_atol", "adjoint_params") if k in kwargs}
+    out.update(method="midpoint", options={"step_size": dt})
+    if adjoint:
+        out["adjoint_method"] = "midpoint"
+    return out, None
+
+
+def _no_time_gradient(t):
+    if torch.is_grad_enabled() and isinstance(t, torch.Tensor) and t.requires_grad:
+        raise NotImplementedError("torchcde_amd: method='reversible_heun' does not differentiate with respect to the times t.")
+
+
+def _revheun_through(X, func, adjoint):
+    """adjoint=False asks for the gradient autograd would find through the solver's steps: the reconstructing backward gives
+    it for z0 and func's parameters; a control tensor that requires a gradient, or a func that is no module, is
+    differentiated by autograd through the host-driven steps themselves."""
+    if adjoint or not torch.is_grad_enabled():
+        return False
+    return not isinstance(func, torch.nn.Module) or any(b.requires_grad for b in X.buffers())
+
+
+class _ReversibleHeunPlan(_Plan):
+    """The fused reversible Heun solve: RHf forward, RHa backward (csrc/revheun.hip)."""
+
+    def __init__(self, path, field, batch, H, C, t, dt, adjoint):
+        super().__init__(path, field, batch, H, C, t, dt, None, adjoint, _lib.VARIANT_AUTO)
+
+    def _head(self, weight, bias):
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        return (w, b), (_lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, _lib.ptr(w), _lib.ptr(b),
+                        self.act)
+
+    def run_forward(self, z0, weight, bias):
+        lib = _lib.load()
+        n_grid = self.grid.numel()
+        out = torch.empty(self.B, self.n_out, self.H, dtype=self.dtype, device=self.device)
+        zhat = torch.empty(self.B, self.H, dtype=self.dtype, device=self.device)
+        node_index = torch.empty(n_grid, dtype=torch.int64, device=self.device)
+        node_frac = torch.empty(n_grid, dtype=self.dtype, device=self.device)
+        z0c = z0.detach().reshape(self.B, self.H).contiguous()
+        keep, head = self._head(weight, bias)
+        begin = self._mark()
+        _lib.check(lib.cde_revheun_forward_linear(
+            *head, _lib.ptr(z0c), _lib.ptr(self.grid), n_grid, _lib.ptr(self.t_out), self.n_out, _lib.ptr(out), _lib.ptr(zhat),
+            self.B, self.C, self.H, _lib.dtype_enum(self.dtype), _lib.dtype_enum(self.time_dtype), _lib.ptr(node_index),
+            _lib.ptr(node_frac), _lib.stream_ptr(self.device)), "cde_revheun_forward_linear")
+        self._log("forward", begin)
+        return out, zhat
+
+    def run_adjoint(self, y_final, zhat_final, grad_out, weight, bias):
+        lib = _lib.load()
+        _, node_ptr, node_out, node_weight, _ = self.grids.backprop_lists()
+        n_grid = self.grid.numel()
+        nbytes = lib.cde_revheun_adjoint_workspace_bytes(self.B, n_grid)
+        workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+        grad_z0 = torch.empty(self.B, self.H, dtype=self.dtype, device=self.device)
+        grad_w, grad_b = self._parameter_gradients()
+        go = grad_out.detach().reshape(self.B, self.n_out, self.H).contiguous()
+        keep, head = self._head(weight, bias)
+        begin = self._mark()
+        _lib.check(lib.cde_revheun_adjoint_linear(
+            *head, _lib.ptr(y_final), _lib.ptr(zhat_final), _lib.ptr(go), _lib.ptr(self.grid), n_grid, _lib.ptr(node_ptr),
+            _lib.ptr(node_out), _lib.ptr(node_weight), self.n_out, _lib.ptr(grad_z0), _lib.ptr(grad_w), _lib.ptr(grad_b),
+            self.B, self.C, self.H, _lib.dtype_enum(self.dtype), _lib.dtype_enum(self.time_dtype), _lib.ptr(workspace),
+            workspace.numel(), _lib.stream_ptr(self.device)), "cde_revheun_adjoint_linear")
+        self._log("adjoint", begin)
+        return grad_z0, grad_w, grad_b
+
+
+class _FusedReversibleHeun(torch.autograd.Function):
+    """cdeint(..., backend="torchsde", method="reversible_heun") for the affine field: the forward kernel keeps nothing but
+    the final (y, zh); the backward kernel rebuilds the trajectory from them and returns the exact gradient of the discrete
+    solve -- what adjoint=True (torchsde's adjoint_reversible_heun) and adjoint=False (autograd through the steps) both ask
+    for, so both take this sweep."""
+
+    @staticmethod
+    def forward(ctx, z0, weight, bias, plan, wants):
+        out, zhat = plan.run_forward(z0, weight, bias)
+        ctx.plan, ctx.wants = plan, wants
+        ctx.save_for_backward(out[:, -1].contiguous(), zhat, weight, bias)
+        return out.reshape(*plan.batch, plan.n_out, plan.H)
+
+    @staticmethod
+    @_once_differentiable
+    def backward(ctx, grad_out):
+        plan, need, wants = ctx.plan, ctx.needs_input_grad, ctx.wants
+        y_final, zhat, weight, bias = ctx.saved_tensors
+        grad_z0, grad_w, grad_b = plan.run_adjoint(y_final, zhat, grad_out, weight, bias)
+        return (grad_z0.reshape(*plan.batch, plan.H) if need[0] else None, grad_w if need[1] and wants[0] else None,
+                grad_b if need[2] and wants[1] else None, None, None)
+
+
+def _cdeint_reversible_heun(X, func, z0, t, adjoint, revheun, variant, field, recognised, recognised_kind, batch, H, C):
+    """method="reversible_heun" once the compatibility probe has run: the fused plan when the probe found the affine field on
+    the kernels' tiles, t is strictly increasing and nothing but z0, W, b wants a gradient; the step-wise solve otherwise."""
+    _no_time_gradient(t)
+    dt, given = revheun["dt"], revheun["adjoint_params"]
+    grad_mode = torch.is_grad_enabled()
+    t_is_vector = isinstance(t, torch.Tensor) and t.dim() == 1 and t.is_floating_point() and t.numel() >= 1
+    t_host = _to_host(t) if t_is_vector else None
+    increasing = t_is_vector and (t_host.numel() == 1 or bool((t_host[1:] > t_host[:-1]).all()))
+    if not t_is_vector:
+        raise ValueError("t must be a one dimensional floating point tensor.")
+    control_wants = grad_mode and not adjoint and any(b.requires_grad for b in X.buffers())
+    foreign = []
+    if field is not None and adjoint and given is not None:
+        foreign = [p for p in given if isinstance(p, torch.Tensor) and p.requires_grad
+                   and p is not field.weight and p is not field.bias]
+    if adjoint and given is None:
+        for buffer in X.buffers():
+            if buffer.requires_grad:
+                warnings.warn(_GRAD_WARNING)
+    reason = ""
+    if field is None:
+        reason = ("the vector field is not of a recognised form (arbitrary module)" if recognised_kind is None else
+                  "reversible Heun is fused for the one-layer fields on the 32 x 8 tiles (float32, H <= 32, C <= 8)")
+    elif not _lib.load().cde_revheun_supported(C, H, _lib.dtype_enum(z0.dtype), field.act):
+        reason = "reversible Heun is fused for the one-layer fields on the 32 x 8 tiles (float32, H <= 32, C <= 8)"
+    elif variant == _lib.VARIANT_GENERIC:
+        reason = "variant='generic' was requested (the step-wise reference path)"
+    elif not increasing:
+        reason = "the output times are not strictly increasing"
+    elif foreign:
+        reason = "adjoint_params holds tensors other than the field's weight and bias"
+    elif control_wants:
+        reason = "adjoint=False with control tensors that require a gradient"
+    params = given if (adjoint and given is not None) else (tuple(func.parameters()) if isinstance(func, torch.nn.Module) else ())
+    wants_grad = grad_mode and (z0.requires_grad or control_wants
+                                or any(isinstance(p, torch.Tensor) and p.requires_grad for p in params))
+    request = dispatch.Request(
+        prod=False, kind=recognised_kind, tiles_ok=field is not None, mfma_shape=field is not None and not reason,
+        method="reversible_heun", adjoint=bool(adjoint), wants_grad=bool(wants_grad), wants_t=False,
+        wants_control=bool(control_wants or foreign), params="default" if given is None else
+        ("foreign" if foreign else "own"), adjoint_method_ok=True, options_ok=True, adjoint_options_ok=True,
+        t_ok=bool(increasing), variant_generic=variant == _lib.VARIANT_GENERIC, shared=False, narrow_control=C <= 8,
+        backprop_ok=field is not None and not reason, identity=bool(field is not None and field.act == _lib.ACT_NONE),
+        control_block=False)
+    choice = dispatch.Choice(dispatch.TORCHSDE_PATHS[1] if reason else dispatch.TORCHSDE_PATHS[0], reason)
+    dispatch.record(choice, request)
+    if reason:
+        from . import stepwise
+        dispatch.warn_once(func, choice, request)
+        return stepwise.solve_reversible_heun(X, func, z0, t, dt, adjoint, given, recognised=recognised,
+                                              through=_revheun_through(X, func, adjoint))
+    weight, bias = field.weight, field.bias
+    plan = _ReversibleHeunPlan(X, field, batch, H, C, t, dt, adjoint)
+    if not wants_grad:
+        with torch.no_grad():
+            return plan.run_forward(z0, weight, bias)[0].reshape(*batch, plan.n_out, H)
+    wants = (True, True)
+    if adjoint and given is not None:
+        wants = (any(p is weight for p in given), any(p is bias for p in given))
+    return _FusedReversibleHeun.apply(z0, weight, bias, plan, wants)
+
+
 def _shape_errors(dX_shape, system_shape, z0):
     # messages of reference solver.py:7-33
     if tuple(dX_shape[:-1]) != tuple(z0.shape[:-1]):
@@ -1339,9 +1534,10 @@ def _shape_errors(dX_shape, system_shape, z0):
 def _cdeint_tuple(X, func, z0, t, adjoint, backend, kwargs):
     """Tuple-valued state (reference solver.py:68-95): checks and messages as the reference, then the step-wise solver
     on the concatenated state (what torchdiffeq does with tuples); returns a tuple of (..., len(t), H_i) tensors."""
+    revheun = None
     if backend == "torchsde":
-        raise NotImplementedError("torchcde_amd: the torchsde backend is outside the native hot path.")
-    if backend != "torchdiffeq":
+        kwargs, revheun = _parse_torchsde(kwargs, adjoint)
+    elif backend != "torchdiffeq":
         raise ValueError(f"Unrecognised backend={backend}")
     for part in z0:
         if not isinstance(part, torch.Tensor):
@@ -1385,13 +1581,20 @@ def _cdeint_tuple(X, func, z0, t, adjoint, backend, kwargs):
         kw.setdefault("adjoint_rtol", kw["rtol"])
     sizes = [part.size(-1) for part in z0]
     field = stepwise.TupleField(X, func, sizes)
+    if revheun is not None:
+        _no_time_gradient(t)
+        dispatch.record(dispatch.Choice(dispatch.TORCHSDE_PATHS[1], "tuple-valued state"), None)
+        out = stepwise.solve_reversible_heun(X, func, torch.cat(z0, dim=-1), t, revheun["dt"], adjoint,
+                                             revheun["adjoint_params"], field=field,
+                                             through=not adjoint and torch.is_grad_enabled())
+        return tuple(out.split(sizes, dim=-1))
     out = stepwise.solve(X, func, torch.cat(z0, dim=-1), t, adjoint, kw.get("method") or "dopri5", kw.get("options"),
                          kw["rtol"], kw["atol"], kw.get("adjoint_method"), kw.get("adjoint_options"),
                          kw.get("adjoint_rtol"), kw.get("adjoint_atol"), kw.get("adjoint_params"), field=field)
     return tuple(out.split(sizes, dim=-1))
 
 
-def _cdeint_foreign_control(X, func, z0, t, adjoint, kwargs):
+def _cdeint_foreign_control(X, func, z0, t, adjoint, kwargs, revheun=None):
     """A control that is not one of this package's paths (reference solver.py:45-46: anything with a `derivative` method,
     typically an nn.Module of the user's): the reference's compatibility checks and messages (solver.py:44-67), then the
     step-wise solver -- X.derivative(t) is called as it is (under autograd when its parameters or the times need a
@@ -1423,10 +1626,16 @@ def _cdeint_foreign_control(X, func, z0, t, adjoint, kwargs):
             if buffer.requires_grad:
                 warnings.warn(_GRAD_WARNING)
     from . import stepwise
+    field = stepwise.ForeignControlField(X, func)
+    if revheun is not None:
+        _no_time_gradient(t)
+        dispatch.record(dispatch.Choice(dispatch.TORCHSDE_PATHS[1], "the control is not one of this package's paths: "
+                                                                    "X.derivative is called at every evaluation"), None)
+        return stepwise.solve_reversible_heun(X, func, z0, t, revheun["dt"], adjoint, revheun["adjoint_params"], field=field,
+                                              through=not adjoint and torch.is_grad_enabled())
     dispatch.record(dispatch.Choice(dispatch.STEPWISE, "the control is not one of this package's paths: X.derivative is "
                                                        "called at every evaluation"), None)
     kw = dict(kwargs)
-    field = stepwise.ForeignControlField(X, func)
     return stepwise.solve(X, func, z0, t, adjoint, kw.pop("method", None) or "dopri5", kw.pop("options", None),
                           kw["rtol"], kw["atol"], kw.get("adjoint_method"), kw.get("adjoint_options"),
                           kw.get("adjoint_rtol"), kw.get("adjoint_atol"), kw.get("adjoint_params"), field=field)
@@ -1454,14 +1663,17 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
         return _cdeint_tuple(X, func, tuple(z0), t, adjoint, backend, kwargs)
     if not isinstance(z0, torch.Tensor):
         raise ValueError("z0 must either a tensor or a tuple/list of tensors.")
+    revheun = None
     if backend == "torchsde":
-        raise NotImplementedError("torchcde_amd: the torchsde backend is outside the native hot path.")
-    if backend != "torchdiffeq":
+        # method="reversible_heun": this package's own solver (csrc/revheun.hip, stepwise.solve_reversible_heun);
+        # method="midpoint": the torchdiffeq request with the same step, which the code below then serves
+        kwargs, revheun = _parse_torchsde(kwargs, adjoint)
+    elif backend != "torchdiffeq":
         raise ValueError(f"Unrecognised backend={backend}")
     if not isinstance(X, _NativePath):
         # solver.py:45-46 asks X for nothing but a `derivative` method: a user-defined control is solved step by step on the
         # GPU with X.derivative(t) itself under every evaluation (cde_contract for the matrix-vector product)
-        return _cdeint_foreign_control(X, func, z0, t, adjoint, kwargs)
+        return _cdeint_foreign_control(X, func, z0, t, adjoint, kwargs, revheun)
     stepwise_kwargs = dict(kwargs)      # what the step-wise path would receive (the reference forwards these verbatim)
     _lib.require_gpu(z0, "z0")
     packed = X._packed()
@@ -1483,6 +1695,12 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
             raise ValueError("func.prod did not return a tensor with the same shape as z0. func.prod returned shape {} "
                              "whilst z0 has shape {}.".format(tuple(first.shape), tuple(z0.shape)))
         from . import stepwise
+        if revheun is not None:
+            _no_time_gradient(t)
+            dispatch.record(dispatch.Choice(dispatch.TORCHSDE_PATHS[1], "func.prod multiplies by the control derivative "
+                                                                        "itself"), None)
+            return stepwise.solve_reversible_heun(X, func, z0, t, revheun["dt"], adjoint, revheun["adjoint_params"],
+                                                  through=_revheun_through(X, func, adjoint))
         dispatch.record(dispatch.Choice(dispatch.STEPWISE, "func.prod multiplies by the control derivative itself"), None)
         kw = stepwise_kwargs
         return stepwise.solve(X, func, z0, t, adjoint, kw.pop("method", None) or "dopri5", kw.pop("options", None),
@@ -1512,6 +1730,9 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
         elif not _lib.load().cde_rk4_supported(C, H, _lib.dtype_enum(z0.dtype), field.act, int(bool(adjoint)), variant):
             field = None              # beyond the fused kernels' tiles (LDS / lane limits): step-wise, not a late error
 
+    if revheun is not None:
+        return _cdeint_reversible_heun(X, func, z0, t, adjoint, revheun, variant, field, recognised, recognised_kind,
+                                       batch, H, C)
     if variant == _lib.VARIANT_BF16X3 and (field is None or field.act != _lib.ACT_NONE or kwargs.get("method") != "rk4"
                                            or z0.dtype != torch.float32 or H > 32 or C > 8):
         # an explicit request for a specific kernel family is never redirected

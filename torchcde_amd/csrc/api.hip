@@ -41,6 +41,18 @@ __global__ void stage_table_kernel(const T* __restrict__ knots, int64_t n_interv
   frac_out[e] = frac;
 }
 
+// Node table of the reversible Heun solves (revheun.hip): the control interval and fractional part at every GRID NODE --
+// the method evaluates the field at grid points only -- one slot per node, by the same `locate` as the stage table.
+template <typename T, typename TT>
+__global__ void node_table_kernel(const T* __restrict__ knots, int64_t n_intervals, const TT* __restrict__ grid,
+                                  int64_t n_grid, int64_t* __restrict__ index_out, T* __restrict__ frac_out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_grid) return;
+  T frac;
+  index_out[e] = locate(knots, n_intervals, (T)grid[e], frac);
+  frac_out[e] = frac;
+}
+
 // A solve's stage table and what follows it in one allocation: [index: 4 n_steps int64 | frac: 4 n_steps elem | tail],
 // every part 256-byte aligned.  `n_grid` grid points are n_grid - 1 steps (none for an empty grid).
 struct StageBuffers {
@@ -351,6 +363,88 @@ extern "C" int cde_fixed_adjoint_linear(int method, const void* coeffs, const vo
     const int rc = fill_stage_table<float, TT>(x, sgrid, layout.n_steps, 1, method, st, s);
     if (rc != CDE_OK) return rc;
     return launch_adjoint_jacobian_pair<TT>(x, f, io, n, st, (float*)layout.tail(workspace), s, PairForm{method, PairRows::f32});
+  });
+}
+
+// ---------------------------------------------------------------------------------------------- reversible Heun
+// node table [index: n_grid int64 | frac: n_grid f32], then the per-wave partial parameter gradients
+namespace cde {
+struct NodeWorkspace {
+  int64_t n_grid;
+  explicit NodeWorkspace(int64_t n) : n_grid(n > 0 ? n : 0) {}
+  size_t frac_offset() const { return align256((size_t)n_grid * sizeof(int64_t)); }
+  size_t tail_offset() const { return frac_offset() + align256((size_t)n_grid * sizeof(float)); }
+  StageBuffers table(const void* ws) const { return StageBuffers{(int64_t*)ws, (unsigned char*)ws + frac_offset()}; }
+  void* tail(const void* ws) const { return (unsigned char*)ws + tail_offset(); }
+};
+template <typename TT>
+static int fill_node_table(const Control& x, const void* grid, int64_t n_grid, StageBuffers to, hipStream_t s) {
+  node_table_kernel<float, TT><<<(unsigned)((n_grid + 255) / 256), 256, 0, s>>>(f32(x.knots), x.n_intervals, (const TT*)grid,
+                                                                                n_grid, to.index, f32(to.frac));
+  return check_launch();
+}
+}  // namespace cde
+
+extern "C" int cde_revheun_supported(int64_t C, int64_t H, int dtype, int act) {
+  return revheun_applicable(C, H, dtype, act) ? 1 : 0;
+}
+
+extern "C" int cde_revheun_forward_linear(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
+                                          const void* W, const void* bias, int act, const void* z0, const void* grid,
+                                          int64_t n_grid, const void* t_out, int64_t n_out, void* z_out, void* zhat_out,
+                                          int64_t B, int64_t C, int64_t H, int dtype, int time_dtype, int64_t* node_index,
+                                          void* node_frac, void* stream) {
+  if (B < 0 || C < 1 || H < 1 || n_intervals < 1 || n_grid < 1 || n_out < 1) return CDE_ERR_SHAPE;
+  if ((dtype != CDE_F32 && dtype != CDE_F64) || (time_dtype != CDE_F32 && time_dtype != CDE_F64)) return CDE_ERR_DTYPE;
+  if (B == 0) return CDE_OK;
+  if (!cde_revheun_supported(C, H, dtype, act)) return CDE_ERR_UNSUPPORTED;
+  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
+  if (!coeffs || !knots || !W || !bias || !z0 || !grid || !t_out || !z_out || !zhat_out || !node_index || !node_frac)
+    return CDE_ERR_NULL;
+  const Control x{coeffs, knots, n_intervals, degree};
+  const AffineField f{W, bias, act};
+  const ForwardIO io{z0, grid, n_grid, t_out, n_out, z_out, nullptr};
+  const Shape n{B, C, H};
+  const StageBuffers nodes{node_index, node_frac};
+  hipStream_t s = (hipStream_t)stream;
+  return dispatch_dtype(time_dtype, [&](auto tt) -> int {
+    using TT = typename decltype(tt)::type;
+    const int rc = fill_node_table<TT>(x, grid, n_grid, nodes, s);
+    return rc != CDE_OK ? rc : launch_revheun_forward<TT>(x, f, io, zhat_out, n, nodes, s);
+  });
+}
+
+extern "C" size_t cde_revheun_adjoint_workspace_bytes(int64_t B, int64_t n_grid) {
+  return NodeWorkspace(n_grid).tail_offset() + (B > 0 ? mfma_adjoint_partial_bytes(B) : 0);
+}
+
+extern "C" int cde_revheun_adjoint_linear(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
+                                          const void* W, const void* bias, int act, const void* y_final,
+                                          const void* zhat_final, const void* grad_out, const void* grid, int64_t n_grid,
+                                          const int64_t* node_ptr, const int64_t* node_out, const float* node_weight,
+                                          int64_t n_out, void* grad_z0, void* grad_W, void* grad_b, int64_t B, int64_t C,
+                                          int64_t H, int dtype, int time_dtype, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  if (B < 1 || C < 1 || H < 1 || n_intervals < 1 || n_grid < 1 || n_out < 1) return CDE_ERR_SHAPE;
+  if ((dtype != CDE_F32 && dtype != CDE_F64) || (time_dtype != CDE_F32 && time_dtype != CDE_F64)) return CDE_ERR_DTYPE;
+  if (!cde_revheun_supported(C, H, dtype, act)) return CDE_ERR_UNSUPPORTED;
+  if (degree != CDE_PATH_CUBIC && degree != CDE_PATH_LINEAR) return CDE_ERR_UNSUPPORTED;
+  if (!coeffs || !knots || !W || !bias || !y_final || !zhat_final || !grad_out || !grid || !node_ptr || !node_out ||
+      !node_weight || !grad_z0 || !grad_W || !grad_b || !workspace)
+    return CDE_ERR_NULL;
+  if (workspace_bytes < cde_revheun_adjoint_workspace_bytes(B, n_grid)) return CDE_ERR_WORKSPACE;
+  const Control x{coeffs, knots, n_intervals, degree};
+  const AffineField f{W, bias, act};
+  const ReversibleIO io{y_final, zhat_final, grad_out, grid, n_grid, node_ptr, node_out, node_weight, n_out,
+                        grad_z0, grad_W, grad_b};
+  const Shape n{B, C, H};
+  const NodeWorkspace layout(n_grid);
+  const StageBuffers nodes = layout.table(workspace);
+  hipStream_t s = (hipStream_t)stream;
+  return dispatch_dtype(time_dtype, [&](auto tt) -> int {
+    using TT = typename decltype(tt)::type;
+    const int rc = fill_node_table<TT>(x, grid, n_grid, nodes, s);
+    return rc != CDE_OK ? rc : launch_revheun_adjoint<TT>(x, f, io, n, nodes, (float*)layout.tail(workspace), s);
   });
 }
 

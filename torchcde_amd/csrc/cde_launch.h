@@ -35,6 +35,13 @@ struct BackpropIO {
   const float* step_dt; int64_t n_steps; const int64_t* node_ptr; const int64_t* node_out; const float* node_weight;
   void* grad_z0; void* grad_W; void* grad_b; void* grad_coeffs;
 };
+// the reconstructing backward pass of the reversible Heun method (revheun.hip): the final (y, zh) of the forward solve, the
+// forward grid, and the output gradients as BackpropIO's node lists
+struct ReversibleIO {
+  const void* y_final; const void* zhat_final; const void* grad_out; const void* grid; int64_t n_grid;
+  const int64_t* node_ptr; const int64_t* node_out; const float* node_weight; int64_t n_out;
+  void* grad_z0; void* grad_W; void* grad_b;
+};
 // steps [k_begin, k_end) of a two-layer sweep.  Continuous adjoint: `y_state`, `a_state` over `grid` = the reversed grid;
 // reverse mode: `a_state` alone (the running gradient) over the forward grid, with the `stages` of all `n_steps` steps.
 struct SweepIO {
@@ -194,6 +201,16 @@ int launch_adjoint_mfma(const Control& x, const AffineField& f, const AdjointIO&
 template <typename TT>
 int launch_adjoint_jacobian_bx(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n,
                                const StageTable& st, float* partial, hipStream_t s);
+
+// ---------------------------------------------------------------- revheun.hip (reversible Heun: f32, H <= 32, C <= 8)
+// `nodes`: control interval and fractional part at every GRID NODE, one slot per node (api.hip: node_table_kernel)
+bool revheun_applicable(int64_t C, int64_t H, int dtype, int act);
+template <typename TT>
+int launch_revheun_forward(const Control& x, const AffineField& f, const ForwardIO& io, void* zhat_out, const Shape& n,
+                           const StageTable& nodes, hipStream_t s);
+template <typename TT>
+int launch_revheun_adjoint(const Control& x, const AffineField& f, const ReversibleIO& io, const Shape& n,
+                           const StageTable& nodes, float* partial, hipStream_t s);
 
 // ---------------------------------------------------------------- rk4_adjoint_pair.hip (chain wave + helper wave per tile)
 template <typename TT>

@@ -69,6 +69,12 @@ FUSED_PATHS = (
     "mlp_rk4_backprop",       # adjoint=False for the two-layer field: K2m storing its stage states + K3m's sweep in reverse mode
 )
 STEPWISE = "stepwise"
+# backend="torchsde", method="reversible_heun" (arXiv 2105.13493): not a row of `select_path` -- that table describes
+# torchdiffeq requests -- but recorded the same way, as a Choice whose path is one of these two
+TORCHSDE_PATHS = (
+    "reversible_heun",            # RHf + RHa (csrc/revheun.hip): the exact gradient of the discrete solve from the final state alone
+    "reversible_heun_stepwise",   # stepwise.solve_reversible_heun: host-driven steps, reconstructing backward
+)
 
 
 def _stepwise(reason):
@@ -169,7 +175,7 @@ def last():
 
 def warn_once(func, choice, request):
     """A recognised field that leaves the fused paths: one warning per (module class, reason)."""
-    if choice.path != STEPWISE or request.kind is None or request.variant_generic:
+    if choice.path not in (STEPWISE, TORCHSDE_PATHS[1]) or request.kind is None or request.variant_generic:
         return
     key = (type(func), choice.reason)
     with _warned_lock:

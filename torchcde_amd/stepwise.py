@@ -534,6 +534,158 @@ class _Adjoint(torch.autograd.Function):
         return (None, aug[2], grad_t, *aug[3:])
 
 
+# ------------------------------------------------------------------------------------------ reversible Heun
+# backend="torchsde", method="reversible_heun" (arXiv 2105.13493, Algorithms 1 and 2; semantics: DESIGN.md section 8) for
+# everything the fused kernels (csrc/revheun.hip) do not take.  State (y, zh, f), zh_0 = y_0, f_0 = F(t_0, y_0); per step
+#     zh' = 2 y - zh + f dt;   f' = F(t', zh');   y' = y + (f + f') dt/2
+# with dt = grid[k+1] - grid[k] rounded once to the state's dtype and used identically in both directions.
+def _revheun_outputs(grid, t_host):
+    """Per output time (node k, slope): y_k itself (slope None) or y_k + slope (y_{k+1} - y_k) -- the walk over
+    (grid, t) that _solve_fixed and the fused kernels make."""
+    outs, j = [(0, None)], 1
+    for k, (t0, t1) in enumerate(zip(grid[:-1], grid[1:])):
+        while j < len(t_host) and bool(t1 >= t_host[j]):
+            tj = t_host[j]
+            if bool(tj == t0):
+                outs.append((k, None))
+            elif bool(tj == t1):
+                outs.append((k + 1, None))
+            else:
+                outs.append((k, (tj - t0) / (t1 - t0)))
+            j += 1
+    if len(outs) != len(t_host):
+        raise NotImplementedError("torchcde_amd: method='reversible_heun' needs non-decreasing output times")
+    return outs
+
+
+def _revheun_forward(f, y0, times, dts, outs):
+    """The forward recurrences; returns (outputs stacked over the output times, y_N, zh_N)."""
+    on_node, in_step = {}, {}
+    for j, (k, slope) in enumerate(outs):
+        (on_node if slope is None else in_step).setdefault(k, []).append((j, slope))
+    result = [None] * len(outs)
+    y = zh = y0
+    for j, _ in on_node.get(0, ()):
+        result[j] = y
+    if dts:
+        fk = f(times[0], zh)
+    for k, dt in enumerate(dts):
+        zh = 2 * y - zh + fk * dt
+        f1 = f(times[k + 1], zh)
+        y1 = y + (fk + f1) * (0.5 * dt)
+        for j, slope in in_step.get(k, ()):
+            result[j] = y + float(slope.to(y0.dtype)) * (y1 - y)
+        for j, _ in on_node.get(k + 1, ()):
+            result[j] = y1
+        y, fk = y1, f1
+    return torch.stack(result), y, zh
+
+
+class _ReversibleHeun(torch.autograd.Function):
+    """The exact gradient of the discrete reversible Heun solve from (y_N, zh_N) alone: the backward pass walks the nodes
+    N .. 0, rebuilds the state by inverting the steps and differentiates them -- one field evaluation and one
+    vector-Jacobian product per node (closed form for a recognised field, autograd otherwise).  With dt = dt_{k-1}:
+        a = fbar_k + ybar_k dt/2;   f_k, v, dtheta = F, (dF/dz)^T a, (dF/dtheta)^T a  at (t_k, zh_k)
+        y_k = y_{k+1} - (f_k + f_{k+1}) dt_k/2   (y lags one node: it needs f_k)
+        zt = zbar_k + v;   fbar_{k-1} = ybar_k dt/2 + zt dt;   ybar_{k-1} = ybar_k + 2 zt + (outputs on node k-1)
+        zbar_{k-1} = -zt;  zh_{k-1} = 2 y_k - zh_k - f_k dt
+    and node 0 is evaluated at zh_0 (= y_0) with cotangent fbar_0: dL/dy_0 = ybar_0 + zbar_0 + v."""
+
+    @staticmethod
+    def forward(ctx, cfg, y0, *params):
+        with torch.no_grad():
+            out, y_last, zh_last = _revheun_forward(cfg["func"], y0, cfg["times"], cfg["dts"], cfg["outs"])
+        ctx.cfg = cfg
+        ctx.save_for_backward(y_last, zh_last, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        cfg = ctx.cfg
+        func, times, dts = cfg["func"], cfg["times"], cfg["dts"]
+        y, zh, *params = ctx.saved_tensors
+        params = tuple(params)
+        n = len(dts)
+        landing = [[] for _ in range(n + 1)]          # the transpose of the output interpolation
+        for j, (k, slope) in enumerate(cfg["outs"]):
+            if slope is None:
+                landing[k].append((j, None))
+            else:
+                s = float(slope.to(y.dtype))
+                landing[k].append((j, float(torch.ones((), dtype=y.dtype) - slope.to(y.dtype))))
+                landing[k + 1].append((j, s))
+
+        def outputs_on(k, g):
+            for j, w in landing[k]:
+                g = g + (grad_out[j] if w is None else w * grad_out[j])
+            return g
+
+        with torch.no_grad():
+            explicit = _explicit_dynamics(func, params)
+
+            def node(tt, z, cot):
+                if explicit is not None:
+                    return explicit(tt, z, -cot)                # (written for the cotangent -a of the continuous adjoint)
+                with torch.enable_grad():
+                    zz = z.detach().requires_grad_(True)
+                    fe = func(tt, zz)
+                    vz, *vp = torch.autograd.grad(fe, (zz,) + params, cot, allow_unused=True, retain_graph=True)
+                vz = torch.zeros_like(z) if vz is None else vz
+                return fe.detach(), vz, [torch.zeros_like(p) if g is None else g for p, g in zip(params, vp)]
+
+            grads = [torch.zeros_like(p) for p in params]
+            ybar = outputs_on(n, torch.zeros_like(y))
+            zbar, fbar = torch.zeros_like(y), torch.zeros_like(y)
+            f_next = None
+            for k in range(n, 0, -1):
+                dt = dts[k - 1]
+                fk, v, dp = node(times[k], zh, fbar + ybar * (0.5 * dt))
+                grads = [g + d for g, d in zip(grads, dp)]
+                if f_next is not None:
+                    y = y - (fk + f_next) * (0.5 * dts[k])
+                zt = zbar + v
+                fbar = ybar * (0.5 * dt) + zt * dt
+                ybar = outputs_on(k - 1, ybar + 2 * zt)
+                zbar = -zt
+                zh = 2 * y - zh - fk * dt
+                f_next = fk
+            _, v, dp = node(times[0], zh, fbar)
+            grads = [g + d for g, d in zip(grads, dp)]
+        return (None, ybar + zbar + v, *grads)
+
+
+def solve_reversible_heun(X, func, z0, t, dt, adjoint, adjoint_params, field=None, recognised=None, through=False):
+    """Step-wise cdeint(..., backend="torchsde", method="reversible_heun", dt=dt): returns (..., len(t), H).  Gradients of z0
+    and the parameters (`adjoint_params`, or func's own) come from the reconstructing backward pass; `through`: plain
+    autograd through the host-driven steps instead (adjoint=False with control tensors -- or anything else outside func's
+    parameters -- that requires a gradient)."""
+    if field is None:
+        field = ControlledField(X, func)
+        field.recognised = recognised
+    t_host = t.detach().cpu()
+    grid = _grid(t_host, dt)
+    outs = _revheun_outputs(grid, t_host)
+    times = grid.to(z0.device).to(z0.dtype)
+    dts = [float(d) for d in (grid[1:] - grid[:-1]).to(z0.dtype)]
+    if through or not torch.is_grad_enabled():
+        out = _revheun_forward(field, z0, times, dts, outs)[0]
+    else:
+        if adjoint_params is None:
+            if not isinstance(func, torch.nn.Module):
+                if adjoint:
+                    raise ValueError("func must be an instance of nn.Module to specify the adjoint parameters; alternatively "
+                                     "they can be specified explicitly via the `adjoint_params` argument. If there are no "
+                                     "parameters then it is allowable to set `adjoint_params=()`.")
+                adjoint_params = ()
+            else:
+                adjoint_params = tuple(func.parameters())
+        params = tuple(p for p in adjoint_params if isinstance(p, torch.Tensor) and p.requires_grad)
+        cfg = dict(func=field, times=times, dts=dts, outs=outs)
+        out = _ReversibleHeun.apply(cfg, z0, *params)
+    lead = range(1, out.dim() - 1)
+    return out.permute(*lead, 0, -1)
+
+
 class TupleField:
     """Tuple state (reference solver.py:68-95, :131-133): z = (z_1, .., z_k), X.derivative(t) = (dX_1, .., dX_k), func
     returns one (.., H_i, C_i) matrix per component (or func.prod the products).  torchdiffeq solves such systems on
