@@ -422,6 +422,38 @@ int cde_rk4_adjoint_mlp3_sweep(const void* coeffs, const void* knots, int64_t n_
                                size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K2mc / K3mc  K2m and K3m's continuous adjoint for the two-layer field on controls of 17 .. 64 channels (a depth-2
+ * logsignature of 6 .. 10 channels, series with time and mask channels): f32, H <= 32, 16 < C <= 64, width <= 128, one
+ * wave per 16 series at every batch size, rk4 only; anything else CDE_ERR_UNSUPPORTED (the entry points above keep turning
+ * C > 16 away).  `act` = CDE_FIELD_ACT(final, hidden) as for K2m.  The output layer (up to 2048 x 128) is read from L2:
+ * by the forward kernel from W2 itself -- 16-byte rows when width is a multiple of 4 and W2 is 16-byte aligned, element by
+ * element otherwise -- by the sweep from zero-padded copies that _prepare leaves in `workspace`.
+ *   cde_rk4_mlp_wide_supported   1 when (C, H, width, dtype, act) is inside this envelope, else 0
+ *   cde_rk4_forward_mlp_wide     arguments of cde_rk4_forward_mlp
+ *   cde_rk4_adjoint_mlp_wide_*   K3m's protocol: prepare once per backward, sweep in chunks of steps, the caller reduces
+ *     the streamed factor rows.  U, G1, Z as K3m.  With CP = C rounded up to 4, G2 is ceil(H CP / 256) BLOCKS of
+ *     (rows, 256) f32, block b 4 (k_end - k_begin) B rows behind block b - 1 and holding columns 256 b .. 256 b + 255 of
+ *     the padded layout (h, c) -> h CP + c; the CALLER zeroes G2 once (rows h >= H are never written) and reduces every
+ *     block against U with cde_mlp_grad_reduce (layer 2) into its own [256][132] image.
+ * No control-coefficient gradients (there is no `grad_coeffs`).
+ * ------------------------------------------------------------------------------------------- */
+int cde_rk4_mlp_wide_supported(int64_t C, int64_t H, int64_t width, int dtype, int act);
+int cde_rk4_forward_mlp_wide(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
+                             const void* bias1, int64_t width, const void* W2, const void* bias2, int act, const void* z0,
+                             const void* grid, int64_t n_grid, const void* t_out, int64_t n_out, void* z_out, int64_t B,
+                             int64_t C, int64_t H, int dtype, int time_dtype, int64_t* stage_index, void* stage_frac,
+                             void* stream);
+size_t cde_rk4_adjoint_mlp_wide_workspace_bytes(int64_t n_sgrid);
+int cde_rk4_adjoint_mlp_wide_prepare(const void* knots, int64_t n_intervals, const void* sgrid, int64_t n_sgrid,
+                                     const void* W1, const void* bias1, int64_t width, const void* W2, const void* bias2,
+                                     int64_t C, int64_t H, int dtype, int time_dtype, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int cde_rk4_adjoint_mlp_wide_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
+                                   void* y_state, void* a_state, const void* sgrid, int64_t n_sgrid, int64_t k_begin,
+                                   int64_t k_end, void* U, void* G2, void* G1, void* Z, int64_t B, int64_t C, int64_t H,
+                                   int dtype, int time_dtype, const void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K3  Fused continuous-adjoint reverse sweep for K2.
  * Replaces torchdiffeq.odeint_adjoint's backward (behind solver.py:226): for every output
  * interval, RK4 (3/8) integration in reversed time of the augmented state (z, a_z, a_W, a_b),
