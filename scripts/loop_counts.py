@@ -99,7 +99,9 @@ def classes(body):
             "mfma_32x32x16_bf16": sum(o == "v_mfma_f32_32x32x16_bf16" for o in op), "valu": len(valu),
             "v_accvgpr_read_b32": op.count("v_accvgpr_read_b32"), "v_accvgpr_write_b32": op.count("v_accvgpr_write_b32"),
             "v_mov_b32": op.count("v_mov_b32"), "copies": sum(op.count(c) for c in COPIES),
-            "v_pk_fma_f32": op.count("v_pk_fma_f32"), "v_readlane_b32": op.count("v_readlane_b32"),
+            "v_pk_fma_f32": op.count("v_pk_fma_f32"), "v_pk_mul_f32": op.count("v_pk_mul_f32"),
+            "v_pk_add_f32": op.count("v_pk_add_f32"), "v_pk": sum(o.startswith("v_pk_") for o in op),
+            "v_readlane_b32": op.count("v_readlane_b32"),
             "branches": sum(o.startswith("s_cbranch") or o == "s_branch" for o in op),
             "scratch": sum(o.startswith("scratch_") for o in op),
             "ds_read_b128": op.count("ds_read_b128"), "lds_reads": sum(o.startswith("ds_read") for o in op),
@@ -123,7 +125,7 @@ if __name__ == "__main__":
         mfma, rest = int(rest[1]), rest[2:]
     table = loop_table(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "", rest or None, mfma)
     cols = ["instructions", "mfma", "mfma_srca_agpr", "valu", "copies", "v_accvgpr_read_b32", "v_accvgpr_write_b32", "v_mov_b32",
-            "v_pk_fma_f32", "v_readlane_b32", "ds_read_b128", "s_waitcnt", "lds_cover_min", "lds_wait_cover_min", "branches", "scratch"]
+            "v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32", "v_pk", "v_readlane_b32", "ds_read_b128", "s_waitcnt", "lds_cover_min", "lds_wait_cover_min", "branches", "scratch"]
     print(" ".join("%-12s" % c[-12:] for c in cols) + " kernel")
     for n, row in table.items():
         print(" ".join("%-12s" % ("-" if row[c] is None else row[c]) for c in cols) + " " + n.replace("cde::", ""))

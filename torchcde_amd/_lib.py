@@ -29,8 +29,9 @@ if PHASE_TRACE:
     HIPCC_FLAGS.append("-DCDE_PHASE_TRACE")
 # per-file additions.  rk4_split.hip: keep MFMA accumulators in VGPRs -- its tiles are consumed by VALU code right
 # away, and on gfx950 every v_accvgpr_read costs matrix-pipe time (f32 MFMA and VALU do not overlap within a wave).
-# rk4_adjoint_pair.hip: no SLP vectorizer -- it packs the scalar bf16 splits and the chain wave's FMAs into v_pk_* f32
-# instructions, which cost matrix-pipe time beside the partner wave's MFMAs and, in K3p, pushed both forms into scratch.
+# rk4_adjoint_pair.hip: no SLP vectorizer -- it packs the scalar bf16 splits of the helper wave into v_pk_* f32
+# instructions, which do not hide beside the partner wave's MFMAs, and pushed both forms of K3p into scratch.  Only what the
+# file writes as vector arithmetic is packed (the bf16 form's chain wave: profiles/NOTES.md, round 12).
 # rk4_bf16x3.hip (K2b alone): the flag took 484 of 530 v_accvgpr_read per RK step out of its one wave, and the AGPRs it
 # leaves empty hold K2b's weight pieces for the whole solve (cde_bf16x3.h: bx_load_resident); K3b, whose scratch the
 # flag would grow from 172 to 388 bytes per lane, is rk4_bf16x3_adjoint.hip and built without it.

@@ -17,7 +17,7 @@
 //               control: it owns the stage table, the coefficient rows and the knot widths, forms dX/dt of every stage
 //               and leaves it (plain for the chain wave, weighted by the quadrature weight for itself) in a three-slot LDS
 //               ring.  That takes 30 registers and ~50 vector instructions per stage off the chain wave, which then fits
-//               256 registers without scratch (all of its vector arithmetic non-packed f32).
+//               256 registers without scratch.
 // One s_barrier per stage orders everything: the chain wave writes (z, a) buffer s & 1 and reads ring slot s % 3 before
 // barrier s; the helper reads both between barriers s and s + 1 and writes slot (s + 2) % 3; the chain wave's next write to
 // buffer s & 1 comes after barrier s + 1.  The matrix pipe sees the chain wave's dependent row chains and the helper's
@@ -101,6 +101,16 @@ __device__ __forceinline__ kp_u32x4 kp_wjb_image(const float* __restrict__ W, co
   }
   return __builtin_bit_cast(kp_u32x4, out);
 }
+// Packed f32 in the chain wave of the bf16 form (BX): the number of J rows of a stage whose consume is v_pk_fma_f32 -- 0,
+// 16 (the odd rows) or 32 -- is a compile-time constant (-DKP_PACK_CHAIN_ROWS=.. for A/B builds); the f32 form and
+// rk4_backprop_jacobian_pair never take this path.  What packed f32 costs beside the partner wave's bf16 MFMAs, and the parts
+// that were built and not kept, are in the BX comment below and in profiles/NOTES.md (round 12).
+#ifndef KP_PACK_CHAIN_ROWS
+#define KP_PACK_CHAIN_ROWS 32
+#endif
+constexpr int KP_PK_CHAIN_ROWS = KP_PACK_CHAIN_ROWS;
+static_assert(KP_PK_CHAIN_ROWS == 0 || KP_PK_CHAIN_ROWS == 16 || KP_PK_CHAIN_ROWS == 32, "KP_PACK_CHAIN_ROWS: 0, 16 or 32");
+
 // the stage barrier: this wave's LDS traffic done, then all eight waves meet
 __device__ __forceinline__ void kp_stage_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -111,6 +121,16 @@ __device__ __forceinline__ void kp_stage_barrier() { asm volatile("s_waitcnt lgk
 // trajectories are bitwise K3bj's.  The helper's dL/dW: 12 bf16 MFMAs per channel tile (six piece products x two K blocks
 // of 16 series) instead of 16 f32 ones, its operands split on the helper itself with non-packed vector instructions, which
 // hide in the chain wave's MFMA gaps (scripts/ubench/mfma_bf16_fill.hip).  dL/db keeps the f32 form's fma order.
+// Packed f32 beside bf16 MFMAs (round 12, scripts/ubench/mfma_bf16_pk_issue.hip, profiles/NOTES.md).  This kernel is bound
+// by the instruction issue of its two waves (~3,000 instructions per stage and SIMD at ~4 cycles, the matrix pipe busy 0.43),
+// and a v_pk_* f32 instruction costs MORE than a non-packed one -- it is no free pair -- but less than the two it replaces.
+// So what is written packed is what halves a large instruction count: the chain's J-row consume (32 v_fma_f32 -> 16
+// v_pk_fma_f32 per row: 3.42 -> 3.33 ms per launch).  A packed instruction that replaces ONE scalar one loses (the sum of a
+// row's two partial-sum halves is kept scalar by a fence: 0.02 ms); the 3/8-rule update as packed arithmetic gained 0.014 ms
+// on the kernel and nothing that the step's timing resolves, and is not kept; packing the helper's products and split
+// remainders (64 v_pk_mul_f32 + 128 v_pk_add_f32 for 384 scalar ones per stage) made the launch slower than no packing at
+// all, 3.33 -> 3.44 ms -- the helper's vector work is what hides under the chain's MFMAs, and packed f32 does not hide.
+// Every packed operation rounds element for element as the scalar one it replaces: all results are bitwise the same.
 template <typename TT, int DEGREE, int METHOD = CDE_METHOD_RK4, bool BX = false>
 __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
     const float* __restrict__ coeffs, const float* __restrict__ knots, int64_t n_intervals,
@@ -403,9 +423,18 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
         // (K3j's code: rows issued one ahead of their use, explicit wait states after the last issue).
         f32x16 f, va;
         {
-          float vs[16];                                 // a^T J, non-packed (packed f32 beside the partner's MFMAs costs pipe time)
+          // a^T J: the f32 form keeps it in `vs` and sums with `consume`; the bf16 form keeps it on register pairs
+          // (vs[2j], vs[2j + 1]) in `vs2` and sums with `consume2`.  Each instantiation uses one of the two and the other is
+          // dead code; `consume` is the reference for the order of operations, `consume2` must match it element for element.
+          float vs[16];
+          f32x2 vs2[8];
+          if constexpr (BX) {
 #pragma unroll
-          for (int j = 0; j < 16; ++j) vs[j] = 0.f;
+            for (int j = 0; j < 8; ++j) vs2[j] = f32x2{0.f, 0.f};
+          } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) vs[j] = 0.f;
+          }
           int opaque = 0;                               // the image reads are loop invariant: keep them inside the stage
           asm volatile("" : "+v"(opaque));
           const float4* wp = wj + lane + opaque;
@@ -457,6 +486,47 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
             for (int j = 0; j < 16; ++j) asm volatile("" : "+v"(vs[j]));
             return (p0 + q0) + (p1 + q1);
           };
+          // (BX) the same sums on register pairs: p = (p0, p1), q = (q0, q1) and vs2[j] each take one v_pk_fma_f32 per pair
+          // of J (element for element the scalar form's operations, so the same bits); a_h is the low (hi = false) or high
+          // element of `aeo`, broadcast by op_sel.  Rows that are not packed (KP_PK_CHAIN_ROWS) run the scalar form on the
+          // same registers.
+          auto consume2 = [&](const f32x16& J, f32x2 aeo, bool hi, bool packed) {
+            const float ah = hi ? aeo[1] : aeo[0];
+            float s;
+            if (packed) {
+              f32x2 p = {0.f, 0.f}, q = {0.f, 0.f};
+              const f32x2 ah2 = {ah, ah};
+#pragma unroll
+              for (int j = 0; j < 8; ++j) {
+                const f32x2 Jp = {J[2 * j], J[2 * j + 1]}, yp = {yst[2 * j], yst[2 * j + 1]};
+                if (j & 1) q = __builtin_elementwise_fma(Jp, yp, q);
+                else p = __builtin_elementwise_fma(Jp, yp, p);
+                vs2[j] = __builtin_elementwise_fma(Jp, ah2, vs2[j]);
+              }
+              const f32x2 pq = p + q;                      // (p0 + q0, p1 + q1)
+              float s0 = pq[0], s1 = pq[1];
+              asm volatile("" : "+v"(s0), "+v"(s1));       // or the compiler adds the two halves with a second v_pk_add_f32
+              s = s0 + s1;
+            } else {
+              float p0 = 0.f, p1 = 0.f, q0 = 0.f, q1 = 0.f;
+#pragma unroll
+              for (int j = 0; j < 8; ++j) {
+                if (j & 1) {
+                  q0 = __builtin_fmaf(J[2 * j], yst[2 * j], q0);
+                  q1 = __builtin_fmaf(J[2 * j + 1], yst[2 * j + 1], q1);
+                } else {
+                  p0 = __builtin_fmaf(J[2 * j], yst[2 * j], p0);
+                  p1 = __builtin_fmaf(J[2 * j + 1], yst[2 * j + 1], p1);
+                }
+                vs2[j][0] = __builtin_fmaf(J[2 * j], ah, vs2[j][0]);
+                vs2[j][1] = __builtin_fmaf(J[2 * j + 1], ah, vs2[j][1]);
+              }
+              s = (p0 + q0) + (p1 + q1);
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(vs2[j]));
+            return s;
+          };
           f32x16 Je, Jo;                                 // rows 2r / 2r + 1 in flight
           if constexpr (BX) {
             // one row image in flight (12 registers): requested right after the previous row's issue, a consume ahead
@@ -475,11 +545,12 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
               asm volatile("" : "+v"(Je));
               float ae = ast[r], ao = ast[r];
               kp_swap32(ae, ao);
-              float X = consume(Je, ae);
+              const f32x2 aeo = {ae, ao};
+              float X = consume2(Je, aeo, false, KP_PK_CHAIN_ROWS == 32);
               issue(Je, img);
               if (r < 15) img = image(2 * r + 3);
               asm volatile("" : "+v"(Jo));
-              float Y = consume(Jo, ao);
+              float Y = consume2(Jo, aeo, true, KP_PK_CHAIN_ROWS >= 16);
               kp_swap32(X, Y);
               f[r] = X + Y;
             }
@@ -507,7 +578,7 @@ __global__ __launch_bounds__(512, 2) void rk4_adjoint_jacobian_pair(
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             f[r] += Je[r];
-            va[r] = vs[r];
+            va[r] = BX ? vs2[r >> 1][r & 1] : vs[r];
           }
         }
 
