@@ -454,6 +454,41 @@ int cde_rk4_adjoint_mlp_wide_sweep(const void* coeffs, const void* knots, int64_
                                    int dtype, int time_dtype, const void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K2mh / K3mh  K2mc and K3mc for the two-layer field on hidden states of 33 .. 64 channels: f32, 32 < H <= 64,
+ * 1 <= C <= 64 with H CP <= 2048 (CP = C rounded up to 4: 64 x 32, 40 x 48 and 33 x 60 are inside, 64 x 33 is not),
+ * width <= 128, one wave per 16 series at every batch size, rk4 only; anything else CDE_ERR_UNSUPPORTED (every entry point
+ * above keeps turning H > 32 away).  `act` = CDE_FIELD_ACT(final, hidden) as for K2m.  The output layer (up to 2048 x 128)
+ * is read from L2 as by K2mc / K3mc: by the forward kernel from W2 itself -- 16-byte rows when width is a multiple of 4 and
+ * W2 is 16-byte aligned, element by element otherwise -- by the sweep from zero-padded copies that _prepare leaves in
+ * `workspace`.
+ *   cde_rk4_mlp_tall_supported   1 when (C, H, width, dtype, act) is inside this envelope, else 0
+ *   cde_rk4_forward_mlp_tall     arguments of cde_rk4_forward_mlp
+ *   cde_rk4_adjoint_mlp_tall_*   the protocol of cde_rk4_adjoint_mlp_wide_*.  U, G1 and the ceil(H CP / 256) <= 8 BLOCKS of
+ *     G2 exactly as there (the CALLER zeroes G2 once).  The state rows come in two halves of (rows, 36) f32:
+ *       Z      units 0 .. 31 | 1 | 0 0 0
+ *       Z_hi   units 32 .. 63 | 1 | 0 0 0     (columns H - 32 .. 31 are never written: the CALLER zeroes Z_hi once)
+ *     the caller writes both "1" columns and reduces G1 against each half with cde_mlp_grad_reduce (layer 1) into its own
+ *     [128][36] image: dW1[:, 0:32] | db1 from the first, dW1[:, 32:H] from the second.
+ * No control-coefficient gradients (there is no `grad_coeffs`).
+ * ------------------------------------------------------------------------------------------- */
+int cde_rk4_mlp_tall_supported(int64_t C, int64_t H, int64_t width, int dtype, int act);
+int cde_rk4_forward_mlp_tall(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
+                             const void* bias1, int64_t width, const void* W2, const void* bias2, int act, const void* z0,
+                             const void* grid, int64_t n_grid, const void* t_out, int64_t n_out, void* z_out, int64_t B,
+                             int64_t C, int64_t H, int dtype, int time_dtype, int64_t* stage_index, void* stage_frac,
+                             void* stream);
+size_t cde_rk4_adjoint_mlp_tall_workspace_bytes(int64_t n_sgrid);
+int cde_rk4_adjoint_mlp_tall_prepare(const void* knots, int64_t n_intervals, const void* sgrid, int64_t n_sgrid,
+                                     const void* W1, const void* bias1, int64_t width, const void* W2, const void* bias2,
+                                     int64_t C, int64_t H, int dtype, int time_dtype, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int cde_rk4_adjoint_mlp_tall_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
+                                   void* y_state, void* a_state, const void* sgrid, int64_t n_sgrid, int64_t k_begin,
+                                   int64_t k_end, void* U, void* G2, void* G1, void* Z, void* Z_hi, int64_t B, int64_t C,
+                                   int64_t H, int dtype, int time_dtype, const void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K3  Fused continuous-adjoint reverse sweep for K2.
  * Replaces torchdiffeq.odeint_adjoint's backward (behind solver.py:226): for every output
  * interval, RK4 (3/8) integration in reversed time of the augmented state (z, a_z, a_W, a_b),

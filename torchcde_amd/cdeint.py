@@ -839,6 +839,116 @@ class _MlpWidePlan(_MlpPlan):
         raise NotImplementedError("torchcde_amd: wide controls have no reverse-mode (adjoint=False) kernels")
 
 
+def _mlp_tall_fusable(field, H, C, z0, packed):
+    """The envelope of the tall-state kernels (csrc/rk4_mlp_tallh.hip; cde_mi355x.h: cde_rk4_forward_mlp_tall): float32,
+    32 < H <= 64, C <= 64 with H * CP <= 2048 (CP = C rounded up to 4), width <= 128 -- the hidden sizes beyond every tile
+    form of _mlp_fusable and _mlp_wide_fusable, which both stop at H = 32."""
+    w1, w2 = field.hidden.weight, field.output.weight
+    return (z0.dtype == packed.dtype == w1.dtype == w2.dtype == torch.float32 and 32 < H <= 64 and 1 <= C <= 64
+            and H * ((C + 3) // 4 * 4) <= 2048 and w1.size(0) <= 128 and tuple(w1.shape) == (w1.size(0), H)
+            and tuple(w2.shape) == (H * C, w1.size(0)))
+
+
+def _mlp_tall_gradients(acc1, acc1_hi, acc2, H, C, width):
+    """(dL/dW1, dL/db1, dL/dW2, dL/db2) from the reduced images of the tall-state sweep.  acc1 / acc1_hi: (128, 36) -- columns
+    0 .. 31 of the first are dL/dW1[:, 0:32] and column 32 dL/db1, columns 0 .. H - 33 of the second dL/dW1[:, 32:H].  acc2 as
+    _mlp_wide_gradients."""
+    g_w1 = torch.cat((acc1[:width, :32], acc1_hi[:width, :H - 32]), dim=1).contiguous()
+    return (g_w1, acc1[:width, 32].contiguous()) + _mlp_wide_gradients(acc1, acc2, H, C, width)[2:]
+
+
+class _MlpTallPlan(_MlpPlan):
+    """Fused RK4 solves for the two-layer field on a hidden state of 33 .. 64 channels: forward (K2mh,
+    cde_rk4_forward_mlp_tall) and continuous-adjoint backward (K3mh sweep, cde_rk4_adjoint_mlp_tall_*, + one factor
+    reduction per 256-column block of the output layer's gradient and one per 32-unit half of the state).  One wave per 16
+    series at every batch size."""
+
+    def run(self, z0, stages=False):
+        if stages:
+            raise NotImplementedError("torchcde_amd: tall hidden states have no reverse-mode (adjoint=False) kernels")
+        lib = _lib.load()
+        g = self.grids
+        out = torch.empty(self.B, g.n_out, self.H, dtype=torch.float32, device=self.device)
+        n_steps = max(g.grid.numel() - 1, 0)
+        stage_index = torch.empty(max(4 * n_steps, 1), dtype=torch.int64, device=self.device)
+        stage_frac = torch.empty(max(4 * n_steps, 1), dtype=torch.float32, device=self.device)
+        z0c = z0.detach().reshape(self.B, self.H).contiguous()
+        weights = self._weights()
+        _lib.check(lib.cde_rk4_forward_mlp_tall(
+            _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, *_weight_args(weights), self.act,
+            _lib.ptr(z0c), _lib.ptr(g.grid), g.grid.numel(), _lib.ptr(g.t_out), g.n_out, _lib.ptr(out), self.B, self.C, self.H,
+            _lib.dtype_enum(torch.float32), _lib.dtype_enum(g.time_dtype), _lib.ptr(stage_index), _lib.ptr(stage_frac),
+            _lib.stream_ptr(self.device)), "cde_rk4_forward_mlp_tall")
+        return out.reshape(*self.batch, g.n_out, self.H)
+
+    def run_adjoint(self, z_saved, grad_out, w1, b1, w2, b2, want_control=False):
+        """As _MlpWidePlan.run_adjoint, with the state rows in two halves: per chunk of steps the sweep streams (U, G2 blocks,
+        G1, Z, Z_hi), each G2 block is reduced against U into its own image, G1 against Z and against Z_hi."""
+        if want_control:
+            raise NotImplementedError("torchcde_amd: the tall-state sweep has no control gradients")
+        lib = _lib.load()
+        g = self.grids
+        B, H, C = self.B, self.H, self.C
+        dev, f32 = self.device, _lib.dtype_enum(torch.float32)
+        weights = self._weights((w1, b1, w2, b2))
+        width = weights[0].size(0)
+        nbytes = lib.cde_rk4_adjoint_mlp_tall_workspace_bytes(g.n_sgrid)
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        stream = _lib.stream_ptr(dev)
+        tdt = _lib.dtype_enum(g.time_dtype)
+        z_saved = z_saved.detach().reshape(B, self.n_out, H)
+        grad_out = grad_out.detach().reshape(B, self.n_out, H)
+        # the sweep integrates (y, a) IN PLACE: private copies (see _MlpPlan.run_adjoint)
+        y = z_saved[:, -1].clone(memory_format=torch.contiguous_format)
+        a = grad_out[:, -1].to(torch.float32).clone(memory_format=torch.contiguous_format)
+        blocks = (H * ((C + 3) // 4 * 4) + 255) // 256
+        acc2 = torch.zeros(blocks, 256, 132, dtype=torch.float32, device=dev)
+        acc1 = torch.zeros(128, 36, dtype=torch.float32, device=dev)
+        acc1_hi = torch.zeros(128, 36, dtype=torch.float32, device=dev)
+        longest = max((g.seg_off_host[p + 1] - 1 - g.seg_off_host[p] for p in range(self.n_out - 1)), default=0)
+        self.steps_per_launch = 0                   # the chunking that ran (tests, tools)
+        if g.n_sgrid > 1 and longest > 0:
+            _lib.check(lib.cde_rk4_adjoint_mlp_tall_prepare(
+                _lib.ptr(self.knots), self.n_intervals, _lib.ptr(g.sgrid), g.n_sgrid, *_weight_args(weights), C, H, f32, tdt,
+                _lib.ptr(workspace), nbytes, stream), "cde_rk4_adjoint_mlp_tall_prepare")
+            row_bytes = (132 + 256 * blocks + 128 + 2 * 36) * 4
+            chunk = max(1, min(longest, self.scratch_budget // (row_bytes * 4 * B)))
+            self.steps_per_launch = chunk
+            rows = chunk * 4 * B
+            U = torch.zeros(rows, 132, dtype=torch.float32, device=dev)
+            U[:, 128] = 1
+            Z = torch.zeros(rows, 36, dtype=torch.float32, device=dev)
+            Z[:, 32] = 1
+            Z_hi = torch.zeros(rows, 36, dtype=torch.float32, device=dev)            # the sweep writes the units < H only
+            Z_hi[:, 32] = 1
+            G2 = torch.zeros(blocks * rows, 256, dtype=torch.float32, device=dev)    # the sweep writes the rows h < H only
+            G1 = torch.empty(rows, 128, dtype=torch.float32, device=dev)
+            reduce_ws = torch.empty(lib.cde_mlp_grad_reduce_workspace_bytes(), dtype=torch.uint8, device=dev)
+            for p in range(self.n_out - 1):
+                k, k_end = g.seg_off_host[p], g.seg_off_host[p + 1] - 1
+                while k < k_end:
+                    ke = min(k_end, k + chunk)
+                    _lib.check(lib.cde_rk4_adjoint_mlp_tall_sweep(
+                        _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, self.act, _lib.ptr(y),
+                        _lib.ptr(a), _lib.ptr(g.sgrid), g.n_sgrid, k, ke, _lib.ptr(U), _lib.ptr(G2), _lib.ptr(G1), _lib.ptr(Z),
+                        _lib.ptr(Z_hi), B, C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream), "cde_rk4_adjoint_mlp_tall_sweep")
+                    n = 4 * (ke - k) * B
+                    for b in range(blocks):         # block b starts n rows behind block b - 1
+                        _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G2[b * n:]), _lib.ptr(U), n, 2, _lib.ptr(acc2[b]),
+                                                           _lib.ptr(reduce_ws), reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
+                    for half, acc in ((Z, acc1), (Z_hi, acc1_hi)):
+                        _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G1), _lib.ptr(half), n, 1, _lib.ptr(acc), _lib.ptr(reduce_ws),
+                                                           reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
+                    k = ke
+                i_out = self.n_out - 1 - p
+                y.copy_(z_saved[:, i_out - 1])                 # torchdiffeq: re-seed z from the stored forward solution
+                a.add_(grad_out[:, i_out - 1])                 # and add the incoming gradient at that output time
+        return (a.reshape(*self.batch, H),) + _mlp_tall_gradients(acc1, acc1_hi, acc2, H, C, width) + (None,)
+
+    def run_backprop(self, *args, **kwargs):
+        raise NotImplementedError("torchcde_amd: tall hidden states have no reverse-mode (adjoint=False) kernels")
+
+
 def _reaches(tensor, leaf):
     """Does the autograd graph of `tensor` reach the leaf `leaf`?  (The coefficient tensor of a control fitted with the same
     knot tensor the spline is evaluated on: test/test_tricks.py:21-49.)"""
@@ -1012,6 +1122,18 @@ class _FusedMlp3RK4(torch.autograd.Function):
 
 class _FusedMlpWideRK4(torch.autograd.Function):
     """The two-layer field on a control of 17 .. 64 channels: K2mc forward, K3mc backward."""
+
+    @staticmethod
+    def forward(ctx, z0, w1, b1, w2, b2, plan, wants, t, knots, *control):
+        out = plan.run(z0)
+        _keep(ctx, plan, wants, t, knots, control, out, w1, b1, w2, b2)
+        return out
+
+    backward = staticmethod(_adjoint_backward)
+
+
+class _FusedMlpTallRK4(torch.autograd.Function):
+    """The two-layer field on a hidden state of 33 .. 64 channels: K2mh forward, K3mh backward."""
 
     @staticmethod
     def forward(ctx, z0, w1, b1, w2, b2, plan, wants, t, knots, *control):
@@ -1836,10 +1958,12 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
     # (`variant="generic"` keeps autograd: the independent cross-check the tests compare against)
     recognised = field if variant == _lib.VARIANT_AUTO else None
     recognised_kind = None if field is None else field.kind
-    mlp = mlp_wide = None
+    mlp = mlp_wide = mlp_tall = None
     if field is not None and field.kind == "mlp2":
         if _mlp_wide_fusable(field, H, C, z0, packed):      # 17 .. 64 channels: its own kernels, rk4 only (kind "mlp2w")
             mlp_wide, field = field, None
+        elif _mlp_tall_fusable(field, H, C, z0, packed):    # 33 .. 64 hidden channels: its own kernels, rk4 only (kind "mlp2h")
+            mlp_tall, field = field, None
         else:
             mlp, field = (field if _mlp_fusable(field, H, C, z0, packed) else None), None
     mlp3 = None
@@ -1901,7 +2025,8 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
     increasing = t_is_vector and (t_host.numel() == 1 or bool((t_host[1:] > t_host[:-1]).all()))
 
     # ---- how the caller's adjoint_params relate to the field's own parameters and the control's tensors
-    known = field if field is not None else mlp if mlp is not None else mlp3 if mlp3 is not None else mlp_wide
+    known = (field if field is not None else mlp if mlp is not None else mlp3 if mlp3 is not None else
+             mlp_wide if mlp_wide is not None else mlp_tall)
     own = () if known is None else (
         (field.weight, field.bias) if field is not None else
         tuple(p for lin in known.linears for p in (lin.weight, lin.bias)))     # two / three layers: all four / all six
@@ -1944,7 +2069,8 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
         adjoint_options_ok = within(fused_adj_opts, fixed_keys)
     from .distributed import step_control
     request = dispatch.Request(
-        prod=False, kind=None if known is None else "mlp2w" if mlp_wide is not None else known.kind,
+        prod=False, kind=(None if known is None else "mlp2w" if mlp_wide is not None else "mlp2h" if mlp_tall is not None
+                          else known.kind),
         tiles_ok=known is not None, mfma_shape=mfma_shape,
         method=method, adjoint=bool(adjoint), wants_grad=bool(wants_grad), wants_t=bool(wants_t),
         wants_control=bool(control_wants), params=params_kind,
@@ -2013,6 +2139,17 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
         plan = _MlpWidePlan(X, mlp_wide, batch, H, C, t, step, adj_step)
         return _FusedMlpWideRK4.apply(z0, mlp_wide.hidden.weight, mlp_wide.hidden.bias, mlp_wide.output.weight,
                                       mlp_wide.output.bias, plan, None, None, None)
+
+    # ---- two-layer fields on 33 .. 64 hidden channels (rk4 only: forward, and the continuous adjoint for z0 and the four parameters)
+    if mlp_tall is not None:
+        step = _parse_fixed_options(fused_options, "solver")
+        if choice.path == "mlp_rk4_forward":
+            with torch.no_grad():
+                return _MlpTallPlan(X, mlp_tall, batch, H, C, t, step).run(z0)
+        adj_step = step if fused_adj_opts is None else _parse_fixed_options(fused_adj_opts, "adjoint")
+        plan = _MlpTallPlan(X, mlp_tall, batch, H, C, t, step, adj_step)
+        return _FusedMlpTallRK4.apply(z0, mlp_tall.hidden.weight, mlp_tall.hidden.bias, mlp_tall.output.weight,
+                                      mlp_tall.output.bias, plan, None, None, None)
 
     # ---- two-layer fields
     if choice.path == "mlp_rk4_adjoint":
