@@ -1,5 +1,5 @@
 """The two-layer vector field on controls of 17 to 64 channels under rk4 on the GPU: the fused forward (K2mc) and
-continuous-adjoint sweep (K3mc, csrc/rk4_mlp_widec.hip) against the float64 oracle and the step-wise path; every other request
+continuous-adjoint sweep (K3mc, csrc/rk4_mlp_tiled.hip) against the float64 oracle and the step-wise path; every other request
 at these shapes runs step-wise with a reason.
 
 Shapes (H, C, width, degree, final, hidden): the full envelope; the first channel count beyond the old tiles with ragged rows

@@ -1,5 +1,5 @@
 """The two-layer vector field on hidden states of 33 to 64 channels under rk4 on the GPU: the fused forward (K2mh) and
-continuous-adjoint sweep (K3mh, csrc/rk4_mlp_tallh.hip) against the float64 oracle and the step-wise path; every other request
+continuous-adjoint sweep (K3mh, csrc/rk4_mlp_tiled.hip) against the float64 oracle and the step-wise path; every other request
 at these shapes runs step-wise with a reason.
 
 Shapes (H, C, width, degree, final, hidden): all 16 unit groups at full width; the first hidden size beyond the old tiles (the
@@ -153,7 +153,7 @@ def _train(native, ref, budget=None, **kw):
 
 
 # 4097 series are 257 tiles: the first batch size at which the launchers put two waves (each with its own dX slab) in a
-# workgroup (rk4_mlp_tallh.hip: tallh_waves)
+# workgroup (cde_launch.h: waves_per_workgroup)
 ADJOINT = ([(c, B_FULL, None, STEP, T_OUT) for c in CASES] + [(c, 1, None, STEP, T_OUT) for c in CASES] +
            [(CASES[1], 261, None, STEP, T_OUT), (CASES[0], B_FULL, 1, STEP, T_OUT), (CASES[1], B_FULL, None, 0.7, (0., 1.4, 2.5, 8.)),
             (CASES[1], 4097, None, STEP, T_OUT)])

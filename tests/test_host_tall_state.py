@@ -1,6 +1,6 @@
 """The two-layer field on hidden states of 33 to 64 channels as far as it goes without a GPU: the dispatch rows of kind "mlp2h",
 the envelope (host and library, and that at most one of the three two-layer envelopes claims a shape), the argument checks of
-the new entry points, and a restatement of the index maps of csrc/cde_mlp_tallh.h -- layer 1 over K = 64, the four tiles of
+the new entry points, and a restatement of the index maps of csrc/cde_mlp_tiled.h -- layer 1 over K = 64, the four tiles of
 va = W1^T g1, the state halves Z | Z_hi and the host's gather of dW1 | db1 -- against plain einsum at ragged shapes."""
 import itertools
 
@@ -277,7 +277,7 @@ def test_state_halves_and_the_gather_of_the_first_layer_gradient():
 
 def test_padded_rows_cover_the_last_unit_group():
     """The sweep's tiles of unit group P run over rows (4 P + 0 .. 3) CP + c: at most 4 ceil(H / 4) CP <= 2240 rows inside the
-    envelope (cde_mlp_tallh.h: TH_ROWS), and more than 2048 at some shapes -- the padded copies must be that long."""
+    envelope (cde_mlp_tiled.h: MlpTiled<4>::ROWS), and more than 2048 at some shapes -- the padded copies must be that long."""
     worst = 0
     for H in range(33, 65):
         for C in range(1, 65):

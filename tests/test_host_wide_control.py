@@ -1,6 +1,6 @@
 """The two-layer field on controls of 17 to 64 channels as far as it goes without a GPU: the dispatch rows of kind "mlp2w", the
 envelope (host and library), the argument checks of the new entry points, and a lane-level restatement of the index maps of
-csrc/rk4_mlp_widec.hip / cde_mlp_widec.h -- the output layer's tiles, the dX slab, the padded copies of the sweep, the G2 blocks
+csrc/rk4_mlp_tiled.hip / cde_mlp_tiled.h -- the output layer's tiles, the dX slab, the padded copies of the sweep, the G2 blocks
 and the host's gather of dW2 | db2 from the reduced block images -- against plain einsum at ragged shapes."""
 import itertools
 
@@ -182,7 +182,7 @@ def test_wide_control_entry_points_reject_bad_calls_without_a_gpu():
 
 # ------------------------------------------------------------------------------------------------ the index maps
 LANES = [(l & 15, l >> 4) for l in range(64)]                                 # lane -> (n, q)
-SLAB_STRIDE = 68                                                               # cde_mlp_widec.h: WC_SLAB_STRIDE
+SLAB_STRIDE = 68                                                               # cde_mlp_tiled.h: TL_SLAB_STRIDE
 ROWS, MW = 2048, 128                                                           # rows / columns of the sweep's padded copies
 
 
@@ -262,7 +262,7 @@ def test_control_slope_slab_from_the_packed_coefficients(H, C, w):
 
 @pytest.mark.parametrize("H,C,w", SHAPES)
 def test_output_layer_tiles_of_the_forward_kernel(H, C, w):
-    """rk4_forward_mlp_widec: per unit group P and tile tb the lane's A operands from the caller's W2 (vector and scalar form:
+    """rk4_forward_mlp_tiled: per unit group P and tile tb the lane's A operands from the caller's W2 (vector and scalar form:
     the same guards), the bias as the accumulator's initial value, the 32 K steps on layer 1's fragment, tanh, and the
     contraction with the slab -- f for unit 4 P + q of series n, against einsum.  No read leaves W2 / b2."""
     W2, b2, u, dX, _ = _inputs(H, C, w, 3)
@@ -304,7 +304,7 @@ def test_output_layer_tiles_of_the_forward_kernel(H, C, w):
 
 
 def _sweep_images(W2, b2, H, C, w):
-    """widec_adj_image_kernel: b2 at h CP + c; the plain copy [row][col]; the gu copy [row][8 n + T1] = W2[row][16 T1 + n]"""
+    """mlp_tiled_adj_image_kernel: b2 at h CP + c; the plain copy [row][col]; the gu copy [row][8 n + T1] = W2[row][16 T1 + n]"""
     CP = (C + 3) // 4 * 4
     b2p, w2p, w2t = np.zeros(ROWS), np.zeros((ROWS, MW)), np.zeros((ROWS, MW))
     for row in range(ROWS):
@@ -321,7 +321,7 @@ def _sweep_images(W2, b2, H, C, w):
 
 @pytest.mark.parametrize("H,C,w", SHAPES)
 def test_sweep_tiles_g2_blocks_and_the_gradient_gather(H, C, w):
-    """rk4_adjoint_mlp_widec_sweep on one (stage, series-tile): Y2 from the padded plain copy, g2 = a_h dX_c (1 - tanh^2) into
+    """rk4_adjoint_mlp_tiled_sweep on one (stage, series-tile): Y2 from the padded plain copy, g2 = a_h dX_c (1 - tanh^2) into
     the G2 blocks (block at >> 8, column at & 255 of at = h CP + c; rows h >= H never written), gu = W2^T g2 through the gu
     copy in layer 1's fragment form; then the reduction G2_b^T [U | 1] per block and the host's gather
     (cdeint._mlp_wide_gradients) -- against einsum."""

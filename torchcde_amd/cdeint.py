@@ -733,7 +733,7 @@ class _Mlp3Plan(_MlpPlan):
 
 
 def _mlp_wide_fusable(field, H, C, z0, packed):
-    """The envelope of the wide-control kernels (csrc/rk4_mlp_widec.hip; cde_mi355x.h: cde_rk4_forward_mlp_wide): float32,
+    """The envelope of the wide-control kernels (csrc/rk4_mlp_tiled.hip, NV = 2; cde_mi355x.h: cde_rk4_forward_mlp_wide): float32,
     H <= 32, 16 < C <= 64, width <= 128 -- the channel counts beyond every tile form of _mlp_fusable (whose 32 x 16 upper-half
     form keeps the shapes it claims)."""
     w1, w2 = field.hidden.weight, field.output.weight
@@ -752,15 +752,22 @@ def _mlp_wide_gradients(acc1, acc2, H, C, width):
             rows[:, :, 128].reshape(H * C))
 
 
-class _MlpWidePlan(_MlpPlan):
-    """Fused RK4 solves for the two-layer field on a control of 17 .. 64 channels: forward (K2mc, cde_rk4_forward_mlp_wide)
-    and continuous-adjoint backward (K3mc sweep, cde_rk4_adjoint_mlp_wide_*, + one factor reduction per 256-column block of
-    the output layer's gradient).  One wave per 16 series at every batch size."""
+class _MlpTiledPlan(_MlpPlan):
+    """Fused RK4 solves for the two-layer field with its output layer worked tile by tile (csrc/rk4_mlp_tiled.hip): forward
+    (cde_rk4_forward_mlp_<form>) and continuous-adjoint backward (the sweep, cde_rk4_adjoint_mlp_<form>_*, + one factor
+    reduction per 256-column block of the output layer's gradient and one per 32-unit half of the state).  One wave per 16
+    series at every batch size.  A subclass names the form: the entry points' infix, the number of Z halves, and what the
+    messages call the shape."""
+    form = z_halves = shape_noun = sweep_noun = None
+
+    def _entry(self, name):
+        """(the entry point `name` with the form's infix, its name for messages)"""
+        name = name % self.form
+        return getattr(_lib.load(), name), name
 
     def run(self, z0, stages=False):
         if stages:
-            raise NotImplementedError("torchcde_amd: wide controls have no reverse-mode (adjoint=False) kernels")
-        lib = _lib.load()
+            raise NotImplementedError("torchcde_amd: %s have no reverse-mode (adjoint=False) kernels" % self.shape_noun)
         g = self.grids
         out = torch.empty(self.B, g.n_out, self.H, dtype=torch.float32, device=self.device)
         n_steps = max(g.grid.numel() - 1, 0)
@@ -768,25 +775,27 @@ class _MlpWidePlan(_MlpPlan):
         stage_frac = torch.empty(max(4 * n_steps, 1), dtype=torch.float32, device=self.device)
         z0c = z0.detach().reshape(self.B, self.H).contiguous()
         weights = self._weights()
-        _lib.check(lib.cde_rk4_forward_mlp_wide(
+        forward, name = self._entry("cde_rk4_forward_mlp_%s")
+        _lib.check(forward(
             _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, *_weight_args(weights), self.act,
             _lib.ptr(z0c), _lib.ptr(g.grid), g.grid.numel(), _lib.ptr(g.t_out), g.n_out, _lib.ptr(out), self.B, self.C, self.H,
             _lib.dtype_enum(torch.float32), _lib.dtype_enum(g.time_dtype), _lib.ptr(stage_index), _lib.ptr(stage_frac),
-            _lib.stream_ptr(self.device)), "cde_rk4_forward_mlp_wide")
+            _lib.stream_ptr(self.device)), name)
         return out.reshape(*self.batch, g.n_out, self.H)
 
     def run_adjoint(self, z_saved, grad_out, w1, b1, w2, b2, want_control=False):
-        """As _MlpPlan.run_adjoint, with the output layer's dL/dY2 rows in blocks of 256 columns: per chunk of steps the sweep
-        streams (U, G2 blocks, G1, Z), each block is reduced against U into its own image, G1 against Z."""
+        """As _MlpPlan.run_adjoint, with the output layer's dL/dY2 rows in blocks of 256 columns and the state rows in halves
+        of 32 units: per chunk of steps the sweep streams (U, G2 blocks, G1, Z halves), each G2 block is reduced against U
+        into its own image, G1 against every Z half."""
         if want_control:
-            raise NotImplementedError("torchcde_amd: the wide-control sweep has no control gradients")
+            raise NotImplementedError("torchcde_amd: the %s sweep has no control gradients" % self.sweep_noun)
         lib = _lib.load()
         g = self.grids
         B, H, C = self.B, self.H, self.C
         dev, f32 = self.device, _lib.dtype_enum(torch.float32)
         weights = self._weights((w1, b1, w2, b2))
         width = weights[0].size(0)
-        nbytes = lib.cde_rk4_adjoint_mlp_wide_workspace_bytes(g.n_sgrid)
+        nbytes = self._entry("cde_rk4_adjoint_mlp_%s_workspace_bytes")[0](g.n_sgrid)
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         stream = _lib.stream_ptr(dev)
         tdt = _lib.dtype_enum(g.time_dtype)
@@ -797,50 +806,61 @@ class _MlpWidePlan(_MlpPlan):
         a = grad_out[:, -1].to(torch.float32).clone(memory_format=torch.contiguous_format)
         blocks = (H * ((C + 3) // 4 * 4) + 255) // 256
         acc2 = torch.zeros(blocks, 256, 132, dtype=torch.float32, device=dev)
-        acc1 = torch.zeros(128, 36, dtype=torch.float32, device=dev)
+        acc1 = [torch.zeros(128, 36, dtype=torch.float32, device=dev) for _ in range(self.z_halves)]
         longest = max((g.seg_off_host[p + 1] - 1 - g.seg_off_host[p] for p in range(self.n_out - 1)), default=0)
         self.steps_per_launch = 0                   # the chunking that ran (tests, tools)
         if g.n_sgrid > 1 and longest > 0:
-            _lib.check(lib.cde_rk4_adjoint_mlp_wide_prepare(
+            prepare, name = self._entry("cde_rk4_adjoint_mlp_%s_prepare")
+            _lib.check(prepare(
                 _lib.ptr(self.knots), self.n_intervals, _lib.ptr(g.sgrid), g.n_sgrid, *_weight_args(weights), C, H, f32, tdt,
-                _lib.ptr(workspace), nbytes, stream), "cde_rk4_adjoint_mlp_wide_prepare")
-            row_bytes = (132 + 256 * blocks + 128 + 36) * 4
+                _lib.ptr(workspace), nbytes, stream), name)
+            row_bytes = (132 + 256 * blocks + 128 + self.z_halves * 36) * 4
             chunk = max(1, min(longest, self.scratch_budget // (row_bytes * 4 * B)))
             self.steps_per_launch = chunk
             rows = chunk * 4 * B
             U = torch.zeros(rows, 132, dtype=torch.float32, device=dev)
             U[:, 128] = 1
-            Z = torch.zeros(rows, 36, dtype=torch.float32, device=dev)
-            Z[:, 32] = 1
+            Z = []
+            for _ in range(self.z_halves):          # (of the last half the sweep writes the units < H only)
+                Z.append(torch.zeros(rows, 36, dtype=torch.float32, device=dev))
+                Z[-1][:, 32] = 1
             G2 = torch.zeros(blocks * rows, 256, dtype=torch.float32, device=dev)    # the sweep writes the rows h < H only
             G1 = torch.empty(rows, 128, dtype=torch.float32, device=dev)
             reduce_ws = torch.empty(lib.cde_mlp_grad_reduce_workspace_bytes(), dtype=torch.uint8, device=dev)
+            sweep, name = self._entry("cde_rk4_adjoint_mlp_%s_sweep")
             for p in range(self.n_out - 1):
                 k, k_end = g.seg_off_host[p], g.seg_off_host[p + 1] - 1
                 while k < k_end:
                     ke = min(k_end, k + chunk)
-                    _lib.check(lib.cde_rk4_adjoint_mlp_wide_sweep(
+                    _lib.check(sweep(
                         _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, self.act, _lib.ptr(y),
-                        _lib.ptr(a), _lib.ptr(g.sgrid), g.n_sgrid, k, ke, _lib.ptr(U), _lib.ptr(G2), _lib.ptr(G1), _lib.ptr(Z),
-                        B, C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream), "cde_rk4_adjoint_mlp_wide_sweep")
+                        _lib.ptr(a), _lib.ptr(g.sgrid), g.n_sgrid, k, ke, _lib.ptr(U), _lib.ptr(G2), _lib.ptr(G1),
+                        *(_lib.ptr(half) for half in Z), B, C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream), name)
                     n = 4 * (ke - k) * B
                     for b in range(blocks):         # block b starts n rows behind block b - 1
                         _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G2[b * n:]), _lib.ptr(U), n, 2, _lib.ptr(acc2[b]),
                                                            _lib.ptr(reduce_ws), reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
-                    _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G1), _lib.ptr(Z), n, 1, _lib.ptr(acc1), _lib.ptr(reduce_ws),
-                                                       reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
+                    for half, acc in zip(Z, acc1):
+                        _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G1), _lib.ptr(half), n, 1, _lib.ptr(acc), _lib.ptr(reduce_ws),
+                                                           reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
                     k = ke
                 i_out = self.n_out - 1 - p
                 y.copy_(z_saved[:, i_out - 1])                 # torchdiffeq: re-seed z from the stored forward solution
                 a.add_(grad_out[:, i_out - 1])                 # and add the incoming gradient at that output time
-        return (a.reshape(*self.batch, H),) + _mlp_wide_gradients(acc1, acc2, H, C, width) + (None,)
+        gradients = _mlp_wide_gradients if self.z_halves == 1 else _mlp_tall_gradients
+        return (a.reshape(*self.batch, H),) + gradients(*acc1, acc2, H, C, width) + (None,)
 
     def run_backprop(self, *args, **kwargs):
-        raise NotImplementedError("torchcde_amd: wide controls have no reverse-mode (adjoint=False) kernels")
+        raise NotImplementedError("torchcde_amd: %s have no reverse-mode (adjoint=False) kernels" % self.shape_noun)
+
+
+class _MlpWidePlan(_MlpTiledPlan):
+    """The two-layer field on a control of 17 .. 64 channels (NV = 2: K2mc forward, K3mc sweep)."""
+    form, z_halves, shape_noun, sweep_noun = "wide", 1, "wide controls", "wide-control"
 
 
 def _mlp_tall_fusable(field, H, C, z0, packed):
-    """The envelope of the tall-state kernels (csrc/rk4_mlp_tallh.hip; cde_mi355x.h: cde_rk4_forward_mlp_tall): float32,
+    """The envelope of the tall-state kernels (csrc/rk4_mlp_tiled.hip, NV = 4; cde_mi355x.h: cde_rk4_forward_mlp_tall): float32,
     32 < H <= 64, C <= 64 with H * CP <= 2048 (CP = C rounded up to 4), width <= 128 -- the hidden sizes beyond every tile
     form of _mlp_fusable and _mlp_wide_fusable, which both stop at H = 32."""
     w1, w2 = field.hidden.weight, field.output.weight
@@ -857,96 +877,9 @@ def _mlp_tall_gradients(acc1, acc1_hi, acc2, H, C, width):
     return (g_w1, acc1[:width, 32].contiguous()) + _mlp_wide_gradients(acc1, acc2, H, C, width)[2:]
 
 
-class _MlpTallPlan(_MlpPlan):
-    """Fused RK4 solves for the two-layer field on a hidden state of 33 .. 64 channels: forward (K2mh,
-    cde_rk4_forward_mlp_tall) and continuous-adjoint backward (K3mh sweep, cde_rk4_adjoint_mlp_tall_*, + one factor
-    reduction per 256-column block of the output layer's gradient and one per 32-unit half of the state).  One wave per 16
-    series at every batch size."""
-
-    def run(self, z0, stages=False):
-        if stages:
-            raise NotImplementedError("torchcde_amd: tall hidden states have no reverse-mode (adjoint=False) kernels")
-        lib = _lib.load()
-        g = self.grids
-        out = torch.empty(self.B, g.n_out, self.H, dtype=torch.float32, device=self.device)
-        n_steps = max(g.grid.numel() - 1, 0)
-        stage_index = torch.empty(max(4 * n_steps, 1), dtype=torch.int64, device=self.device)
-        stage_frac = torch.empty(max(4 * n_steps, 1), dtype=torch.float32, device=self.device)
-        z0c = z0.detach().reshape(self.B, self.H).contiguous()
-        weights = self._weights()
-        _lib.check(lib.cde_rk4_forward_mlp_tall(
-            _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, *_weight_args(weights), self.act,
-            _lib.ptr(z0c), _lib.ptr(g.grid), g.grid.numel(), _lib.ptr(g.t_out), g.n_out, _lib.ptr(out), self.B, self.C, self.H,
-            _lib.dtype_enum(torch.float32), _lib.dtype_enum(g.time_dtype), _lib.ptr(stage_index), _lib.ptr(stage_frac),
-            _lib.stream_ptr(self.device)), "cde_rk4_forward_mlp_tall")
-        return out.reshape(*self.batch, g.n_out, self.H)
-
-    def run_adjoint(self, z_saved, grad_out, w1, b1, w2, b2, want_control=False):
-        """As _MlpWidePlan.run_adjoint, with the state rows in two halves: per chunk of steps the sweep streams (U, G2 blocks,
-        G1, Z, Z_hi), each G2 block is reduced against U into its own image, G1 against Z and against Z_hi."""
-        if want_control:
-            raise NotImplementedError("torchcde_amd: the tall-state sweep has no control gradients")
-        lib = _lib.load()
-        g = self.grids
-        B, H, C = self.B, self.H, self.C
-        dev, f32 = self.device, _lib.dtype_enum(torch.float32)
-        weights = self._weights((w1, b1, w2, b2))
-        width = weights[0].size(0)
-        nbytes = lib.cde_rk4_adjoint_mlp_tall_workspace_bytes(g.n_sgrid)
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        stream = _lib.stream_ptr(dev)
-        tdt = _lib.dtype_enum(g.time_dtype)
-        z_saved = z_saved.detach().reshape(B, self.n_out, H)
-        grad_out = grad_out.detach().reshape(B, self.n_out, H)
-        # the sweep integrates (y, a) IN PLACE: private copies (see _MlpPlan.run_adjoint)
-        y = z_saved[:, -1].clone(memory_format=torch.contiguous_format)
-        a = grad_out[:, -1].to(torch.float32).clone(memory_format=torch.contiguous_format)
-        blocks = (H * ((C + 3) // 4 * 4) + 255) // 256
-        acc2 = torch.zeros(blocks, 256, 132, dtype=torch.float32, device=dev)
-        acc1 = torch.zeros(128, 36, dtype=torch.float32, device=dev)
-        acc1_hi = torch.zeros(128, 36, dtype=torch.float32, device=dev)
-        longest = max((g.seg_off_host[p + 1] - 1 - g.seg_off_host[p] for p in range(self.n_out - 1)), default=0)
-        self.steps_per_launch = 0                   # the chunking that ran (tests, tools)
-        if g.n_sgrid > 1 and longest > 0:
-            _lib.check(lib.cde_rk4_adjoint_mlp_tall_prepare(
-                _lib.ptr(self.knots), self.n_intervals, _lib.ptr(g.sgrid), g.n_sgrid, *_weight_args(weights), C, H, f32, tdt,
-                _lib.ptr(workspace), nbytes, stream), "cde_rk4_adjoint_mlp_tall_prepare")
-            row_bytes = (132 + 256 * blocks + 128 + 2 * 36) * 4
-            chunk = max(1, min(longest, self.scratch_budget // (row_bytes * 4 * B)))
-            self.steps_per_launch = chunk
-            rows = chunk * 4 * B
-            U = torch.zeros(rows, 132, dtype=torch.float32, device=dev)
-            U[:, 128] = 1
-            Z = torch.zeros(rows, 36, dtype=torch.float32, device=dev)
-            Z[:, 32] = 1
-            Z_hi = torch.zeros(rows, 36, dtype=torch.float32, device=dev)            # the sweep writes the units < H only
-            Z_hi[:, 32] = 1
-            G2 = torch.zeros(blocks * rows, 256, dtype=torch.float32, device=dev)    # the sweep writes the rows h < H only
-            G1 = torch.empty(rows, 128, dtype=torch.float32, device=dev)
-            reduce_ws = torch.empty(lib.cde_mlp_grad_reduce_workspace_bytes(), dtype=torch.uint8, device=dev)
-            for p in range(self.n_out - 1):
-                k, k_end = g.seg_off_host[p], g.seg_off_host[p + 1] - 1
-                while k < k_end:
-                    ke = min(k_end, k + chunk)
-                    _lib.check(lib.cde_rk4_adjoint_mlp_tall_sweep(
-                        _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, self.act, _lib.ptr(y),
-                        _lib.ptr(a), _lib.ptr(g.sgrid), g.n_sgrid, k, ke, _lib.ptr(U), _lib.ptr(G2), _lib.ptr(G1), _lib.ptr(Z),
-                        _lib.ptr(Z_hi), B, C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream), "cde_rk4_adjoint_mlp_tall_sweep")
-                    n = 4 * (ke - k) * B
-                    for b in range(blocks):         # block b starts n rows behind block b - 1
-                        _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G2[b * n:]), _lib.ptr(U), n, 2, _lib.ptr(acc2[b]),
-                                                           _lib.ptr(reduce_ws), reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
-                    for half, acc in ((Z, acc1), (Z_hi, acc1_hi)):
-                        _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G1), _lib.ptr(half), n, 1, _lib.ptr(acc), _lib.ptr(reduce_ws),
-                                                           reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
-                    k = ke
-                i_out = self.n_out - 1 - p
-                y.copy_(z_saved[:, i_out - 1])                 # torchdiffeq: re-seed z from the stored forward solution
-                a.add_(grad_out[:, i_out - 1])                 # and add the incoming gradient at that output time
-        return (a.reshape(*self.batch, H),) + _mlp_tall_gradients(acc1, acc1_hi, acc2, H, C, width) + (None,)
-
-    def run_backprop(self, *args, **kwargs):
-        raise NotImplementedError("torchcde_amd: tall hidden states have no reverse-mode (adjoint=False) kernels")
+class _MlpTallPlan(_MlpTiledPlan):
+    """The two-layer field on a hidden state of 33 .. 64 channels (NV = 4: K2mh forward, K3mh sweep; Z and Z_hi)."""
+    form, z_halves, shape_noun, sweep_noun = "tall", 2, "tall hidden states", "tall-state"
 
 
 def _reaches(tensor, leaf):
@@ -1132,16 +1065,8 @@ class _FusedMlpWideRK4(torch.autograd.Function):
     backward = staticmethod(_adjoint_backward)
 
 
-class _FusedMlpTallRK4(torch.autograd.Function):
+class _FusedMlpTallRK4(_FusedMlpWideRK4):
     """The two-layer field on a hidden state of 33 .. 64 channels: K2mh forward, K3mh backward."""
-
-    @staticmethod
-    def forward(ctx, z0, w1, b1, w2, b2, plan, wants, t, knots, *control):
-        out = plan.run(z0)
-        _keep(ctx, plan, wants, t, knots, control, out, w1, b1, w2, b2)
-        return out
-
-    backward = staticmethod(_adjoint_backward)
 
 
 class _FusedRK4Backprop(torch.autograd.Function):

@@ -3,8 +3,7 @@
 #include "cde_common.h"
 #include "cde_launch.h"
 #include "cde_mlp3.h"
-#include "cde_mlp_widec.h"
-#include "cde_mlp_tallh.h"
+#include "cde_mlp_tiled.h"
 
 namespace cde {
 
@@ -731,16 +730,85 @@ extern "C" int cde_rk4_adjoint_mlp3_sweep(const void* coeffs, const void* knots,
   });
 }
 
-// ---------------------------------------------------------------------------------------------- K2mc / K3mc (17 .. 64 channels)
-// argument checks in the siblings' order, all before the first HIP call: sizes, dtype, (forward) the empty batch, the
-// envelope of rk4_mlp_widec.hip, pointers, workspace
-extern "C" int cde_rk4_mlp_wide_supported(int64_t C, int64_t H, int64_t width, int dtype, int act) {
-  return (dtype == CDE_F32 && field_act_known(act) && mlp_widec_shape_ok(C, H, width)) ? 1 : 0;
+// ------------------------------------------------------ K2mc / K3mc (17 .. 64 channels), K2mh / K3mh (33 .. 64 hidden channels)
+// One implementation over the state vectors per lane (rk4_mlp_tiled.hip: NV = 2 behind *_mlp_wide_*, NV = 4 behind
+// *_mlp_tall_*).  Argument checks in the siblings' order, all before the first HIP call: sizes, dtype, (forward) the empty
+// batch, the envelope of the form, pointers, workspace
+template <int NV>
+static int mlp_tiled_supported(int64_t C, int64_t H, int64_t width, int dtype, int act) {
+  return (dtype == CDE_F32 && field_act_known(act) && MlpTiled<NV>::shape_ok(C, H, width)) ? 1 : 0;
 }
 
-static int mlp_wide_envelope(int64_t C, int64_t H, int64_t width, int dtype, int act) {
+template <int NV>
+static int mlp_tiled_envelope(int64_t C, int64_t H, int64_t width, int dtype, int act) {
   if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
-  return cde_rk4_mlp_wide_supported(C, H, width, dtype, act) ? CDE_OK : CDE_ERR_UNSUPPORTED;
+  return mlp_tiled_supported<NV>(C, H, width, dtype, act) ? CDE_OK : CDE_ERR_UNSUPPORTED;
+}
+
+template <int NV>
+static int mlp_tiled_forward(const Control& x, const TwoLayerField& f, const ForwardIO& io, const Shape& n, Dtypes dt,
+                             const StageBuffers& st, void* stream) {
+  if (n.B < 0 || n.C < 1 || n.H < 1 || f.width < 1 || x.n_intervals < 1 || io.n_grid < 1 || io.n_out < 1) return CDE_ERR_SHAPE;
+  if (dt.state != CDE_F32 && dt.state != CDE_F64) return CDE_ERR_DTYPE;
+  if (n.B == 0) return CDE_OK;
+  const int rc = mlp_tiled_envelope<NV>(n.C, n.H, f.width, dt.state, f.act);
+  if (rc != CDE_OK) return rc;
+  if (!x.coeffs || !x.knots || !f.W1 || !f.bias1 || !f.W2 || !f.bias2 || !io.z0 || !io.grid || !io.t_out || !io.z_out)
+    return CDE_ERR_NULL;
+  if (io.n_grid > 1 && (!st.index || !st.frac)) return CDE_ERR_NULL;
+  hipStream_t s = (hipStream_t)stream;
+  return forward_solve(dt, x, io, CDE_METHOD_RK4, st, s, [&](auto, auto tt) {
+    return launch_forward_mlp_tiled<NV, typename decltype(tt)::type>(x, f, io, n, st, s);
+  });
+}
+
+// workspace: [stage_index: 4*(n_sgrid-1) int64][stage_frac: 4*(n_sgrid-1) f32][layer-1 images and the padded output-layer copies]
+template <int NV>
+static size_t mlp_tiled_workspace_bytes(int64_t n_sgrid) {
+  return StageWorkspace(n_sgrid, sizeof(float)).total(align256(mlp_tiled_adjoint_image_bytes<NV>()));
+}
+
+template <int NV>
+static int mlp_tiled_prepare(const void* knots, int64_t n_intervals, const void* sgrid, int64_t n_sgrid, const TwoLayerField& f,
+                             int64_t C, int64_t H, Dtypes dt, Workspace ws, void* stream) {
+  if (C < 1 || H < 1 || f.width < 1 || n_intervals < 1 || n_sgrid < 0) return CDE_ERR_SHAPE;
+  const int rc = mlp_tiled_envelope<NV>(C, H, f.width, dt.state, CDE_ACT_NONE);
+  if (rc != CDE_OK) return rc;
+  if (!knots || !f.W1 || !f.bias1 || !f.W2 || !f.bias2 || !ws.base || (n_sgrid > 1 && !sgrid)) return CDE_ERR_NULL;
+  if (ws.bytes < mlp_tiled_workspace_bytes<NV>(n_sgrid)) return CDE_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const Control x{nullptr, knots, n_intervals, 0};
+  const StageWorkspace layout(n_sgrid, sizeof(float));
+  const int table = dispatch_dtype(dt.time, [&](auto tt) {
+    return fill_stage_table<float, typename decltype(tt)::type>(x, sgrid, layout.n_steps, 1, CDE_METHOD_RK4,
+                                                                layout.table(ws.base), s);
+  });
+  if (table != CDE_OK) return table;
+  return launch_mlp_tiled_adjoint_images<NV>(f, C, H, (float*)layout.tail(ws.base), s);
+}
+
+// `io.image` is filled in here; `io.Z_hi` is read by NV = 4 alone
+template <int NV>
+static int mlp_tiled_sweep(const Control& x, TiledSweepIO io, int64_t n_sgrid, const Shape& n, Dtypes dt, Workspace ws,
+                           void* stream) {
+  if (n.B < 1 || n.C < 1 || n.H < 1 || x.n_intervals < 1 || io.k_begin < 0 || io.k_end < io.k_begin || io.k_end > n_sgrid - 1)
+    return CDE_ERR_SHAPE;
+  const int rc = mlp_tiled_envelope<NV>(n.C, n.H, 1, dt.state, io.act);
+  if (rc != CDE_OK) return rc;
+  if (!x.coeffs || !x.knots || !io.y_state || !io.a_state || !io.grid || !io.U || !io.G2 || !io.G1 || !io.Z ||
+      (NV == 4 && !io.Z_hi) || !ws.base)
+    return CDE_ERR_NULL;
+  if (ws.bytes < mlp_tiled_workspace_bytes<NV>(n_sgrid)) return CDE_ERR_WORKSPACE;
+  const StageWorkspace layout(n_sgrid, sizeof(float));
+  const StageTable st = layout.table(ws.base);
+  io.image = (const float*)layout.tail(ws.base);
+  return dispatch_dtype(dt.time, [&](auto tt) {
+    return launch_mlp_tiled_adjoint_sweep<NV, typename decltype(tt)::type>(x, io, n, st, (hipStream_t)stream);
+  });
+}
+
+extern "C" int cde_rk4_mlp_wide_supported(int64_t C, int64_t H, int64_t width, int dtype, int act) {
+  return mlp_tiled_supported<2>(C, H, width, dtype, act);
 }
 
 extern "C" int cde_rk4_forward_mlp_wide(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
@@ -748,48 +816,19 @@ extern "C" int cde_rk4_forward_mlp_wide(const void* coeffs, const void* knots, i
                                         const void* z0, const void* grid, int64_t n_grid, const void* t_out, int64_t n_out,
                                         void* z_out, int64_t B, int64_t C, int64_t H, int dtype, int time_dtype,
                                         int64_t* stage_index, void* stage_frac, void* stream) {
-  if (B < 0 || C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_grid < 1 || n_out < 1) return CDE_ERR_SHAPE;
-  if (dtype != CDE_F32 && dtype != CDE_F64) return CDE_ERR_DTYPE;
-  if (B == 0) return CDE_OK;
-  const int rc = mlp_wide_envelope(C, H, width, dtype, act);
-  if (rc != CDE_OK) return rc;
-  if (!coeffs || !knots || !W1 || !bias1 || !W2 || !bias2 || !z0 || !grid || !t_out || !z_out) return CDE_ERR_NULL;
-  if (n_grid > 1 && (!stage_index || !stage_frac)) return CDE_ERR_NULL;
-  const Control x{coeffs, knots, n_intervals, degree};
-  const TwoLayerField f{W1, bias1, width, W2, bias2, act};
-  const ForwardIO io{z0, grid, n_grid, t_out, n_out, z_out, nullptr};
-  const Shape n{B, C, H};
-  const StageBuffers st{stage_index, stage_frac};
-  hipStream_t s = (hipStream_t)stream;
-  return forward_solve(Dtypes{dtype, time_dtype}, x, io, CDE_METHOD_RK4, st, s, [&](auto, auto tt) {
-    return launch_forward_mlp_widec<typename decltype(tt)::type>(x, f, io, n, st, s);
-  });
+  return mlp_tiled_forward<2>(Control{coeffs, knots, n_intervals, degree}, TwoLayerField{W1, bias1, width, W2, bias2, act},
+                              ForwardIO{z0, grid, n_grid, t_out, n_out, z_out, nullptr}, Shape{B, C, H},
+                              Dtypes{dtype, time_dtype}, StageBuffers{stage_index, stage_frac}, stream);
 }
 
-// workspace: [stage_index: 4*(n_sgrid-1) int64][stage_frac: 4*(n_sgrid-1) f32][layer-1 images and the padded output-layer copies]
-extern "C" size_t cde_rk4_adjoint_mlp_wide_workspace_bytes(int64_t n_sgrid) {
-  return StageWorkspace(n_sgrid, sizeof(float)).total(align256(mlp_widec_adjoint_image_bytes()));
-}
+extern "C" size_t cde_rk4_adjoint_mlp_wide_workspace_bytes(int64_t n_sgrid) { return mlp_tiled_workspace_bytes<2>(n_sgrid); }
 
 extern "C" int cde_rk4_adjoint_mlp_wide_prepare(const void* knots, int64_t n_intervals, const void* sgrid, int64_t n_sgrid,
                                                 const void* W1, const void* bias1, int64_t width, const void* W2,
                                                 const void* bias2, int64_t C, int64_t H, int dtype, int time_dtype,
                                                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_sgrid < 0) return CDE_ERR_SHAPE;
-  const int rc = mlp_wide_envelope(C, H, width, dtype, CDE_ACT_NONE);
-  if (rc != CDE_OK) return rc;
-  if (!knots || !W1 || !bias1 || !W2 || !bias2 || !workspace || (n_sgrid > 1 && !sgrid)) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_rk4_adjoint_mlp_wide_workspace_bytes(n_sgrid)) return CDE_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const Control x{nullptr, knots, n_intervals, 0};
-  const StageWorkspace layout(n_sgrid, sizeof(float));
-  const int table = dispatch_dtype(time_dtype, [&](auto tt) {
-    return fill_stage_table<float, typename decltype(tt)::type>(x, sgrid, layout.n_steps, 1, CDE_METHOD_RK4,
-                                                                layout.table(workspace), s);
-  });
-  if (table != CDE_OK) return table;
-  return launch_mlp_widec_adjoint_images(TwoLayerField{W1, bias1, width, W2, bias2, CDE_ACT_NONE}, C, H,
-                                         (float*)layout.tail(workspace), s);
+  return mlp_tiled_prepare<2>(knots, n_intervals, sgrid, n_sgrid, TwoLayerField{W1, bias1, width, W2, bias2, CDE_ACT_NONE}, C, H,
+                              Dtypes{dtype, time_dtype}, Workspace{workspace, workspace_bytes}, stream);
 }
 
 extern "C" int cde_rk4_adjoint_mlp_wide_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
@@ -797,30 +836,13 @@ extern "C" int cde_rk4_adjoint_mlp_wide_sweep(const void* coeffs, const void* kn
                                               int64_t k_begin, int64_t k_end, void* U, void* G2, void* G1, void* Z, int64_t B,
                                               int64_t C, int64_t H, int dtype, int time_dtype, const void* workspace,
                                               size_t workspace_bytes, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || n_intervals < 1 || k_begin < 0 || k_end < k_begin || k_end > n_sgrid - 1) return CDE_ERR_SHAPE;
-  const int rc = mlp_wide_envelope(C, H, 1, dtype, act);
-  if (rc != CDE_OK) return rc;
-  if (!coeffs || !knots || !y_state || !a_state || !sgrid || !U || !G2 || !G1 || !Z || !workspace) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_rk4_adjoint_mlp_wide_workspace_bytes(n_sgrid)) return CDE_ERR_WORKSPACE;
-  const StageWorkspace layout(n_sgrid, sizeof(float));
-  const StageTable st = layout.table(workspace);
-  const Control x{coeffs, knots, n_intervals, degree};
-  const WideSweepIO io{(const float*)layout.tail(workspace), act, y_state, a_state, sgrid, k_begin, k_end, U, G2, G1, Z};
-  return dispatch_dtype(time_dtype, [&](auto tt) {
-    return launch_mlp_widec_adjoint_sweep<typename decltype(tt)::type>(x, io, Shape{B, C, H}, st, (hipStream_t)stream);
-  });
+  return mlp_tiled_sweep<2>(Control{coeffs, knots, n_intervals, degree},
+                            TiledSweepIO{nullptr, act, y_state, a_state, sgrid, k_begin, k_end, U, G2, G1, Z, nullptr}, n_sgrid,
+                            Shape{B, C, H}, Dtypes{dtype, time_dtype}, Workspace{(void*)workspace, workspace_bytes}, stream);
 }
 
-// ---------------------------------------------------------------------------------------------- K2mh / K3mh (33 .. 64 hidden channels)
-// argument checks in the siblings' order, all before the first HIP call: sizes, dtype, (forward) the empty batch, the
-// envelope of rk4_mlp_tallh.hip, pointers, workspace
 extern "C" int cde_rk4_mlp_tall_supported(int64_t C, int64_t H, int64_t width, int dtype, int act) {
-  return (dtype == CDE_F32 && field_act_known(act) && mlp_tallh_shape_ok(C, H, width)) ? 1 : 0;
-}
-
-static int mlp_tall_envelope(int64_t C, int64_t H, int64_t width, int dtype, int act) {
-  if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
-  return cde_rk4_mlp_tall_supported(C, H, width, dtype, act) ? CDE_OK : CDE_ERR_UNSUPPORTED;
+  return mlp_tiled_supported<4>(C, H, width, dtype, act);
 }
 
 extern "C" int cde_rk4_forward_mlp_tall(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
@@ -828,48 +850,19 @@ extern "C" int cde_rk4_forward_mlp_tall(const void* coeffs, const void* knots, i
                                         const void* z0, const void* grid, int64_t n_grid, const void* t_out, int64_t n_out,
                                         void* z_out, int64_t B, int64_t C, int64_t H, int dtype, int time_dtype,
                                         int64_t* stage_index, void* stage_frac, void* stream) {
-  if (B < 0 || C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_grid < 1 || n_out < 1) return CDE_ERR_SHAPE;
-  if (dtype != CDE_F32 && dtype != CDE_F64) return CDE_ERR_DTYPE;
-  if (B == 0) return CDE_OK;
-  const int rc = mlp_tall_envelope(C, H, width, dtype, act);
-  if (rc != CDE_OK) return rc;
-  if (!coeffs || !knots || !W1 || !bias1 || !W2 || !bias2 || !z0 || !grid || !t_out || !z_out) return CDE_ERR_NULL;
-  if (n_grid > 1 && (!stage_index || !stage_frac)) return CDE_ERR_NULL;
-  const Control x{coeffs, knots, n_intervals, degree};
-  const TwoLayerField f{W1, bias1, width, W2, bias2, act};
-  const ForwardIO io{z0, grid, n_grid, t_out, n_out, z_out, nullptr};
-  const Shape n{B, C, H};
-  const StageBuffers st{stage_index, stage_frac};
-  hipStream_t s = (hipStream_t)stream;
-  return forward_solve(Dtypes{dtype, time_dtype}, x, io, CDE_METHOD_RK4, st, s, [&](auto, auto tt) {
-    return launch_forward_mlp_tallh<typename decltype(tt)::type>(x, f, io, n, st, s);
-  });
+  return mlp_tiled_forward<4>(Control{coeffs, knots, n_intervals, degree}, TwoLayerField{W1, bias1, width, W2, bias2, act},
+                              ForwardIO{z0, grid, n_grid, t_out, n_out, z_out, nullptr}, Shape{B, C, H},
+                              Dtypes{dtype, time_dtype}, StageBuffers{stage_index, stage_frac}, stream);
 }
 
-// workspace: [stage_index: 4*(n_sgrid-1) int64][stage_frac: 4*(n_sgrid-1) f32][layer-1 images and the padded output-layer copies]
-extern "C" size_t cde_rk4_adjoint_mlp_tall_workspace_bytes(int64_t n_sgrid) {
-  return StageWorkspace(n_sgrid, sizeof(float)).total(align256(mlp_tallh_adjoint_image_bytes()));
-}
+extern "C" size_t cde_rk4_adjoint_mlp_tall_workspace_bytes(int64_t n_sgrid) { return mlp_tiled_workspace_bytes<4>(n_sgrid); }
 
 extern "C" int cde_rk4_adjoint_mlp_tall_prepare(const void* knots, int64_t n_intervals, const void* sgrid, int64_t n_sgrid,
                                                 const void* W1, const void* bias1, int64_t width, const void* W2,
                                                 const void* bias2, int64_t C, int64_t H, int dtype, int time_dtype,
                                                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_sgrid < 0) return CDE_ERR_SHAPE;
-  const int rc = mlp_tall_envelope(C, H, width, dtype, CDE_ACT_NONE);
-  if (rc != CDE_OK) return rc;
-  if (!knots || !W1 || !bias1 || !W2 || !bias2 || !workspace || (n_sgrid > 1 && !sgrid)) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_rk4_adjoint_mlp_tall_workspace_bytes(n_sgrid)) return CDE_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const Control x{nullptr, knots, n_intervals, 0};
-  const StageWorkspace layout(n_sgrid, sizeof(float));
-  const int table = dispatch_dtype(time_dtype, [&](auto tt) {
-    return fill_stage_table<float, typename decltype(tt)::type>(x, sgrid, layout.n_steps, 1, CDE_METHOD_RK4,
-                                                                layout.table(workspace), s);
-  });
-  if (table != CDE_OK) return table;
-  return launch_mlp_tallh_adjoint_images(TwoLayerField{W1, bias1, width, W2, bias2, CDE_ACT_NONE}, C, H,
-                                         (float*)layout.tail(workspace), s);
+  return mlp_tiled_prepare<4>(knots, n_intervals, sgrid, n_sgrid, TwoLayerField{W1, bias1, width, W2, bias2, CDE_ACT_NONE}, C, H,
+                              Dtypes{dtype, time_dtype}, Workspace{workspace, workspace_bytes}, stream);
 }
 
 extern "C" int cde_rk4_adjoint_mlp_tall_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
@@ -877,16 +870,7 @@ extern "C" int cde_rk4_adjoint_mlp_tall_sweep(const void* coeffs, const void* kn
                                               int64_t k_begin, int64_t k_end, void* U, void* G2, void* G1, void* Z, void* Z_hi,
                                               int64_t B, int64_t C, int64_t H, int dtype, int time_dtype, const void* workspace,
                                               size_t workspace_bytes, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || n_intervals < 1 || k_begin < 0 || k_end < k_begin || k_end > n_sgrid - 1) return CDE_ERR_SHAPE;
-  const int rc = mlp_tall_envelope(C, H, 1, dtype, act);
-  if (rc != CDE_OK) return rc;
-  if (!coeffs || !knots || !y_state || !a_state || !sgrid || !U || !G2 || !G1 || !Z || !Z_hi || !workspace) return CDE_ERR_NULL;
-  if (workspace_bytes < cde_rk4_adjoint_mlp_tall_workspace_bytes(n_sgrid)) return CDE_ERR_WORKSPACE;
-  const StageWorkspace layout(n_sgrid, sizeof(float));
-  const StageTable st = layout.table(workspace);
-  const Control x{coeffs, knots, n_intervals, degree};
-  const TallSweepIO io{(const float*)layout.tail(workspace), act, y_state, a_state, sgrid, k_begin, k_end, U, G2, G1, Z, Z_hi};
-  return dispatch_dtype(time_dtype, [&](auto tt) {
-    return launch_mlp_tallh_adjoint_sweep<typename decltype(tt)::type>(x, io, Shape{B, C, H}, st, (hipStream_t)stream);
-  });
+  return mlp_tiled_sweep<4>(Control{coeffs, knots, n_intervals, degree},
+                            TiledSweepIO{nullptr, act, y_state, a_state, sgrid, k_begin, k_end, U, G2, G1, Z, Z_hi}, n_sgrid,
+                            Shape{B, C, H}, Dtypes{dtype, time_dtype}, Workspace{(void*)workspace, workspace_bytes}, stream);
 }

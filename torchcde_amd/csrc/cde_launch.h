@@ -125,6 +125,13 @@ template <typename K>
 void allow_lds(K kernel, size_t bytes) {
   (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
+// Waves (16-series tiles) per workgroup of the one-wave-per-tile kernels (rk4_mlp3.hip, rk4_mlp_tiled.hip).  Their LDS images
+// allow one workgroup per CU, and there is one tile form only, so a small batch is spread over the 256 CUs first: one wave
+// per workgroup up to 256 tiles, then two, .. up to `most`.
+static inline unsigned waves_per_workgroup(int64_t tiles, unsigned most) {
+  const int64_t per_cu = (tiles + 255) / 256;
+  return per_cu < 1 ? 1u : per_cu > most ? most : (unsigned)per_cu;
+}
 // the launch loop of every adaptive family: per launch of the window the attempt kernel on its parity, then `after(parity)`
 // (the kernels that digest what the attempt left); a code other than CDE_OK from `after` ends the loop
 template <typename K, typename Args, typename After>

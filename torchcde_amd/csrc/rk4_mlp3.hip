@@ -40,7 +40,7 @@ __global__ __launch_bounds__(512, 2) void rk4_forward_mlp3(
   const int Hr = dims.H, Cr = dims.C, w1r = dims.w1, w2r = dims.w2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = lane & 15, q = lane >> 4;
-  const int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;     // (1 .. 8 waves per workgroup: mlp3_waves)
+  const int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;     // (1 .. 8 waves per workgroup: cde_launch.h, waves_per_workgroup)
   if (tile * 16 >= B) return;
   // (waves w and w + 4 share a SIMD: half a stage of head start for one of them, as in K2)
   if (__builtin_amdgcn_readfirstlane(wave) >= 4) __builtin_amdgcn_s_sleep(FWD_STAGGER_SLEEP);
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256, 1) void rk4_adjoint_mlp3_sweep(
   const int Hr = dims.H, Cr = dims.C;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = lane & 15, q = lane >> 4;
-  const int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;     // (1 .. 4 waves per workgroup: mlp3_waves)
+  const int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;     // (1 .. 4 waves per workgroup: cde_launch.h, waves_per_workgroup)
   if (tile * 16 >= B) return;
   const int64_t series = tile * 16 + n;
   const bool valid = series < B;
@@ -417,13 +417,6 @@ bool mlp3_shape_ok(int64_t C, int64_t H, int64_t width1, int64_t width2) {
   return H >= 1 && H <= MH && C >= 1 && C <= MC && width1 >= 1 && width1 <= MW && width2 >= 1 && width2 <= MW;
 }
 
-// Waves (16-series tiles) per workgroup.  The LDS images allow one workgroup per CU, and there is one tile form only, so a
-// small batch is spread over the 256 CUs first: one wave per workgroup up to 256 tiles, then two, .. up to `most`.
-static unsigned mlp3_waves(int64_t tiles, unsigned most) {
-  const int64_t per_cu = (tiles + 255) / 256;
-  return per_cu < 1 ? 1u : per_cu > most ? most : (unsigned)per_cu;
-}
-
 size_t mlp3_adjoint_image_bytes() { return (size_t)MLP3_ADJ_IMAGE_FLOATS * sizeof(float); }
 
 int launch_mlp3_adjoint_images(const ThreeLayerField& f, int64_t C, int64_t H, float* img, hipStream_t s) {
@@ -439,7 +432,7 @@ int launch_forward_mlp3(const Control& x, const ThreeLayerField& f, const Forwar
   if (!mlp3_shape_ok(n.C, n.H, f.width1, f.width2)) return CDE_ERR_UNSUPPORTED;
   const Mlp3Dims dims{(int)n.H, (int)n.C, (int)f.width1, (int)f.width2};
   const int64_t tiles = (n.B + 15) / 16;
-  const unsigned waves = mlp3_waves(tiles, 8), blocks = (unsigned)((tiles + waves - 1) / waves);
+  const unsigned waves = waves_per_workgroup(tiles, 8), blocks = (unsigned)((tiles + waves - 1) / waves);
   const size_t lds = (size_t)MLP3_FWD_LDS_FLOATS * sizeof(float);
   const bool vec = (f.width1 & 3) == 0 && ((uintptr_t)f.Wm & 15) == 0;
   const int rc = dispatch_degree_field(x.degree, f.act, [&](auto D, auto A) {
@@ -461,7 +454,7 @@ int launch_mlp3_adjoint_sweep(const Control& x, const Sweep3IO& io, const Shape&
   if (io.k_end <= io.k_begin) return CDE_OK;
   const Dims dims{(int)n.H, (int)n.C};
   const int64_t tiles = (n.B + 15) / 16;
-  const unsigned waves = mlp3_waves(tiles, 4), blocks = (unsigned)((tiles + waves - 1) / waves);
+  const unsigned waves = waves_per_workgroup(tiles, 4), blocks = (unsigned)((tiles + waves - 1) / waves);
   const size_t lds = (size_t)MLP3_ADJ_LDS_FLOATS * sizeof(float);
   const int rc = dispatch_degree_field(x.degree, io.act, [&](auto D, auto A) {
     auto kernel = rk4_adjoint_mlp3_sweep<TT, D(), A()>;

@@ -105,7 +105,7 @@ def select_path(q):
                          "the three-layer field is fused under method='rk4' only: forward, and adjoint=True for z0 and all six "
                          "parameters (step_size options, no time / control gradients)")
     if q.kind == "mlp2w":
-        # the two-layer field on a control of 17 .. 64 channels: K2mc / K3mc (csrc/rk4_mlp_widec.hip) under rk4, nothing else
+        # the two-layer field on a control of 17 .. 64 channels: K2mc / K3mc (csrc/rk4_mlp_tiled.hip, NV = 2) under rk4, nothing else
         if q.method == "rk4" and not q.variant_generic and q.options_ok:
             if not q.wants_grad:
                 return Choice("mlp_rk4_forward", "")
@@ -116,7 +116,7 @@ def select_path(q):
                          "on a wide control (17 to 64 channels) the two-layer field is fused under method='rk4' only: forward, "
                          "and adjoint=True for z0 and all four parameters (step_size options, no time / control gradients)")
     if q.kind == "mlp2h":
-        # the two-layer field on a hidden state of 33 .. 64 channels: K2mh / K3mh (csrc/rk4_mlp_tallh.hip) under rk4, nothing else
+        # the two-layer field on a hidden state of 33 .. 64 channels: K2mh / K3mh (csrc/rk4_mlp_tiled.hip, NV = 4) under rk4, nothing else
         if q.method == "rk4" and not q.variant_generic and q.options_ok:
             if not q.wants_grad:
                 return Choice("mlp_rk4_forward", "")
