@@ -489,6 +489,47 @@ int cde_rk4_adjoint_mlp_tall_sweep(const void* coeffs, const void* knots, int64_
                                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K2mb / K3mb  K2mc and K3mc for the two-layer field with an inner layer of 129 .. 256 units: f32, 128 < width <= 256,
+ * 1 <= H <= 32, 1 <= C <= 64 with H CP <= 1024 (CP = C rounded up to 4: 32 x 32 and 16 x 64 are inside, 32 x 33 is not),
+ * one wave per 16 series at every batch size, rk4 only; anything else CDE_ERR_UNSUPPORTED (every entry point above keeps
+ * turning width > 128 away).  `act` = CDE_FIELD_ACT(final, hidden) as for K2m.  The output layer (up to 1024 x 256) is read
+ * from L2 as by K2mc / K3mc: by the forward kernel from W2 itself -- 16-byte rows when width is a multiple of 4 and W2 is
+ * 16-byte aligned, element by element otherwise -- by the sweep from zero-padded copies that _prepare leaves in `workspace`.
+ *   cde_rk4_mlp_broad_supported   1 when (C, H, width, dtype, act) is inside this envelope, else 0
+ *   cde_rk4_forward_mlp_broad     arguments of cde_rk4_forward_mlp
+ *   cde_rk4_adjoint_mlp_broad_*   the protocol of cde_rk4_adjoint_mlp_wide_*.  Z and the ceil(H CP / 256) <= 4 BLOCKS of G2
+ *     exactly as there (the CALLER zeroes G2 once).  The inner layer's rows come in two halves, so that
+ *     cde_mlp_grad_reduce serves each as it is:
+ *       U_lo, U_hi     (rows, 132) f32 each: units 0 .. 127 | 1 | 0 0 0 and units 128 .. 255 | 1 | 0 0 0.  The caller writes
+ *                      both "1" columns.  The SWEEP writes all 128 unit columns of both halves; a unit >= width carries hid(0)
+ *                      (0, or ln 2 under softplus), which reaches only the columns >= width - 128 of the hi image of dW2: the
+ *                      caller drops them.
+ *       G1_lo, G1_hi   (rows, 128) f32 each, already weighted.  The columns of G1_hi from width - 128 on are exact zeros, and
+ *                      the SWEEP guarantees it: the prepared copy of W2 is zero from column `width` on, so dL/du of those
+ *                      units is 0 and so is 0 * hid'.  The sweep is not told the width; it runs on what _prepare left.
+ *     the caller reduces every G2 block against each U half (layer 2) into its own [256][132] image -- dW2[:, 0:128] | db2
+ *     from the lo images, dW2[:, 128:width] from the hi images -- and each G1 half against Z (layer 1) into its own
+ *     [128][36] image: rows 0 .. 127 and 128 .. width - 1 of dW1 | db1.
+ * No control-coefficient gradients (there is no `grad_coeffs`).
+ * ------------------------------------------------------------------------------------------- */
+int cde_rk4_mlp_broad_supported(int64_t C, int64_t H, int64_t width, int dtype, int act);
+int cde_rk4_forward_mlp_broad(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
+                              const void* bias1, int64_t width, const void* W2, const void* bias2, int act, const void* z0,
+                              const void* grid, int64_t n_grid, const void* t_out, int64_t n_out, void* z_out, int64_t B,
+                              int64_t C, int64_t H, int dtype, int time_dtype, int64_t* stage_index, void* stage_frac,
+                              void* stream);
+size_t cde_rk4_adjoint_mlp_broad_workspace_bytes(int64_t n_sgrid);
+int cde_rk4_adjoint_mlp_broad_prepare(const void* knots, int64_t n_intervals, const void* sgrid, int64_t n_sgrid,
+                                      const void* W1, const void* bias1, int64_t width, const void* W2, const void* bias2,
+                                      int64_t C, int64_t H, int dtype, int time_dtype, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+int cde_rk4_adjoint_mlp_broad_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
+                                    void* y_state, void* a_state, const void* sgrid, int64_t n_sgrid, int64_t k_begin,
+                                    int64_t k_end, void* U_lo, void* U_hi, void* G2, void* G1_lo, void* G1_hi, void* Z,
+                                    int64_t B, int64_t C, int64_t H, int dtype, int time_dtype, const void* workspace,
+                                    size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K3  Fused continuous-adjoint reverse sweep for K2.
  * Replaces torchdiffeq.odeint_adjoint's backward (behind solver.py:226): for every output
  * interval, RK4 (3/8) integration in reversed time of the augmented state (z, a_z, a_W, a_b),

@@ -756,9 +756,10 @@ class _MlpTiledPlan(_MlpPlan):
     """Fused RK4 solves for the two-layer field with its output layer worked tile by tile (csrc/rk4_mlp_tiled.hip): forward
     (cde_rk4_forward_mlp_<form>) and continuous-adjoint backward (the sweep, cde_rk4_adjoint_mlp_<form>_*, + one factor
     reduction per 256-column block of the output layer's gradient and one per 32-unit half of the state).  One wave per 16
-    series at every batch size.  A subclass names the form: the entry points' infix, the number of Z halves, and what the
-    messages call the shape."""
+    series at every batch size.  A subclass names the form: the entry points' infix, the number of Z halves, the number of
+    128-unit halves of the inner layer (U and G1 come in as many), and what the messages call the shape."""
     form = z_halves = shape_noun = sweep_noun = None
+    inner_halves = 1
 
     def _entry(self, name):
         """(the entry point `name` with the form's infix, its name for messages)"""
@@ -785,8 +786,8 @@ class _MlpTiledPlan(_MlpPlan):
 
     def run_adjoint(self, z_saved, grad_out, w1, b1, w2, b2, want_control=False):
         """As _MlpPlan.run_adjoint, with the output layer's dL/dY2 rows in blocks of 256 columns and the state rows in halves
-        of 32 units: per chunk of steps the sweep streams (U, G2 blocks, G1, Z halves), each G2 block is reduced against U
-        into its own image, G1 against every Z half."""
+        of 32 units: per chunk of steps the sweep streams (U halves, G2 blocks, G1 halves, Z halves), each G2 block is reduced
+        against every U half into its own image, every G1 half against every Z half."""
         if want_control:
             raise NotImplementedError("torchcde_amd: the %s sweep has no control gradients" % self.sweep_noun)
         lib = _lib.load()
@@ -805,8 +806,9 @@ class _MlpTiledPlan(_MlpPlan):
         y = z_saved[:, -1].clone(memory_format=torch.contiguous_format)
         a = grad_out[:, -1].to(torch.float32).clone(memory_format=torch.contiguous_format)
         blocks = (H * ((C + 3) // 4 * 4) + 255) // 256
-        acc2 = torch.zeros(blocks, 256, 132, dtype=torch.float32, device=dev)
-        acc1 = [torch.zeros(128, 36, dtype=torch.float32, device=dev) for _ in range(self.z_halves)]
+        inner = self.inner_halves
+        acc2 = [torch.zeros(blocks, 256, 132, dtype=torch.float32, device=dev) for _ in range(inner)]
+        acc1 = [[torch.zeros(128, 36, dtype=torch.float32, device=dev) for _ in range(self.z_halves)] for _ in range(inner)]
         longest = max((g.seg_off_host[p + 1] - 1 - g.seg_off_host[p] for p in range(self.n_out - 1)), default=0)
         self.steps_per_launch = 0                   # the chunking that ran (tests, tools)
         if g.n_sgrid > 1 and longest > 0:
@@ -814,18 +816,20 @@ class _MlpTiledPlan(_MlpPlan):
             _lib.check(prepare(
                 _lib.ptr(self.knots), self.n_intervals, _lib.ptr(g.sgrid), g.n_sgrid, *_weight_args(weights), C, H, f32, tdt,
                 _lib.ptr(workspace), nbytes, stream), name)
-            row_bytes = (132 + 256 * blocks + 128 + self.z_halves * 36) * 4
+            row_bytes = (inner * 132 + 256 * blocks + inner * 128 + self.z_halves * 36) * 4
             chunk = max(1, min(longest, self.scratch_budget // (row_bytes * 4 * B)))
             self.steps_per_launch = chunk
             rows = chunk * 4 * B
-            U = torch.zeros(rows, 132, dtype=torch.float32, device=dev)
-            U[:, 128] = 1
+            U = []
+            for _ in range(inner):
+                U.append(torch.zeros(rows, 132, dtype=torch.float32, device=dev))
+                U[-1][:, 128] = 1
             Z = []
             for _ in range(self.z_halves):          # (of the last half the sweep writes the units < H only)
                 Z.append(torch.zeros(rows, 36, dtype=torch.float32, device=dev))
                 Z[-1][:, 32] = 1
             G2 = torch.zeros(blocks * rows, 256, dtype=torch.float32, device=dev)    # the sweep writes the rows h < H only
-            G1 = torch.empty(rows, 128, dtype=torch.float32, device=dev)
+            G1 = [torch.empty(rows, 128, dtype=torch.float32, device=dev) for _ in range(inner)]
             reduce_ws = torch.empty(lib.cde_mlp_grad_reduce_workspace_bytes(), dtype=torch.uint8, device=dev)
             sweep, name = self._entry("cde_rk4_adjoint_mlp_%s_sweep")
             for p in range(self.n_out - 1):
@@ -834,21 +838,30 @@ class _MlpTiledPlan(_MlpPlan):
                     ke = min(k_end, k + chunk)
                     _lib.check(sweep(
                         _lib.ptr(self.coeffs), _lib.ptr(self.knots), self.n_intervals, self.degree, self.act, _lib.ptr(y),
-                        _lib.ptr(a), _lib.ptr(g.sgrid), g.n_sgrid, k, ke, _lib.ptr(U), _lib.ptr(G2), _lib.ptr(G1),
-                        *(_lib.ptr(half) for half in Z), B, C, H, f32, tdt, _lib.ptr(workspace), nbytes, stream), name)
+                        _lib.ptr(a), _lib.ptr(g.sgrid), g.n_sgrid, k, ke, *(_lib.ptr(half) for half in U), _lib.ptr(G2),
+                        *(_lib.ptr(half) for half in G1), *(_lib.ptr(half) for half in Z), B, C, H, f32, tdt,
+                        _lib.ptr(workspace), nbytes, stream), name)
                     n = 4 * (ke - k) * B
-                    for b in range(blocks):         # block b starts n rows behind block b - 1
-                        _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G2[b * n:]), _lib.ptr(U), n, 2, _lib.ptr(acc2[b]),
-                                                           _lib.ptr(reduce_ws), reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
-                    for half, acc in zip(Z, acc1):
-                        _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G1), _lib.ptr(half), n, 1, _lib.ptr(acc), _lib.ptr(reduce_ws),
-                                                           reduce_ws.numel(), stream), "cde_mlp_grad_reduce")
+                    for s in range(inner):
+                        for b in range(blocks):     # block b starts n rows behind block b - 1
+                            _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G2[b * n:]), _lib.ptr(U[s]), n, 2, _lib.ptr(acc2[s][b]),
+                                                               _lib.ptr(reduce_ws), reduce_ws.numel(), stream),
+                                       "cde_mlp_grad_reduce")
+                        for half, acc in zip(Z, acc1[s]):
+                            _lib.check(lib.cde_mlp_grad_reduce(_lib.ptr(G1[s]), _lib.ptr(half), n, 1, _lib.ptr(acc),
+                                                               _lib.ptr(reduce_ws), reduce_ws.numel(), stream),
+                                       "cde_mlp_grad_reduce")
                     k = ke
                 i_out = self.n_out - 1 - p
                 y.copy_(z_saved[:, i_out - 1])                 # torchdiffeq: re-seed z from the stored forward solution
                 a.add_(grad_out[:, i_out - 1])                 # and add the incoming gradient at that output time
-        gradients = _mlp_wide_gradients if self.z_halves == 1 else _mlp_tall_gradients
-        return (a.reshape(*self.batch, H),) + gradients(*acc1, acc2, H, C, width) + (None,)
+        if inner == 2:
+            gradients = _mlp_broad_gradients(acc1[0][0], acc1[1][0], acc2[0], acc2[1], H, C, width)
+        elif self.z_halves == 1:
+            gradients = _mlp_wide_gradients(*acc1[0], acc2[0], H, C, width)
+        else:
+            gradients = _mlp_tall_gradients(*acc1[0], acc2[0], H, C, width)
+        return (a.reshape(*self.batch, H),) + gradients + (None,)
 
     def run_backprop(self, *args, **kwargs):
         raise NotImplementedError("torchcde_amd: %s have no reverse-mode (adjoint=False) kernels" % self.shape_noun)
@@ -880,6 +893,31 @@ def _mlp_tall_gradients(acc1, acc1_hi, acc2, H, C, width):
 class _MlpTallPlan(_MlpTiledPlan):
     """The two-layer field on a hidden state of 33 .. 64 channels (NV = 4: K2mh forward, K3mh sweep; Z and Z_hi)."""
     form, z_halves, shape_noun, sweep_noun = "tall", 2, "tall hidden states", "tall-state"
+
+
+def _mlp_broad_fusable(field, H, C, z0, packed):
+    """The envelope of the broad-inner-layer kernels (csrc/rk4_mlp_broad.hip; cde_mi355x.h: cde_rk4_forward_mlp_broad): float32,
+    128 < width <= 256, H <= 32, C <= 64 with H * CP <= 1024 (CP = C rounded up to 4) -- the inner widths beyond _mlp_fusable,
+    _mlp_wide_fusable and _mlp_tall_fusable, which all stop at 128."""
+    w1, w2 = field.hidden.weight, field.output.weight
+    return (z0.dtype == packed.dtype == w1.dtype == w2.dtype == torch.float32 and 128 < w1.size(0) <= 256
+            and 1 <= H <= 32 and 1 <= C <= 64 and H * ((C + 3) // 4 * 4) <= 1024
+            and tuple(w1.shape) == (w1.size(0), H) and tuple(w2.shape) == (H * C, w1.size(0)))
+
+
+def _mlp_broad_gradients(acc1_lo, acc1_hi, acc2_lo, acc2_hi, H, C, width):
+    """(dL/dW1, dL/db1, dL/dW2, dL/db2) from the reduced images of the broad-inner-layer sweep.  acc1_lo / acc1_hi: (128, 36)
+    -- rows 0 .. 127 and 128 .. width - 1 of dL/dW1 | dL/db1 (column 32).  acc2_lo / acc2_hi as _mlp_wide_gradients: columns
+    0 .. 127 and 128 .. width - 1 of dL/dW2; dL/db2 in column 128 of the first."""
+    lo = _mlp_wide_gradients(acc1_lo, acc2_lo, H, C, 128)
+    hi = _mlp_wide_gradients(acc1_hi, acc2_hi, H, C, width - 128)
+    return (torch.cat((lo[0], hi[0]), dim=0), torch.cat((lo[1], hi[1]), dim=0), torch.cat((lo[2], hi[2]), dim=1).contiguous(),
+            lo[3])
+
+
+class _MlpBroadPlan(_MlpTiledPlan):
+    """The two-layer field with an inner layer of 129 .. 256 units (K2mb forward, K3mb sweep; U and G1 in two halves)."""
+    form, z_halves, inner_halves, shape_noun, sweep_noun = "broad", 1, 2, "broad inner layers", "broad-inner-layer"
 
 
 def _reaches(tensor, leaf):
@@ -1067,6 +1105,10 @@ class _FusedMlpWideRK4(torch.autograd.Function):
 
 class _FusedMlpTallRK4(_FusedMlpWideRK4):
     """The two-layer field on a hidden state of 33 .. 64 channels: K2mh forward, K3mh backward."""
+
+
+class _FusedMlpBroadRK4(_FusedMlpWideRK4):
+    """The two-layer field with an inner layer of 129 .. 256 units: K2mb forward, K3mb backward."""
 
 
 class _FusedRK4Backprop(torch.autograd.Function):
@@ -1883,9 +1925,11 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
     # (`variant="generic"` keeps autograd: the independent cross-check the tests compare against)
     recognised = field if variant == _lib.VARIANT_AUTO else None
     recognised_kind = None if field is None else field.kind
-    mlp = mlp_wide = mlp_tall = None
+    mlp = mlp_wide = mlp_tall = mlp_broad = None
     if field is not None and field.kind == "mlp2":
-        if _mlp_wide_fusable(field, H, C, z0, packed):      # 17 .. 64 channels: its own kernels, rk4 only (kind "mlp2w")
+        if _mlp_broad_fusable(field, H, C, z0, packed):     # 129 .. 256 inner units: its own kernels, rk4 only (kind "mlp2b")
+            mlp_broad, field = field, None
+        elif _mlp_wide_fusable(field, H, C, z0, packed):      # 17 .. 64 channels: its own kernels, rk4 only (kind "mlp2w")
             mlp_wide, field = field, None
         elif _mlp_tall_fusable(field, H, C, z0, packed):    # 33 .. 64 hidden channels: its own kernels, rk4 only (kind "mlp2h")
             mlp_tall, field = field, None
@@ -1951,7 +1995,7 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
 
     # ---- how the caller's adjoint_params relate to the field's own parameters and the control's tensors
     known = (field if field is not None else mlp if mlp is not None else mlp3 if mlp3 is not None else
-             mlp_wide if mlp_wide is not None else mlp_tall)
+             mlp_wide if mlp_wide is not None else mlp_tall if mlp_tall is not None else mlp_broad)
     own = () if known is None else (
         (field.weight, field.bias) if field is not None else
         tuple(p for lin in known.linears for p in (lin.weight, lin.bias)))     # two / three layers: all four / all six
@@ -1995,7 +2039,7 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
     from .distributed import step_control
     request = dispatch.Request(
         prod=False, kind=(None if known is None else "mlp2w" if mlp_wide is not None else "mlp2h" if mlp_tall is not None
-                          else known.kind),
+                          else "mlp2b" if mlp_broad is not None else known.kind),
         tiles_ok=known is not None, mfma_shape=mfma_shape,
         method=method, adjoint=bool(adjoint), wants_grad=bool(wants_grad), wants_t=bool(wants_t),
         wants_control=bool(control_wants), params=params_kind,
@@ -2075,6 +2119,17 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
         plan = _MlpTallPlan(X, mlp_tall, batch, H, C, t, step, adj_step)
         return _FusedMlpTallRK4.apply(z0, mlp_tall.hidden.weight, mlp_tall.hidden.bias, mlp_tall.output.weight,
                                       mlp_tall.output.bias, plan, None, None, None)
+
+    # ---- two-layer fields with 129 .. 256 inner units (rk4 only: forward, and the continuous adjoint for z0 and the four parameters)
+    if mlp_broad is not None:
+        step = _parse_fixed_options(fused_options, "solver")
+        if choice.path == "mlp_rk4_forward":
+            with torch.no_grad():
+                return _MlpBroadPlan(X, mlp_broad, batch, H, C, t, step).run(z0)
+        adj_step = step if fused_adj_opts is None else _parse_fixed_options(fused_adj_opts, "adjoint")
+        plan = _MlpBroadPlan(X, mlp_broad, batch, H, C, t, step, adj_step)
+        return _FusedMlpBroadRK4.apply(z0, mlp_broad.hidden.weight, mlp_broad.hidden.bias, mlp_broad.output.weight,
+                                       mlp_broad.output.bias, plan, None, None, None)
 
     # ---- two-layer fields
     if choice.path == "mlp_rk4_adjoint":

@@ -4,6 +4,7 @@
 #include "cde_launch.h"
 #include "cde_mlp3.h"
 #include "cde_mlp_tiled.h"
+#include "cde_mlp_broad.h"
 
 namespace cde {
 
@@ -873,4 +874,93 @@ extern "C" int cde_rk4_adjoint_mlp_tall_sweep(const void* coeffs, const void* kn
   return mlp_tiled_sweep<4>(Control{coeffs, knots, n_intervals, degree},
                             TiledSweepIO{nullptr, act, y_state, a_state, sgrid, k_begin, k_end, U, G2, G1, Z, Z_hi}, n_sgrid,
                             Shape{B, C, H}, Dtypes{dtype, time_dtype}, Workspace{(void*)workspace, workspace_bytes}, stream);
+}
+
+// ------------------------------------------------------ K2mb / K3mb (inner layer of 129 .. 256 units; rk4_mlp_broad.hip)
+// Argument checks in the order of *_mlp_wide_*, all before the first HIP call: sizes, dtype, (forward) the empty batch, the
+// envelope, pointers, workspace.  The sweep is not told the width: it checks the rest of the envelope at the widest.
+static int mlp_broad_supported(int64_t C, int64_t H, int64_t width, int dtype, int act) {
+  return (dtype == CDE_F32 && field_act_known(act) && mlp_broad_shape_ok(C, H, width)) ? 1 : 0;
+}
+
+static int mlp_broad_envelope(int64_t C, int64_t H, int64_t width, int dtype, int act) {
+  if (dtype != CDE_F32) return dtype == CDE_F64 ? CDE_ERR_UNSUPPORTED : CDE_ERR_DTYPE;
+  return mlp_broad_supported(C, H, width, dtype, act) ? CDE_OK : CDE_ERR_UNSUPPORTED;
+}
+
+// workspace: [stage_index: 4*(n_sgrid-1) int64][stage_frac: 4*(n_sgrid-1) f32][layer-1 images and the padded output-layer copies]
+static size_t mlp_broad_workspace_bytes(int64_t n_sgrid) {
+  return StageWorkspace(n_sgrid, sizeof(float)).total(align256(mlp_broad_adjoint_image_bytes()));
+}
+
+extern "C" int cde_rk4_mlp_broad_supported(int64_t C, int64_t H, int64_t width, int dtype, int act) {
+  return mlp_broad_supported(C, H, width, dtype, act);
+}
+
+extern "C" int cde_rk4_forward_mlp_broad(const void* coeffs, const void* knots, int64_t n_intervals, int degree, const void* W1,
+                                         const void* bias1, int64_t width, const void* W2, const void* bias2, int act,
+                                         const void* z0, const void* grid, int64_t n_grid, const void* t_out, int64_t n_out,
+                                         void* z_out, int64_t B, int64_t C, int64_t H, int dtype, int time_dtype,
+                                         int64_t* stage_index, void* stage_frac, void* stream) {
+  const Control x{coeffs, knots, n_intervals, degree};
+  const TwoLayerField f{W1, bias1, width, W2, bias2, act};
+  const ForwardIO io{z0, grid, n_grid, t_out, n_out, z_out, nullptr};
+  const Shape n{B, C, H};
+  const Dtypes dt{dtype, time_dtype};
+  const StageBuffers st{stage_index, stage_frac};
+  if (B < 0 || C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_grid < 1 || n_out < 1) return CDE_ERR_SHAPE;
+  if (dtype != CDE_F32 && dtype != CDE_F64) return CDE_ERR_DTYPE;
+  if (B == 0) return CDE_OK;
+  const int rc = mlp_broad_envelope(C, H, width, dtype, act);
+  if (rc != CDE_OK) return rc;
+  if (!coeffs || !knots || !W1 || !bias1 || !W2 || !bias2 || !z0 || !grid || !t_out || !z_out) return CDE_ERR_NULL;
+  if (n_grid > 1 && (!stage_index || !stage_frac)) return CDE_ERR_NULL;
+  hipStream_t s = (hipStream_t)stream;
+  return forward_solve(dt, x, io, CDE_METHOD_RK4, st, s, [&](auto, auto tt) {
+    return launch_forward_mlp_broad<typename decltype(tt)::type>(x, f, io, n, st, s);
+  });
+}
+
+extern "C" size_t cde_rk4_adjoint_mlp_broad_workspace_bytes(int64_t n_sgrid) { return mlp_broad_workspace_bytes(n_sgrid); }
+
+extern "C" int cde_rk4_adjoint_mlp_broad_prepare(const void* knots, int64_t n_intervals, const void* sgrid, int64_t n_sgrid,
+                                                 const void* W1, const void* bias1, int64_t width, const void* W2,
+                                                 const void* bias2, int64_t C, int64_t H, int dtype, int time_dtype,
+                                                 void* workspace, size_t workspace_bytes, void* stream) {
+  if (C < 1 || H < 1 || width < 1 || n_intervals < 1 || n_sgrid < 0) return CDE_ERR_SHAPE;
+  const int rc = mlp_broad_envelope(C, H, width, dtype, CDE_ACT_NONE);
+  if (rc != CDE_OK) return rc;
+  if (!knots || !W1 || !bias1 || !W2 || !bias2 || !workspace || (n_sgrid > 1 && !sgrid)) return CDE_ERR_NULL;
+  if (workspace_bytes < mlp_broad_workspace_bytes(n_sgrid)) return CDE_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const Control x{nullptr, knots, n_intervals, 0};
+  const StageWorkspace layout(n_sgrid, sizeof(float));
+  const int table = dispatch_dtype(time_dtype, [&](auto tt) {
+    return fill_stage_table<float, typename decltype(tt)::type>(x, sgrid, layout.n_steps, 1, CDE_METHOD_RK4,
+                                                                layout.table(workspace), s);
+  });
+  if (table != CDE_OK) return table;
+  return launch_mlp_broad_adjoint_images(TwoLayerField{W1, bias1, width, W2, bias2, CDE_ACT_NONE}, C, H,
+                                         (float*)layout.tail(workspace), s);
+}
+
+extern "C" int cde_rk4_adjoint_mlp_broad_sweep(const void* coeffs, const void* knots, int64_t n_intervals, int degree, int act,
+                                               void* y_state, void* a_state, const void* sgrid, int64_t n_sgrid,
+                                               int64_t k_begin, int64_t k_end, void* U_lo, void* U_hi, void* G2, void* G1_lo,
+                                               void* G1_hi, void* Z, int64_t B, int64_t C, int64_t H, int dtype, int time_dtype,
+                                               const void* workspace, size_t workspace_bytes, void* stream) {
+  if (B < 1 || C < 1 || H < 1 || n_intervals < 1 || k_begin < 0 || k_end < k_begin || k_end > n_sgrid - 1) return CDE_ERR_SHAPE;
+  const int rc = mlp_broad_envelope(C, H, BR_WIDTH, dtype, act);
+  if (rc != CDE_OK) return rc;
+  if (!coeffs || !knots || !y_state || !a_state || !sgrid || !U_lo || !U_hi || !G2 || !G1_lo || !G1_hi || !Z || !workspace)
+    return CDE_ERR_NULL;
+  if (workspace_bytes < mlp_broad_workspace_bytes(n_sgrid)) return CDE_ERR_WORKSPACE;
+  const StageWorkspace layout(n_sgrid, sizeof(float));
+  const StageTable st = layout.table((void*)workspace);
+  const Control x{coeffs, knots, n_intervals, degree};
+  const BroadSweepIO io{(const float*)layout.tail((void*)workspace), act, y_state, a_state, sgrid, k_begin, k_end,
+                        U_lo, U_hi, G2, G1_lo, G1_hi, Z};
+  return dispatch_dtype(time_dtype, [&](auto tt) {
+    return launch_mlp_broad_adjoint_sweep<typename decltype(tt)::type>(x, io, Shape{B, C, H}, st, (hipStream_t)stream);
+  });
 }

@@ -19,6 +19,7 @@ Request = collections.namedtuple("Request", [
                          # "mlp3": act(Linear(hid(Linear(hid(Linear(z)))))) -- fused under rk4 only (K2m3 / K3m3)
                          # "mlp2w": "mlp2" on a control of 17 .. 64 channels -- fused under rk4 only (K2mc / K3mc)
                          # "mlp2h": "mlp2" on a hidden state of 33 .. 64 channels -- fused under rk4 only (K2mh / K3mh)
+                         # "mlp2b": "mlp2" with an inner layer of 129 .. 256 units -- fused under rk4 only (K2mb / K3mb)
     "tiles_ok",          # the field's shape / dtype fit some fused kernel (cde_rk4_supported; _mlp_fusable)
     "mfma_shape",        # affine field on the 32 x 8 MFMA tiles (float32, H <= 32, C <= 8, variant != "generic")
     "method",            # "rk4" | "dopri5" | any other torchdiffeq method name
@@ -125,6 +126,18 @@ def select_path(q):
                 return Choice("mlp_rk4_adjoint", "")
         return _stepwise(("variant='generic' was requested (the step-wise reference path); " if q.variant_generic else "") +
                          "on a tall hidden state (33 to 64 channels) the two-layer field is fused under method='rk4' only: "
+                         "forward, and adjoint=True for z0 and all four parameters (step_size options, no time / control "
+                         "gradients)")
+    if q.kind == "mlp2b":
+        # the two-layer field with an inner layer of 129 .. 256 units: K2mb / K3mb (csrc/rk4_mlp_broad.hip) under rk4, nothing else
+        if q.method == "rk4" and not q.variant_generic and q.options_ok:
+            if not q.wants_grad:
+                return Choice("mlp_rk4_forward", "")
+            if (q.adjoint and q.adjoint_method_ok and q.adjoint_options_ok and q.params != "foreign" and not q.wants_t
+                    and not q.wants_control):
+                return Choice("mlp_rk4_adjoint", "")
+        return _stepwise(("variant='generic' was requested (the step-wise reference path); " if q.variant_generic else "") +
+                         "with a broad inner layer (129 to 256 units) the two-layer field is fused under method='rk4' only: "
                          "forward, and adjoint=True for z0 and all four parameters (step_size options, no time / control "
                          "gradients)")
     if q.method in ("midpoint", "euler"):

@@ -6,10 +6,11 @@ The fused kernels implement three families:
 i.e. the README field (reference README.md:42-49) and ``example/irregular_data.py:36-46``, and
         f(t, z) = act( Linear(W, H*C)( hidden( Linear(H, W)(z) ) ) ) viewed as (..., H, C),   hidden in {relu, softplus}
 i.e. ``example/time_series_classification.py:20-51`` and its smooth variant with ``torch.nn.functional.softplus`` (torch's
-defaults only: beta 1, threshold 20; any other beta / threshold is refused) in place of the relu -- fused in four shape
-families (cdeint.py: _mlp_fusable, _mlp_wide_fusable, _mlp_tall_fusable): H <= 32 with C <= 8, H <= 16 with C <= 16 and 32 x 16
-(kind "mlp2": rk4 and dopri5), H <= 32 with 17 <= C <= 64 (recorded as "mlp2w": rk4), and 33 <= H <= 64 with C <= 64 and
-H * (C rounded up to 4) <= 2048 (recorded as "mlp2h": rk4), all float32 with W <= 128 -- and
+defaults only: beta 1, threshold 20; any other beta / threshold is refused) in place of the relu -- fused in five shape
+families (cdeint.py: _mlp_fusable, _mlp_wide_fusable, _mlp_tall_fusable, _mlp_broad_fusable): H <= 32 with C <= 8, H <= 16 with
+C <= 16 and 32 x 16 (kind "mlp2": rk4 and dopri5), H <= 32 with 17 <= C <= 64 (recorded as "mlp2w": rk4), and 33 <= H <= 64 with
+C <= 64 and H * (C rounded up to 4) <= 2048 (recorded as "mlp2h": rk4), all float32 with W <= 128; and 128 < W <= 256 with
+H <= 32, C <= 64 and H * (C rounded up to 4) <= 1024 (recorded as "mlp2b": rk4) -- and
         f(t, z) = act( Linear(W2, H*C)( hidden( Linear(W1, W2)( hidden( Linear(H, W1)(z) ) ) ) ) ) viewed as (..., H, C)
 with the SAME hidden activation after both hidden layers (kind "mlp3": fused under rk4 -- forward and adjoint=True -- and solved
 step by step in closed form everywhere else).  A module is recognised by
