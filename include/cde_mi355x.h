@@ -111,7 +111,8 @@ enum {
   CDE_OPT_K4AM_NO_FSAL = 16,    /* 0 default; 1 evaluate every first stage (bit-identical results), 2 after accepted
                                    steps only, 3 after rejected steps only */
   CDE_OPT_WIDE_SCRATCH_BYTES = 17, /* 0 default (4 GB); otherwise the chunk budget of the wide-shape sweep in bytes */
-  CDE_OPT_COUNT = 18
+  CDE_OPT_K2B_GROUPS = 18,      /* bf16 rk4 forward: 0 default (= 2: K2bd, two 16-series groups per wave, rk4_bf16x3_duo.hip), 1: K2b */
+  CDE_OPT_COUNT = 19
 };
 /* Set / read one entry of the tuning table.  cde_set_option returns CDE_ERR_SHAPE for an unknown key; cde_get_option
  * returns INT64_MIN for one.  cde_reset_options() restores every default. */

@@ -5,7 +5,8 @@ counted -- for the fixed-grid solvers that is one RK step.
 A loop is the span from a label to the last branch back to it, so the count is static: both sides of a branch inside the
 loop are counted once each.  `--mfma N` takes the loop with exactly N MFMAs instead of the one with the most (the helper
 wave's stage loop of rk4_adjoint_pair.hip has 96).  Beside the instruction classes the table counts the MFMAs whose SrcA is
-read from AGPRs (`a[...]` as second operand), the LDS reads and waits of the loop, and `lds_cover_min` / `lds_wait_cover_min`: how far
+read from AGPRs (`a[...]` as second operand, whatever the MFMA's shape), the longest run of MFMAs with no other vector
+instruction between them (`mfma_run_max`), the LDS reads and waits of the loop, and `lds_cover_min` / `lds_wait_cover_min`: how far
 ahead of the waits for them the LDS operands are requested (see lds_cover; `-` = the loop has no such wait)."""
 import os
 import re
@@ -92,11 +93,25 @@ def lds_cover(body, gating_only=True, mfma_only=False):
     return cover
 
 
+def mfma_run_max(op):
+    """the longest run of MFMAs with no other vector instruction between them (waits, s_nop and LDS reads do not end a run)"""
+    run = best = 0
+    for o in op:
+        if o.startswith("v_mfma"):
+            run += 1
+            best = max(best, run)
+        elif o.startswith("v_"):
+            run = 0
+    return best
+
+
 def classes(body):
     op = [re.sub(r"_(e32|e64|dpp|sdwa)$", "", ln.split()[0]) for ln in body]
     valu = [o for o in op if o.startswith("v_") and not o.startswith("v_mfma")]
     return {"instructions": len(op), "mfma": sum(o.startswith("v_mfma") for o in op),
-            "mfma_32x32x16_bf16": sum(o == "v_mfma_f32_32x32x16_bf16" for o in op), "valu": len(valu),
+            "mfma_32x32x16_bf16": sum(o == "v_mfma_f32_32x32x16_bf16" for o in op),
+            "mfma_16x16x32_bf16": sum(o == "v_mfma_f32_16x16x32_bf16" for o in op), "mfma_run_max": mfma_run_max(op),
+            "valu": len(valu),
             "v_accvgpr_read_b32": op.count("v_accvgpr_read_b32"), "v_accvgpr_write_b32": op.count("v_accvgpr_write_b32"),
             "v_mov_b32": op.count("v_mov_b32"), "copies": sum(op.count(c) for c in COPIES),
             "v_pk_fma_f32": op.count("v_pk_fma_f32"), "v_pk_mul_f32": op.count("v_pk_mul_f32"),
@@ -124,7 +139,7 @@ if __name__ == "__main__":
     if rest[:1] == ["--mfma"]:
         mfma, rest = int(rest[1]), rest[2:]
     table = loop_table(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "", rest or None, mfma)
-    cols = ["instructions", "mfma", "mfma_srca_agpr", "valu", "copies", "v_accvgpr_read_b32", "v_accvgpr_write_b32", "v_mov_b32",
+    cols = ["instructions", "mfma", "mfma_16x16x32_bf16", "mfma_srca_agpr", "mfma_run_max", "valu", "copies", "v_accvgpr_read_b32", "v_accvgpr_write_b32", "v_mov_b32",
             "v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32", "v_pk", "v_readlane_b32", "ds_read_b128", "s_waitcnt", "lds_cover_min", "lds_wait_cover_min", "branches", "scratch"]
     print(" ".join("%-12s" % c[-12:] for c in cols) + " kernel")
     for n, row in table.items():

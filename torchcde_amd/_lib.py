@@ -17,9 +17,9 @@ _CSRC = os.path.join(_HERE, "csrc")
 PHASE_TRACE = os.environ.get("CDE_PHASE_TRACE", "") == "1"
 SO_PATH = os.path.join(_HERE, "libcde_mi355x_trace.so" if PHASE_TRACE else "libcde_mi355x.so")
 SOURCES = ["library.hip", "interp_kernels.hip", "logsig_kernels.hip", "rk4_generic.hip", "rk4_mfma.hip", "rk4_split.hip", "rk4_wide.hip", "rk4_mlp_adjoint.hip", "rk4_mlp3.hip", "rk4_mlp_tiled.hip", "rk4_mlp_broad.hip",
-           "rk4_bf16x3.hip", "rk4_bf16x3_adjoint.hip", "rk4_backprop.hip", "revheun.hip", "rk4_adjoint_pair.hip", "dopri5.hip", "dopri5_adjoint.hip", "dopri5_mlp_adjoint.hip", "mlp_grad_reduce.hip", "api.hip"]
+           "rk4_bf16x3.hip", "rk4_bf16x3_duo.hip", "rk4_bf16x3_adjoint.hip", "rk4_backprop.hip", "revheun.hip", "rk4_adjoint_pair.hip", "dopri5.hip", "dopri5_adjoint.hip", "dopri5_mlp_adjoint.hip", "mlp_grad_reduce.hip", "api.hip"]
 HEADERS = [os.path.join(_CSRC, "cde_common.h"), os.path.join(_CSRC, "cde_mfma.h"), os.path.join(_CSRC, "cde_split.h"),
-           os.path.join(_CSRC, "cde_bf16x3.h"),
+           os.path.join(_CSRC, "cde_bf16x3.h"), os.path.join(_CSRC, "cde_bf16x3_duo.h"),
            os.path.join(_CSRC, "cde_dopri.h"), os.path.join(_CSRC, "cde_dopri_adj.h"), os.path.join(_CSRC, "cde_dopri_ctl.h"),
            os.path.join(_CSRC, "cde_mlp_adj.h"), os.path.join(_CSRC, "cde_mlp3.h"), os.path.join(_CSRC, "cde_mlp_tiled.h"),
            os.path.join(_CSRC, "cde_mlp_broad.h"),
@@ -36,8 +36,12 @@ if PHASE_TRACE:
 # rk4_bf16x3.hip (K2b alone): the flag took 484 of 530 v_accvgpr_read per RK step out of its one wave, and the AGPRs it
 # leaves empty hold K2b's weight pieces for the whole solve (cde_bf16x3.h: bx_load_resident); K3b, whose scratch the
 # flag would grow from 172 to 388 bytes per lane, is rk4_bf16x3_adjoint.hip and built without it.
+# rk4_bf16x3_duo.hip (K2bd): K2b's flag for the same reason; its vector work is written one instruction per step to sit in
+# the other group's MFMA gaps, so nothing may pack it (no SLP vectorizer: packed f32 does not hide beside MFMAs) and nothing
+# may turn the pairs its splits convert into vector loads of the arrays they come from (vector-combine: 24 B/lane of scratch).
 EXTRA_FLAGS = {"rk4_split.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "rk4_bf16x3.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+               "rk4_bf16x3_duo.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine"],
                "rk4_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "rk4_adjoint_pair.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
                "dopri5_adjoint.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
@@ -73,6 +77,7 @@ OPTIONS = {
     "k4am_no_small_reduce": (14, None), "k4am_sps": (15, None),
     "k4am_no_fsal": (16, {False: 0, True: 1, "accepted": 2, "rejected": 3}),
     "wide_scratch_bytes": (17, None),
+    "k2b_groups": (18, {"default": 0, 1: 1, 2: 2}),
 }
 
 

@@ -131,7 +131,8 @@ static int forward_typed(const Control& x, const AffineField& f, const ForwardIO
                          const StageTable& st, hipStream_t s) {
   if (variant == CDE_VARIANT_BF16X3 || auto_bf16x3(variant, n.B, n.C, n.H, dtype, f.act)) {
     if (!bf16x3_applicable(n.C, n.H, dtype, f.act)) return CDE_ERR_UNSUPPORTED;
-    return launch_forward_bf16x3<TT>(x, f, io, n, st, s);
+    if (option(CDE_OPT_K2B_GROUPS) == 1) return launch_forward_bf16x3<TT>(x, f, io, n, st, s);      // K2b, for A/B timing
+    return launch_forward_bf16x3_duo<TT>(x, f, io, n, st, s);
   }
   const Mfma mfma = pick_mfma(variant, n.C, n.H, dtype, f.act);
   if (mfma == Mfma::unsupported) return CDE_ERR_UNSUPPORTED;

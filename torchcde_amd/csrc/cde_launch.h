@@ -235,6 +235,10 @@ int launch_backprop_jacobian(const Control& x, const AffineField& f, const Backp
 template <typename TT>
 int launch_forward_bf16x3(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
                           hipStream_t s);
+// rk4_bf16x3_duo.hip: the same solve with the wave's 32 series as two interleaved groups of 16 (the default forward)
+template <typename TT>
+int launch_forward_bf16x3_duo(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                              hipStream_t s);
 template <typename TT>
 int launch_adjoint_bf16x3(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
                           float* partial, hipStream_t s);

@@ -12,7 +12,7 @@ static constexpr int64_t OPTION_DEFAULTS[] = {
     /* K3_FORM */ 0, /* K3_WAVES */ 0, /* K3D_WAVES */ 0, /* K2M_NO_SPLIT */ 0, /* K3M_NO_SPLIT */ 0, /* K3M_SPLIT4 */ 0,
     /* K3M_S8_TILES */ -1, /* K4_NO_SPLIT */ 0, /* K4M_NO_SPLIT */ 0, /* K4M_SPLIT_TILES */ -1, /* K4AM_WAVES */ 0,
     /* K4AM_S8_TILES */ -1, /* K4AM_SPLIT4 */ 0, /* K4AM_NO_SPLIT */ 0, /* K4AM_NO_SMALL_REDUCE */ 0, /* K4AM_SPS */ 0,
-    /* K4AM_NO_FSAL */ 0, /* WIDE_SCRATCH_BYTES */ 0};
+    /* K4AM_NO_FSAL */ 0, /* WIDE_SCRATCH_BYTES */ 0, /* K2B_GROUPS */ 0};
 static_assert(sizeof(OPTION_DEFAULTS) / sizeof(OPTION_DEFAULTS[0]) == CDE_OPT_COUNT, "one default per CDE_OPT_* key");
 // the live table: it starts out as cde_reset_options leaves it
 static struct Options {

@@ -1,6 +1,7 @@
 // rk4_bf16x3.hip -- K2b: the forward of the headline solve (f32 state, H <= 32, C <= 8, affine field) with its weight GEMM
-// on the BF16 matrix pipe at float32 accuracy (csrc/cde_bf16x3.h).  `variant = CDE_VARIANT_BF16X3` (cdeint(..., variant="bf16x3")),
-// and what AUTO takes at wave-per-tile batch sizes (api.hip).  The one-wave adjoint K3b is rk4_bf16x3_adjoint.hip: this file is
+// on the BF16 matrix pipe at float32 accuracy (csrc/cde_bf16x3.h).  Since round 13 `variant = CDE_VARIANT_BF16X3` and AUTO's
+// bf16 form run K2bd (rk4_bf16x3_duo.hip: the same solve as two interleaved 16-series groups per wave); this kernel is what
+// tuning option k2b_groups = 1 selects, kept for A/B timing and as the reference the new one is tested beside (api.hip).  The one-wave adjoint K3b is rk4_bf16x3_adjoint.hip: this file is
 // built with -amdgpu-mfma-vgpr-form (torchcde_amd/_lib.py), which keeps K2b's accumulators out of AGPRs and would cost K3b scratch.
 // The AGPRs hold the weights instead: the piece image is staged in LDS as in K3b, then every wave reads its lane's 48 entries
 // once (bx_load_resident) and the time loop evaluates the field with bx_field_resident -- the MFMAs take SrcA from a[...] and
