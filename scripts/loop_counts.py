@@ -7,7 +7,8 @@ loop are counted once each.  `--mfma N` takes the loop with exactly N MFMAs inst
 wave's stage loop of rk4_adjoint_pair.hip has 96).  Beside the instruction classes the table counts the MFMAs whose SrcA is
 read from AGPRs (`a[...]` as second operand, whatever the MFMA's shape), the longest run of MFMAs with no other vector
 instruction between them (`mfma_run_max`), the LDS reads and waits of the loop, and `lds_cover_min` / `lds_wait_cover_min`: how far
-ahead of the waits for them the LDS operands are requested (see lds_cover; `-` = the loop has no such wait)."""
+ahead of the waits for them the LDS operands are requested (see lds_cover; `-` = the loop has no such wait), and
+`vm_wait_cover_min` / `global_load_site_max`: the same for the loop's global loads (see vm_wait_cover)."""
 import os
 import re
 import subprocess
@@ -93,6 +94,39 @@ def lds_cover(body, gating_only=True, mfma_only=False):
     return cover
 
 
+def vm_wait_cover(body):
+    """For every s_waitcnt with a vmcnt field, the loop body taken as circular: the number of MFMAs between the wait and the
+    nearest global_load_* before it -- the matrix work a memory request has had to arrive under before the wave may stop
+    for it (vmcnt is one in-order counter: behind a branch the compiler waits for every load in flight, so a wait next to
+    a request drains it on the spot).  Empty when the loop has no such wait or no global load."""
+    if not any(b.startswith("global_load") for b in body):
+        return []
+    cover = []
+    for i, ln in enumerate(body):
+        if not (ln.startswith("s_waitcnt") and "vmcnt" in ln):
+            continue
+        n = 0
+        for b in reversed(body[i + 1:] + body[:i]):
+            if b.startswith("global_load"):
+                cover.append(n)
+                break
+            n += b.startswith("v_mfma")
+    return cover
+
+
+def global_load_site_max(body):
+    """the most global_load_* between two successive MFMAs of the loop (circular): the loads of one request site"""
+    first = next((i for i, b in enumerate(body) if b.startswith("v_mfma")), 0)
+    run = best = 0
+    for b in body[first:] + body[:first]:
+        if b.startswith("v_mfma"):
+            run = 0
+        elif b.startswith("global_load"):
+            run += 1
+            best = max(best, run)
+    return best
+
+
 def mfma_run_max(op):
     """the longest run of MFMAs with no other vector instruction between them (waits, s_nop and LDS reads do not end a run)"""
     run = best = 0
@@ -122,6 +156,8 @@ def classes(body):
             "ds_read_b128": op.count("ds_read_b128"), "lds_reads": sum(o.startswith("ds_read") for o in op),
             "s_waitcnt": op.count("s_waitcnt"), "lds_cover_min": min(lds_cover(body), default=None),
             "lds_wait_cover_min": min(lds_cover(body, gating_only=False), default=None),
+            "global_load": sum(o.startswith("global_load") for o in op), "global_load_site_max": global_load_site_max(body),
+            "vm_wait_cover_min": min(vm_wait_cover(body), default=None),
             # MFMAs whose SrcA (the second operand) is read straight from accumulator registers
             "mfma_srca_agpr": sum(bool(re.match(r"v_mfma\S*\s+[^,]+,\s*a\[", ln)) for ln in body)}
 
@@ -140,7 +176,8 @@ if __name__ == "__main__":
         mfma, rest = int(rest[1]), rest[2:]
     table = loop_table(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "", rest or None, mfma)
     cols = ["instructions", "mfma", "mfma_16x16x32_bf16", "mfma_srca_agpr", "mfma_run_max", "valu", "copies", "v_accvgpr_read_b32", "v_accvgpr_write_b32", "v_mov_b32",
-            "v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32", "v_pk", "v_readlane_b32", "ds_read_b128", "s_waitcnt", "lds_cover_min", "lds_wait_cover_min", "branches", "scratch"]
+            "v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32", "v_pk", "v_readlane_b32", "ds_read_b128", "s_waitcnt", "lds_cover_min", "lds_wait_cover_min", "global_load", "global_load_site_max", "vm_wait_cover_min",
+            "branches", "scratch"]
     print(" ".join("%-12s" % c[-12:] for c in cols) + " kernel")
     for n, row in table.items():
         print(" ".join("%-12s" % ("-" if row[c] is None else row[c]) for c in cols) + " " + n.replace("cde::", ""))

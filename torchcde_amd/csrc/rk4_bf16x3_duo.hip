@@ -8,7 +8,13 @@
 // two single-instruction steps of V -- with a scheduling barrier behind every slot and an empty asm on every step's result
 // (bxd_phase, bxd_vstep); __builtin_amdgcn_sched_group_barrier over a phase written as M then V did not hold the order: the
 // compiler emitted V whole, then 96 bare MFMAs (profiles/NOTES.md, round 13).  -DBXD_INTERLEAVE=0 builds the same source
-// with V behind M.  M_A(0) runs alone before the loop and one M_A past the last step is computed and dropped.  Weights
+// with V behind M.  M_A(0) runs alone before the loop and one M_A past the last step is computed and dropped.
+// The control: a phase opens with the slopes of vg's stage s + 1 from the row in its registers and, where the interval index
+// changes, requests the row of stage s + 2 into the same registers right there, in front of the phase's 96 MFMAs.  The
+// wave's global loads share one in-order counter and the request sits behind branches, so the next read of any row
+// register -- the next phase's first instruction, on the other group's row -- waits for every load in flight: requested
+// behind V, as first built (-DBXD_ROW_AT_TAIL=1), the row was drained where it was issued
+// (tests/test_kernel_forward_row_request.py holds the distance from request to wait).  Weights
 // resident in AGPRs, built with -amdgpu-mfma-vgpr-form, one wave per SIMD, as K2b; dead series clamp to series B - 1 and
 // store nothing, a tile beyond B returns before the loop.  `variant = "bf16x3"` and AUTO's bf16 form take this kernel;
 // tuning option k2b_groups = 1 selects K2b (api.hip).  The values differ from K2b's in the last bits: K = 32 is summed
@@ -18,6 +24,9 @@
 
 #ifndef BXD_INTERLEAVE
 #define BXD_INTERLEAVE 1
+#endif
+#ifndef BXD_ROW_AT_TAIL
+#define BXD_ROW_AT_TAIL 0                    // 1: the row request behind V, as first built (A/B timing: profiles/NOTES.md, round 14)
 #endif
 
 namespace cde {
@@ -143,6 +152,13 @@ __device__ __forceinline__ void bxd_phase(BxdGroup<DEGREE>& mg, BxdGroup<DEGREE>
   bx_wave_lds_sync();                        // the slopes `mg` wrote in the last phase are read in this one
   const int64_t idx1 = sp.idx[STAGE + 1];
   bxd_write_slopes<DEGREE>(vg.row, sp.frac[STAGE + 1], sp.width[STAGE + 1], vg.strip, q);  // of vg's next stage
+  // the row of the stage after that, into the registers just read, where the interval index changes.  Requested here, not
+  // behind V: the wait for a row is the next phase's first instruction and, behind these branches, one for every load in
+  // flight (vmcnt counts in order and the compiler cannot tell which loads were issued) -- this request included, so it
+  // has to be a phase old by then
+  const int64_t idx2 = sp.idx[STAGE + 2];
+  if constexpr (!BXD_ROW_AT_TAIL)
+    if (idx2 != idx1) vg.row = bxd_load_row<DEGREE>(coeffs, vg.sc, n_intervals, idx2, Cr, q);
   auto bias = [&](f32x4& acc, int t) { const float4 bb = b4[t * 4]; acc = f32x4{bb.x, bb.y, bb.z, bb.w}; };
   BxdTemps t;
   __builtin_amdgcn_sched_barrier(0);
@@ -167,8 +183,8 @@ __device__ __forceinline__ void bxd_phase(BxdGroup<DEGREE>& mg, BxdGroup<DEGREE>
 #pragma unroll
   for (int m = 0; m < 3; ++m) vg.zp[m] = __builtin_bit_cast(bf16x8, u32x4{t.pw[m][0], t.pw[m][1], t.pw[m][2], t.pw[m][3]});
   __builtin_amdgcn_sched_barrier(0);
-  const int64_t idx2 = sp.idx[STAGE + 2];                       // the row is requested a stage ahead of its slopes
-  if (idx2 != idx1) vg.row = bxd_load_row<DEGREE>(coeffs, vg.sc, n_intervals, idx2, Cr, q);
+  if constexpr (BXD_ROW_AT_TAIL)
+    if (idx2 != idx1) vg.row = bxd_load_row<DEGREE>(coeffs, vg.sc, n_intervals, idx2, Cr, q);
 }
 
 template <typename TT, int DEGREE>
