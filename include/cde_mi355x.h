@@ -66,8 +66,9 @@ enum { CDE_HIDDEN_RELU = 0, CDE_HIDDEN_SOFTPLUS = 1 };
 /* kernel selection for the fused solvers */
 enum {
   CDE_VARIANT_AUTO = 0,    /* f32: the MFMA kernels for H <= 32, C <= 8 (identity or tanh), the wide tile kernels for
-                              H <= 64, C <= 8 or H <= 32, C <= 16 (rk4 forward / adjoint, dopri5 forward); anything
-                              else: the generic kernels */
+                              H <= 64, C <= 8 or H <= 32, C <= 16 (rk4 forward / adjoint, dopri5 forward), the tiled
+                              kernels for H <= 32, 17 <= C <= 64 (rk4 forward / adjoint); anything else: the generic
+                              kernels */
   CDE_VARIANT_GENERIC = 1, /* VALU kernel: any H, C, f32 or f64                             */
   CDE_VARIANT_MFMA = 2,    /* fail with CDE_ERR_UNSUPPORTED unless the MFMA kernel applies   */
   CDE_VARIANT_SPLIT = 3,   /* MFMA, one workgroup (4 waves) per 16 series: the latency-oriented kernels for small
@@ -282,6 +283,12 @@ int cde_contract(const void* F, const void* dX, void* out, int64_t B, int64_t H,
  * runs the bf16x3 forward and the exact-f32 adjoint), 0 otherwise. */
 int cde_rk4_bf16x3_form(int64_t B, int64_t C, int64_t H, int dtype, int act, int variant);
 int cde_rk4_supported(int64_t C, int64_t H, int dtype, int act, int adjoint, int variant);
+/* 1 when an rk4 solve of the affine field with these dimensions takes the tiled wide-control kernels K2c / K3c under
+ * CDE_VARIANT_AUTO -- f32, 1 <= H <= 32, 17 <= C <= 64, act CDE_ACT_NONE or CDE_ACT_TANH: forward, and the adjoint for z0, W
+ * and b (no control or time gradients) -- 0 otherwise.  Every other variant keeps the kernels it had at these shapes
+ * (GENERIC: the VALU kernels; MFMA, SPLIT, BF16X3: CDE_ERR_UNSUPPORTED).  The backward pass streams its factor rows in chunks
+ * of RK steps within CDE_OPT_WIDE_SCRATCH_BYTES; cde_rk4_adjoint_workspace_bytes includes them. */
+int cde_rk4_affine_tiled_supported(int64_t C, int64_t H, int dtype, int act);
 
 /* ---------------------------------------------------------------------------------------------
  * K2  Fused fixed-grid RK4 (3/8 rule) solve of  dz/dt = f(t, z) dX/dt  for the affine family.

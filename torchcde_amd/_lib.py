@@ -16,13 +16,13 @@ _CSRC = os.path.join(_HERE, "csrc")
 # scripts/phase_trace.py).  A different file, so the product library is never the instrumented one.
 PHASE_TRACE = os.environ.get("CDE_PHASE_TRACE", "") == "1"
 SO_PATH = os.path.join(_HERE, "libcde_mi355x_trace.so" if PHASE_TRACE else "libcde_mi355x.so")
-SOURCES = ["library.hip", "interp_kernels.hip", "logsig_kernels.hip", "rk4_generic.hip", "rk4_mfma.hip", "rk4_split.hip", "rk4_wide.hip", "rk4_mlp_adjoint.hip", "rk4_mlp3.hip", "rk4_mlp_tiled.hip", "rk4_mlp_broad.hip",
+SOURCES = ["library.hip", "interp_kernels.hip", "logsig_kernels.hip", "rk4_generic.hip", "rk4_mfma.hip", "rk4_split.hip", "rk4_wide.hip", "rk4_affine_tiled.hip", "rk4_mlp_adjoint.hip", "rk4_mlp3.hip", "rk4_mlp_tiled.hip", "rk4_mlp_broad.hip",
            "rk4_bf16x3.hip", "rk4_bf16x3_duo.hip", "rk4_bf16x3_adjoint.hip", "rk4_backprop.hip", "revheun.hip", "rk4_adjoint_pair.hip", "dopri5.hip", "dopri5_adjoint.hip", "dopri5_mlp_adjoint.hip", "mlp_grad_reduce.hip", "api.hip"]
 HEADERS = [os.path.join(_CSRC, "cde_common.h"), os.path.join(_CSRC, "cde_mfma.h"), os.path.join(_CSRC, "cde_split.h"),
            os.path.join(_CSRC, "cde_bf16x3.h"), os.path.join(_CSRC, "cde_bf16x3_duo.h"),
            os.path.join(_CSRC, "cde_dopri.h"), os.path.join(_CSRC, "cde_dopri_adj.h"), os.path.join(_CSRC, "cde_dopri_ctl.h"),
            os.path.join(_CSRC, "cde_mlp_adj.h"), os.path.join(_CSRC, "cde_mlp3.h"), os.path.join(_CSRC, "cde_mlp_tiled.h"),
-           os.path.join(_CSRC, "cde_mlp_broad.h"),
+           os.path.join(_CSRC, "cde_mlp_broad.h"), os.path.join(_CSRC, "cde_affine_tiled.h"),
            os.path.join(_CSRC, "cde_launch.h"),
            os.path.join(_HERE, "..", "include", "cde_mi355x.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC"]
@@ -244,6 +244,7 @@ _SIGNATURES = {
     "cde_contract": (_i, [_p, _p, _p, _i64, _i64, _i64, _i, _p]),
     "cde_rk4_supported": (_i, [_i64, _i64, _i, _i, _i, _i]),
     "cde_rk4_bf16x3_form": (_i, [_i64, _i64, _i64, _i, _i, _i]),
+    "cde_rk4_affine_tiled_supported": (_i, [_i64, _i64, _i, _i]),
     "cde_rk4_forward_linear": (_i, [_p, _p, _i64, _i, _p, _p, _i, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i, _i,
                                     _i, _p, _p, _p]),
     "cde_rk4_forward_mlp": (_i, [_p, _p, _i64, _i, _p, _p, _i64, _p, _p, _i, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64,

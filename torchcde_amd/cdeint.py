@@ -2065,7 +2065,9 @@ def cdeint(X, func, z0, t, adjoint=True, backend="torchdiffeq", **kwargs):
             form = "bf16x3_forward" if (control_wants and variant == _lib.VARIANT_AUTO) else "bf16x3"
         else:
             form = "exact"
-        choice = choice.with_form(form)
+        tiled = (variant == _lib.VARIANT_AUTO and not control_wants and not wants_t
+                 and _lib.load().cde_rk4_affine_tiled_supported(C, H, _lib.dtype_enum(z0.dtype), field.act))
+        choice = choice.with_form(form, "tiled" if tiled else "")
     dispatch.record(choice, request)
 
     if choice.path == dispatch.STEPWISE:

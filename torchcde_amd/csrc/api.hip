@@ -126,6 +126,18 @@ static bool pick_wide(int variant, int64_t C, int64_t H, int dtype, int act) {
   return variant == CDE_VARIANT_AUTO && !mfma_applicable(C, H, dtype, act) && wide_applicable(C, H, dtype, act);
 }
 
+// Controls of 17 .. 64 channels on H <= 32 (rk4_affine_tiled.hip): the tiled kernels K2c / K3c under AUTO
+static bool pick_affine_tiled(int variant, int64_t C, int64_t H, int dtype, int act) {
+  return variant == CDE_VARIANT_AUTO && !mfma_applicable(C, H, dtype, act) && !wide_applicable(C, H, dtype, act) &&
+         affine_tiled_applicable(C, H, dtype, act);
+}
+// ... whose backward pass reserves the larger of its own and the generic kernels' need (cde_rk4_adjoint_workspace_bytes
+// answers before it knows the activation)
+static size_t affine_tiled_reserve(int64_t B, int64_t C, int64_t H, int64_t n_steps, size_t elem) {
+  const size_t a = affine_tiled_adjoint_workspace_bytes(B, C, H, n_steps), b = generic_adjoint_workspace_bytes(B, C, H, elem);
+  return a > b ? a : b;
+}
+
 template <typename T, typename TT>
 static int forward_typed(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, int dtype, int variant,
                          const StageTable& st, hipStream_t s) {
@@ -139,6 +151,7 @@ static int forward_typed(const Control& x, const AffineField& f, const ForwardIO
   if (mfma == Mfma::yes && pick_split(variant, n.B, false, f.act)) return launch_forward_split<TT>(x, f, io, n, st, s);
   if (mfma == Mfma::yes) return launch_forward_mfma<TT>(x, f, io, n, st, s);
   if (pick_wide(variant, n.C, n.H, dtype, f.act)) return launch_forward_wide<TT>(x, f, io, n, st, s);
+  if (pick_affine_tiled(variant, n.C, n.H, dtype, f.act)) return launch_forward_affine_tiled<TT>(x, f, io, n, st, s);
   return launch_forward_generic<T, TT>(x, f, io, n, st, s);
 }
 
@@ -147,7 +160,7 @@ template <typename T, typename TT>
 static int adjoint_typed(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, int dtype, int variant,
                          Workspace ws, hipStream_t s) {
   const bool bx = variant == CDE_VARIANT_BF16X3 || (auto_bf16x3(variant, n.B, n.C, n.H, dtype, f.act) && !io.grad_coeffs);
-  bool use_split = false, use_mfma = true, use_wide = false;
+  bool use_split = false, use_mfma = true, use_wide = false, use_tiled = false;
   if (bx) {
     if (!bf16x3_applicable(n.C, n.H, dtype, f.act) || io.grad_coeffs) return CDE_ERR_UNSUPPORTED;
   } else {
@@ -158,11 +171,13 @@ static int adjoint_typed(const Control& x, const AffineField& f, const AdjointIO
     use_split = use_mfma && pick_split(variant, n.B, io.grad_coeffs != nullptr, f.act);
     if (variant == CDE_VARIANT_SPLIT && !use_split) return CDE_ERR_UNSUPPORTED;
     use_wide = !use_mfma && pick_wide(variant, n.C, n.H, dtype, f.act);
+    use_tiled = !use_mfma && !use_wide && pick_affine_tiled(variant, n.C, n.H, dtype, f.act);
   }
   const StageWorkspace layout(io.n_sgrid, sizeof(T));
   const size_t part_bytes = use_split ? split_adjoint_partial_bytes(n.B)
                             : use_mfma ? mfma_adjoint_partial_bytes(n.B)
                             : use_wide ? wide_adjoint_workspace_bytes(n.B, n.C, n.H, io.n_sgrid - 1)
+                            : use_tiled ? affine_tiled_reserve(n.B, n.C, n.H, layout.n_steps, sizeof(T))
                                        : generic_adjoint_workspace_bytes(n.B, n.C, n.H, sizeof(T));
   if (ws.bytes < layout.total(part_bytes)) return CDE_ERR_WORKSPACE;
   const StageBuffers st = layout.table(ws.base);
@@ -180,6 +195,7 @@ static int adjoint_typed(const Control& x, const AffineField& f, const AdjointIO
   if (use_split) return launch_adjoint_split<TT>(x, f, io, n, st, (float*)partial, s);
   if (use_mfma) return launch_adjoint_mfma<TT>(x, f, io, n, st, (float*)partial, s);
   if (use_wide) return launch_adjoint_wide<TT>(x, f, io, n, st, partial, s);
+  if (use_tiled) return launch_adjoint_affine_tiled<TT>(x, f, io, n, st, partial, s);
   return launch_adjoint_generic<T, TT>(x, f, io, n, st, partial, s);
 }
 
@@ -201,7 +217,13 @@ extern "C" int cde_rk4_supported(int64_t C, int64_t H, int dtype, int act, int a
   const Mfma mfma = pick_mfma(variant, C, H, dtype, act);
   if (mfma != Mfma::no) return mfma == Mfma::yes ? 1 : 0;
   if (pick_wide(variant, C, H, dtype, act)) return 1;
+  if (pick_affine_tiled(variant, C, H, dtype, act)) return 1;
   return generic_applicable(C, H, dtype == CDE_F64 ? 8 : 4, adjoint != 0) ? 1 : 0;
+}
+
+// the rule of pick_affine_tiled under CDE_VARIANT_AUTO, for the host's dispatch record
+extern "C" int cde_rk4_affine_tiled_supported(int64_t C, int64_t H, int dtype, int act) {
+  return pick_affine_tiled(CDE_VARIANT_AUTO, C, H, dtype, act) ? 1 : 0;
 }
 
 extern "C" int cde_rk4_forward_linear(const void* coeffs, const void* knots, int64_t n_intervals, int degree,
@@ -264,6 +286,7 @@ extern "C" size_t cde_rk4_adjoint_workspace_bytes(int64_t B, int64_t C, int64_t 
     const size_t wb = wide_adjoint_workspace_bytes(B, C, H, layout.n_steps);
     b = wb > b ? wb : b;
   }
+  if (!use_mfma && pick_affine_tiled(variant, C, H, dtype, CDE_ACT_NONE)) b = affine_tiled_reserve(B, C, H, layout.n_steps, elem);
   if (variant == CDE_VARIANT_MFMA || variant == CDE_VARIANT_SPLIT) return layout.total(a);
   if (variant == CDE_VARIANT_GENERIC || !use_mfma) return layout.total(b);
   return layout.total(a > b ? a : b);

@@ -266,6 +266,16 @@ size_t wide_grad_reduce_partial_bytes(int M, int N);
 int launch_wide_grad_reduce(const float* G, const float* Z, int64_t rows, int M, int N, float* acc, float* partial,
                             hipStream_t s);
 
+// ---------------------------------------------------------------- rk4_affine_tiled.hip (H <= 32, 17 <= C <= 64)
+bool affine_tiled_applicable(int64_t C, int64_t H, int dtype, int act);
+size_t affine_tiled_adjoint_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t n_steps);
+template <typename TT>
+int launch_forward_affine_tiled(const Control& x, const AffineField& f, const ForwardIO& io, const Shape& n, const StageTable& st,
+                                hipStream_t s);
+template <typename TT>
+int launch_adjoint_affine_tiled(const Control& x, const AffineField& f, const AdjointIO& io, const Shape& n, const StageTable& st,
+                                void* scratch, hipStream_t s);
+
 // ---------------------------------------------------------------- rk4_mlp_adjoint.hip (sweeps of the two-layer field)
 size_t mlp_adjoint_image_bytes();                              // (cde_mlp_adj.h declares these two for the kernel files)
 int launch_mlp_adjoint_images(const void* W1, const void* b1, int64_t width, const void* W2, const void* b2, int64_t C,

@@ -4,6 +4,9 @@
 // linear control, ACT_NONE or ACT_TANH.  This is the correctness path (small configs, float64,
 // odd shapes) and the on-device cross-check of the MFMA kernels; the headline configuration
 // (f32, H=32, C=8) runs rk4_mfma.hip instead.
+// What still reaches it under CDE_VARIANT_AUTO: float64 states; f32 with H > 64, with H > 32 and
+// C > 8, or with C > 64 (H <= 64 with C <= 8 and H <= 32 with C <= 16 run rk4_wide.hip, H <= 32 with
+// 17 <= C <= 64 rk4_affine_tiled.hip).  variant = "generic" reaches it at every shape.
 //
 // Work decomposition: a workgroup of NT = NS*H lanes owns NS series at a time (grid-stride over
 // series tiles); lane (s, h) keeps its own RK state for hidden unit h of series s in registers.

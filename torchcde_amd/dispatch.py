@@ -51,16 +51,22 @@ Request = collections.namedtuple("Request", [
 # three-piece splits: the default for the headline field above 16384 series), "bf16x3_forward" (the same forward, the
 # exact-f32 adjoint: control gradients), "exact" (the f32 kernels, e.g. variant="mfma"); "" for every other path
 # (an attribute beside the tuple, so a Choice still compares equal to its (path, reason))
+# family: which kernels a fused rk4 solve of the affine field runs where `form` does not say -- "tiled" for K2c / K3c
+# (csrc/rk4_affine_tiled.hip: float32, H <= 32, 17 to 64 control channels, variant AUTO), "" otherwise; an attribute by the
+# same mechanism as `form`
 class Choice(collections.namedtuple("Choice", ["path", "reason"])):
     form = ""
+    family = ""
 
-    def with_form(self, form):
+    def with_form(self, form, family=""):
         c = Choice(*self)
         c.form = form
+        c.family = family
         return c
 
 FUSED_PATHS = (
-    "rk4",                    # K2 / K3 (+ split, wide, generic variants behind CDE_VARIANT_AUTO), incl. time / control gradients
+    "rk4",                    # K2 / K3 (+ split, wide, tiled wide-control (K2c / K3c: Choice.family "tiled") and generic
+                              # variants behind CDE_VARIANT_AUTO), incl. time / control gradients on the 32 x 8 tiles
     "dopri5_forward",         # K4 (MFMA, wide or generic attempt kernel), nothing to differentiate
     "dopri5_adjoint",         # K4 + K4a: the reference's default training call
     "mlp_rk4_forward",        # K2m (three-layer field: K2m3)
